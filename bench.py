@@ -10,6 +10,11 @@
         N fresh ranks, relays rank 0's JSON line and exits with the child's code.
     python bench.py --gpus 2 --dry-run-dist   # CPU rehearsal of the N-rank path: gloo ranks, host logic only
     python bench.py --config {2,4,5} ...                               # the other BASELINE configurations
+    --dump-outputs DIR: after the timed steps, write what the last one computed (losses, seeded samples of the updated
+        parameters, gradients and EWMA generator) as DIR/<name>.npy; the inputs are seeded, so two builds compare
+        output for output.
+    --full: also the figures that take work of their own (roofline, executed FLOPs, cpu_baseline; below).  A plain run
+        sets up, warms up, times the K steps, dumps if asked and prints the record.
 
 Default (= --config 3): images/sec of the full G+D step (1 D-iteration + 1 G-iteration), StyleGAN 1024^2, batch 32
 per GPU, fp32, nonsaturating loss + R1 (lambda 10) + drift, stabilised phase at the final resolution, synthetic
@@ -20,7 +25,7 @@ FFHQ-shaped data resident in HBM.
               of the stabilised 256^2 phase are timed (WGAN + WGAN-GP + drift, batch 32).
   --config 5: ResNet GAN 64^2, batch 64, WGAN + WGAN-GP; a step = one main iteration = 1 G + 5 critic iterations.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  With --full it also holds:
 ``roofline``: the dominant kernel family is the MFMA implicit-GEMM 3x3 conv; the configuration's north-star instance
 is timed with device events on the launch stream INSIDE the timed steps and priced with its algorithmic FLOPs
 (2*9*Cin*Cout*H*W*B); ``kernel`` / ``grid`` are read back from the library (the symbol that was dispatched).
@@ -32,6 +37,7 @@ the reference's pass count and is a label, not a roofline fract
 batch, 1 warm-up + 3 timed steps, median - a reported baseline, not a target.
 """
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -50,7 +56,7 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0                   # MI355X_MICROARCH.md: dense bf
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument('--gpus', type=int, default=1)
-    p.add_argument('--steps', type=int, default=None)
+    p.add_argument('--steps', type=int, default=None, help='timed steps (default: 3; config 2: 20, 4: 10, 5: 5)')
     p.add_argument('--warmup', type=int, default=None,
                    help='untimed steps (default 1; config 2: 5, so that the step graphs are captured before the timed region)')
     p.add_argument('--config', type=int, choices=(2, 3, 4, 5), default=3, help='BASELINE.json configuration (3 = headline)')
@@ -67,6 +73,10 @@ def parse():
     p.add_argument('--step-graph', choices=('auto', '0', '1'), default='auto',
                    help='replay the stabilised iteration as HIP graphs (gan_lab_amd/graphs.py GraphedStep): auto = the '
                         "learner's own rule (single process, resolutions up to 256 - the launch-bound configurations)")
+    p.add_argument('--full', action='store_true',
+                   help='also measure roofline / executed FLOPs (an extra counted step) / cpu_baseline, as listed above')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     p.add_argument('--dry-run-dist', action='store_true',
                    help='rehearse the multi-rank path on CPU: gloo ranks build a small learner (host logic only), '
                         'broadcast its arenas and run the bucketed gradient exchange; no GPU is touched')
@@ -77,7 +87,9 @@ def parse():
     a.res = a.res or dflt[1]
     a.batch = a.batch or dflt[2]
     a.dtype = a.dtype or dflt[3]
-    a.steps = a.steps or dflt[4]
+    a.steps = dflt[4] if a.steps is None else a.steps
+    if a.steps < 1:
+        p.error('--steps must be at least 1')
     if a.warmup is None:
         a.warmup = 5 if a.config == 2 else 1
     return a
@@ -338,6 +350,36 @@ class FlopCounter(object):
     @property
     def total(self):
         return sum(self.by_kind.values())
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ------------------------------------------------------------------------------------------------------------------
+DUMP_SAMPLE = 2 ** 21          # entries kept of a larger flat buffer: 8 MiB each, five buffers + the losses < 64 MB
+
+
+def dump_outputs(out_dir, learner, ld, lg):
+    """What the last timed step computed, as float32 .npy files: the two losses and the state the step updated - the
+    parameter and gradient arenas of both networks and the EWMA generator.  A buffer longer than ``DUMP_SAMPLE`` is
+    sampled at fixed indices (seeded by its length), so two runs with the same arguments dump the same entries."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'loss_d': ld, 'loss_g': lg}
+    for tag, arena in (('g', getattr(learner, 'arena_g', None)), ('d', getattr(learner, 'arena_d', None))):
+        if arena is not None:
+            arrays['params_' + tag], arrays['grads_' + tag] = arena.flat, arena.gflat
+    ewma = getattr(learner, 'ewma', None)
+    if ewma is not None and torch.is_tensor(getattr(ewma, 'flat', None)):
+        arrays['params_g_ewma'] = ewma.flat
+    for name, v in arrays.items():
+        if v is None:
+            continue
+        a = v.detach().float().reshape(-1) if torch.is_tensor(v) else torch.tensor([float(v)])
+        if a.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(a.numel()).choice(a.numel(), DUMP_SAMPLE, replace=False))
+            a = a[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), a.cpu().numpy().astype(np.float32))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -642,6 +684,10 @@ def main():
     from gan_lab_amd import _lib, ops as _ops
     _lib.lib()
     torch.manual_seed(1234 + rank)      # parameter init differs per rank on purpose: rank 0's values are broadcast
+    # the style-mixing coin is numpy's global generator (np.random.rand(), as in the reference): seeded too, so that a
+    # run repeats its inputs exactly (--dump-outputs compares builds output for output)
+    import numpy as np
+    np.random.seed(1234 + rank)
 
     wl = Workload(a, torch)             # builds the learner (device RNG seeded from config.random_seed + rank)
 
@@ -658,23 +704,27 @@ def main():
     flops = FlopCounter(_ops)
     barrier()
     t0 = time.perf_counter()
-    with insitu, insitu_top:
+    # --full: the roofline's in-step timers bracket launches of the timed steps (plain run: nothing but the steps)
+    with (insitu if a.full else contextlib.nullcontext()), (insitu_top if a.full else contextlib.nullcontext()):
         for _ in range(a.steps):
             ld, lg = wl.step()
     barrier()
     dt = time.perf_counter() - t0
-    # executed conv FLOPs of a step: counted on ONE more step outside the timed region (every stabilised step launches
-    # the same kernels; the Python observer would cost a launch-bound configuration ~1 us per launch inside it)
-    with flops:
-        prev = os.environ.get('GANLAB_STEP_GRAPH')
-        os.environ['GANLAB_STEP_GRAPH'] = '0'          # the observer sits in the Python launchers: count an eager step
-        try:
-            wl.step()
-        finally:
-            if prev is None:
-                del os.environ['GANLAB_STEP_GRAPH']
-            else:
-                os.environ['GANLAB_STEP_GRAPH'] = prev
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, wl.learner, ld, lg)
+    if a.full:
+        # executed conv FLOPs of a step: counted on ONE more step outside the timed region (every stabilised step launches
+        # the same kernels; the Python observer would cost a launch-bound configuration ~1 us per launch inside it)
+        with flops:
+            prev = os.environ.get('GANLAB_STEP_GRAPH')
+            os.environ['GANLAB_STEP_GRAPH'] = '0'          # the observer sits in the Python launchers: count an eager step
+            try:
+                wl.step()
+            finally:
+                if prev is None:
+                    del os.environ['GANLAB_STEP_GRAPH']
+                else:
+                    os.environ['GANLAB_STEP_GRAPH'] = prev
     torch.cuda.synchronize()
     exchange = None
     if use_dist:
@@ -720,20 +770,24 @@ def main():
                                                                              'bf16 products, fp32 accumulate')),
             'config': {'workload': wl.what, 'baseline_config': a.config, 'global_batch': world * a.batch,
                        'per_gpu_batch': a.batch, 'parallelism': f'dp{world}' if world > 1 else 'single'},
-            # executed: what the launchers ran (per GPU) over the MFMA peak of one GPU - a roofline fraction of the step
-            'executed_tflops_step': round(exec_tflops, 2),
-            # with the split-product kernels on, the thick layers' FLOPs run on the bf16 matrix cores (six bf16 products per fp32
-            # product): fp32-equivalent FLOPs over the fp32 peak is then a speed label, not a fraction of one pipe's roofline
-            'frac_of_mfma_peak_step': None if x3_on else round(exec_tflops / peak, 4),
-            'fp32_equivalent_over_fp32_mfma_peak_step': round(exec_tflops / peak, 4) if x3_on else None,
-            'executed_conv_tflop_per_step': round(flops.total / 1e12, 3),
-            'executed_conv_tflop_by_pass': {k: round(v / 1e12, 3) for k, v in flops.by_kind.items()},
-            'conv_launches_per_step': flops.launches,
             # algorithmic: the reference's pass count (4 G + 14 D conv passes) - NOT a roofline fraction:
             # the implementation executes fewer FLOPs (stride-2 fusion, shared D(real), no discarded weight gradients)
             'algorithmic_tflops_step': round(ips / world * algo, 2) if algo else None,
-            'loss_d': ld, 'loss_g': lg, 'peak_mem_gib': round(peak_mem, 1),
+            'loss_d': ld, 'loss_g': lg, 'peak_mem_gib': round(peak_mem, 1), 'full': bool(a.full),
         }
+        if a.full:
+            out.update({
+                # executed: what the launchers ran (per GPU) over the MFMA peak of one GPU - a roofline fraction of the step
+                'executed_tflops_step': round(exec_tflops, 2),
+                # with the split-product kernels on, the thick layers' FLOPs run on the bf16 matrix cores (six bf16 products per
+                # fp32 product): fp32-equivalent FLOPs over the fp32 peak is then a speed label, not a fraction of one pipe's
+                # roofline
+                'frac_of_mfma_peak_step': None if x3_on else round(exec_tflops / peak, 4),
+                'fp32_equivalent_over_fp32_mfma_peak_step': round(exec_tflops / peak, 4) if x3_on else None,
+                'executed_conv_tflop_per_step': round(flops.total / 1e12, 3),
+                'executed_conv_tflop_by_pass': {k: round(v / 1e12, 3) for k, v in flops.by_kind.items()},
+                'conv_launches_per_step': flops.launches,
+            })
         if exchange is not None:
             out['gradient_exchange'] = exchange
         sg = getattr(wl.learner, '_step_graph', None)
@@ -742,7 +796,7 @@ def main():
         out.update(wl.extra)
     del wl
     torch.cuda.empty_cache()
-    if rank == 0:
+    if rank == 0 and a.full:
         def with_insitu(r, timer):
             ms_t, n_t = timer.mean_ms()
             if r is not None and ms_t is not None:
@@ -776,6 +830,7 @@ def main():
                                                           a.cpu_baseline_steps)
             else:
                 out['cpu_baseline'] = cpu_baseline_resnet(torch, a.res, min(a.batch, 16), a.cpu_baseline_steps)
+    if rank == 0:
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + '\n').encode())
     if use_dist:

@@ -10,9 +10,29 @@ The per-layer noise of StyleGAN is an explicit input of the captured forward (th
 by-value kernel arguments and would be frozen inside a graph): it is redrawn into the static buffers before every
 replay, or pinned by the caller.
 """
+import contextlib
+import gc
+
 import torch
 
 from . import ops, rng
+
+
+@contextlib.contextmanager
+def _no_collector():
+    """Keep Python's cyclic collector out of a capture.  A collection that starts inside one runs the finalizers of
+    whatever unreachable cycles exist at that moment - another learner's step graphs, their graph executables, pools and
+    events.  Destroyed while a stream was capturing, they aborted the process (two learners trained one after the other
+    in one process: tests/test_gpu_learner.py::test_training_is_bitwise_reproducible).  The garbage is collected before
+    the capture instead."""
+    was = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 class GraphedGenerator(object):
@@ -49,7 +69,7 @@ class GraphedGenerator(object):
         if follow_weight_updates:
             ops.bump_weight_epoch()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with _no_collector(), torch.cuda.graph(self.graph):
             self.out = self._forward()
         if follow_weight_updates:
             # The capture inserted packed-weight tensors into the cache that live in the graph's private pool and that
@@ -147,7 +167,7 @@ class _StepGraphs(object):
                 # (a capture that an exception - or Ctrl-C - cuts short ends empty: torch says so in a warning of its own; the
                 # graph object is dropped below, nothing is left behind)
                 warnings.filterwarnings('ignore', message='The CUDA Graph is empty')
-                with torch.cuda.graph(graph, pool=self.pool):
+                with _no_collector(), torch.cuda.graph(graph, pool=self.pool):
                     self.losses[key[0]].copy_(fn())
         except Exception as exc:      # an op that cannot be captured (a host sync, an allocation outside the pool): no retry
             self.failed = exc

@@ -609,6 +609,37 @@ def golden_checkpoint_stylegan():
     save('ref_stylegan_ckpt_expect.npz', **out)
 
 
+def golden_refformat():
+    """The reverse direction of the checkpoint format: a file written by THIS package's ``save_model(...,
+    reference_format=True)`` (tests/test_checkpoint_reference.py ``_product_learner``: mid fade-in at 8x8, Adam moments,
+    EWMA generator, truncation trick) is loaded by the REAL reference learner and checked (``check_reference_reads``);
+    only then is its fingerprint stored - what tests/test_checkpoint_reference.py requires of a freshly written file."""
+    import json
+    import pathlib
+    import pytest
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_checkpoint_reference as TC
+    for kind in ('progan', 'stylegan'):
+        tmp = pathlib.Path(tempfile.mkdtemp(prefix='ganlab_refformat_'))
+        mp = pytest.MonkeyPatch()
+        try:
+            L = TC._product_learner(kind, mp, tmp)
+            path = str(tmp / f'{kind}_model.tar')
+            L.save_model(path, reference_format=True)
+            cfg, _ = (_ref_stylegan_setup if kind == 'stylegan' else _ref_progan_setup)(num_main_iters=3)
+            TC.check_reference_reads(kind, L, path, ns, cfg)
+        finally:
+            mp.undo()
+        name, fp = f'refformat_{kind}_ckpt.json', TC.checkpoint_fingerprint(path, tmp)
+        with open(os.path.join(HERE, name), 'w') as f:
+            json.dump({'written_by': "gan_lab_amd save_model(reference_format=True) of test_checkpoint_reference's "
+                                     '_product_learner',
+                       'checked_by': "the reference's own load_model (test_checkpoint_reference.check_reference_reads)",
+                       'fingerprint': fp}, f)
+        print(f'wrote {name}: {os.path.getsize(os.path.join(HERE, name)) / 1024:.1f} KiB')
+
+
 def golden_schedule():
     """Host-logic trace of the REAL reference ProGANLearner.train over a 4 -> 8 -> 16 schedule
     (BASELINE config #1 shape: 64 random images, batch 4): per main iteration the resolution, phase,
@@ -830,6 +861,7 @@ if __name__ == '__main__':
         'data': golden_data,
         'checkpoint': golden_checkpoint,
         'checkpoint_sg': golden_checkpoint_stylegan,
+        'refformat': golden_refformat,
         'resnet64': lambda: golden_resnet(64, 'resnet64', fmap_g=2, fmap_d=2),
         'resnet32': lambda: golden_resnet(32, 'resnet32', fmap_g=8, fmap_d=8),
         # --nonlinearity tanh as the hidden activation (config.py:208, resnetgan/learner.py:180-181)

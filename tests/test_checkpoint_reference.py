@@ -1,39 +1,112 @@
 """Checkpoint wire-format compatibility, reverse direction: a file written by
 ``save_model(..., reference_format=True)`` of THIS package is read by the REFERENCE's own ``load_model``
-(gan_lab/progan/learner.py:1305-1448, gan_lab/stylegan/learner.py:503-640), imported here from /root/reference.
-Host logic only (``GANLAB_HOST_LOGIC_ONLY``: CPU tensors, no kernels).  Skipped where the reference is absent (the
-GPU box): the forward direction (reference-written files -> this package) is covered there by committed fixtures."""
+(gan_lab/progan/learner.py:1305-1448, gan_lab/stylegan/learner.py:503-640).
+Host logic only (``GANLAB_HOST_LOGIC_ONLY``: CPU tensors, no kernels).
+
+The reference is not part of this repository.  ``tests/golden/make_golden.py --only refformat`` writes the file with
+this package, has the reference's learner load it and checks what it read (``check_reference_reads`` below), and only
+then stores the file's fingerprint (``tests/golden/refformat_<kind>_ckpt.json``: every pickled class by name, every
+key and scalar, a SHA-256 of every tensor's bytes).  The test writes the same file again and requires the same
+fingerprint: the reference's reader then reads exactly what it was checked to read.  The forward direction
+(reference-written files -> this package) is covered by the committed reference files (tests/golden/ref_*_ckpt.tar)."""
 import contextlib
 import functools
+import hashlib
 import io
+import json
 import os
-import sys
+import pickle
+import zipfile
+from collections import OrderedDict
 
-import numpy as np
 import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
-pytestmark = pytest.mark.skipif(not os.path.isdir('/root/reference/gan_lab'),
-                                reason='needs the reference checkout (build container only)')
 
 
-@pytest.fixture(scope='module')
-def ref():
-    """tests/golden/make_golden.py with the reference imported through its stubs - and everything it put on
-    ``sys.path`` / into ``sys.modules`` (the reference's top-level ``_int``, ``utils``, ``progan`` ... packages, the
-    ``torchvision`` / ``indexed`` stand-ins) taken out again afterwards, so later tests see a clean interpreter."""
-    path0, mods0 = list(sys.path), set(sys.modules)
-    sys.path.insert(0, GOLDEN)
-    with contextlib.redirect_stdout(io.StringIO()):
-        import make_golden as MG
-    yield MG
-    sys.path[:] = path0
-    for name in set(sys.modules) - mods0:
-        f = getattr(sys.modules[name], '__file__', None) or ''
-        if '/root/reference' in f or f.startswith(GOLDEN) or name.split('.')[0] in ('torchvision', 'indexed'):
-            del sys.modules[name]
+class _Pickled(object):
+    """Stand-in for any class a checkpoint pickles (other than the containers and tensor rebuilds below): what it was
+    built from, kept by the class's module and name."""
+    ref, args, state = None, (), None
+
+    def __init__(self, *args):
+        self.args = args
+        self.state = None
+
+    def __setstate__(self, state):
+        self.state = state
+
+
+class _FingerprintReader(pickle.Unpickler):
+    """Reads ``data.pkl`` of a torch zip checkpoint without importing anything it names."""
+
+    def __init__(self, f, storages):
+        super().__init__(f)
+        self.storages = storages
+
+    def find_class(self, module, name):
+        if (module, name) == ('collections', 'OrderedDict'):
+            return OrderedDict
+        if module in ('builtins', '__builtin__', 'copyreg'):
+            return super().find_class(module, name)
+        if (module, name) == ('torch._utils', '_rebuild_tensor_v2'):
+            return lambda storage, offset, size, stride, *rest: ('tensor', storage, offset, list(size), list(stride))
+        if module == 'pathlib':
+            return lambda *parts: ('path', os.path.join(*parts) if parts else '')
+        if module == 'torch' and name.endswith('Storage'):
+            return 'torch.' + name
+        return type(name, (_Pickled,), {'ref': module + '.' + name})
+
+    def persistent_load(self, pid):
+        _, stype, key, _, numel = pid
+        return ['storage', str(stype if isinstance(stype, str) else getattr(stype, '__name__', stype)), int(numel),
+                hashlib.sha256(self.storages[key]).hexdigest()]
+
+
+def _canon(x, tmp):
+    """JSON-able, order-preserving, type-tagged form of an unpickled checkpoint (``tmp``: the directory the learner was
+    configured with, replaced by a placeholder)."""
+    if isinstance(x, _Pickled):
+        return ['obj', x.ref, _canon(list(x.args), tmp), _canon(x.state, tmp)]
+    if isinstance(x, tuple) and x and x[0] == 'tensor':
+        return ['tensor'] + [_canon(v, tmp) for v in x[1:]]
+    if isinstance(x, tuple) and x and x[0] == 'path':
+        return ['path', x[1].replace(str(tmp), '<tmp>', 1)]
+    if isinstance(x, dict):
+        return [type(x).__name__, [[_canon(k, tmp), _canon(v, tmp)] for k, v in x.items()]]
+    if isinstance(x, (set, frozenset)):
+        return ['set', sorted((_canon(v, tmp) for v in x), key=json.dumps)]
+    if isinstance(x, (list, tuple)):
+        return [type(x).__name__, [_canon(v, tmp) for v in x]]
+    if x is None or isinstance(x, (bool, int, float, str)):
+        return [type(x).__name__, x]
+    if isinstance(x, bytes):
+        return ['bytes', x.hex()]
+    return ['?', repr(x)]
+
+
+def checkpoint_fingerprint(path, tmp):
+    with zipfile.ZipFile(path) as z:
+        names = z.namelist()
+        top = names[0].split('/')[0]
+        storages = {n.split('/')[-1]: z.read(n) for n in names if n.startswith(top + '/data/')}
+        data = z.read(top + '/data.pkl')
+    return json.loads(json.dumps(_canon(_FingerprintReader(io.BytesIO(data), storages).load(), tmp)))
+
+
+def _first_difference(a, b, where='checkpoint'):
+    if type(a) is not type(b) or (not isinstance(a, list) and a != b):
+        return f'{where}: {str(a)[:120]} != {str(b)[:120]}'
+    if isinstance(a, list):
+        if len(a) != len(b):
+            return f'{where}: {len(a)} entries != {len(b)}'
+        for i, (u, v) in enumerate(zip(a, b)):
+            d = _first_difference(u, v, f'{where}[{i}]')
+            if d:
+                return d
+    return None
 
 
 def _product_learner(kind, monkeypatch, tmp_path):
@@ -80,27 +153,18 @@ def _product_learner(kind, monkeypatch, tmp_path):
     return L
 
 
-@pytest.mark.parametrize('kind', ['progan', 'stylegan'])
-def test_reference_loads_a_checkpoint_written_in_reference_format(kind, ref, monkeypatch, tmp_path):
-    MG = ref
-    ns = MG.ns
-    L = _product_learner(kind, monkeypatch, tmp_path)
-    path = str(tmp_path / f'{kind}_model.tar')
-    L.save_model(path, reference_format=True)
-    from gan_lab_amd import checkpoint as ckpt
-    assert ckpt.is_reference_format(ckpt.load_checkpoint(path))
-    # ---- the reference's own learner reads it ----
+def check_reference_reads(kind, L, path, ns, cfg):
+    """What the reference's own learner (``ns``: the imported reference modules, ``cfg``: its configuration) must make
+    of ``path``, written by ``L.save_model(path, reference_format=True)``.  Run by tests/golden/make_golden.py before it
+    stores the file's fingerprint."""
     with contextlib.redirect_stdout(io.StringIO()):
-        if kind == 'stylegan':
-            cfg, _ = MG._ref_stylegan_setup(num_main_iters=3)
-            R = ns.sl.StyleGANLearner(cfg)
-        else:
-            cfg, _ = MG._ref_progan_setup(num_main_iters=3)
-            R = ns.pl.ProGANLearner(cfg)
+        R = ns.sl.StyleGANLearner(cfg) if kind == 'stylegan' else ns.pl.ProGANLearner(cfg)
         orig = torch.load
-        monkeypatch.setattr(torch, 'load', functools.partial(orig, weights_only=False))   # torch >= 2.6 default
-        R.load_model(path)
-        monkeypatch.setattr(torch, 'load', orig)
+        torch.load = functools.partial(orig, weights_only=False)     # torch >= 2.6 default
+        try:
+            R.load_model(path)
+        finally:
+            torch.load = orig
     assert R.gen_model.curr_res == 8 and R.gen_model.fade_in_phase and abs(R.gen_model.alpha - 0.375) < 1e-12
     for mine, theirs in ((L.gen_model, R.gen_model), (L.disc_model, R.disc_model)):
         sd_a, sd_b = mine.state_dict(), theirs.state_dict()
@@ -140,6 +204,20 @@ def test_reference_loads_a_checkpoint_written_in_reference_format(kind, ref, mon
     with torch.no_grad():
         img = R.gen_model(torch.randn(2, 16))
     assert img.shape == (2, 3, 8, 8) and torch.isfinite(img).all()
+
+
+@pytest.mark.parametrize('kind', ['progan', 'stylegan'])
+def test_reference_loads_a_checkpoint_written_in_reference_format(kind, monkeypatch, tmp_path):
+    L = _product_learner(kind, monkeypatch, tmp_path)
+    path = str(tmp_path / f'{kind}_model.tar')
+    L.save_model(path, reference_format=True)
+    from gan_lab_amd import checkpoint as ckpt
+    assert ckpt.is_reference_format(ckpt.load_checkpoint(path))
+    # ---- the very file the reference's own learner was checked to read (make_golden.py --only refformat) ----
+    with open(os.path.join(GOLDEN, f'refformat_{kind}_ckpt.json')) as f:
+        want = json.load(f)
+    got = checkpoint_fingerprint(path, tmp_path)
+    assert got == want['fingerprint'], _first_difference(got, want['fingerprint'])
     # ---- round trip back into this package ----
     L2 = _product_learner(kind, monkeypatch, tmp_path)
     with contextlib.redirect_stdout(io.StringIO()):

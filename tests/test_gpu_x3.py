@@ -430,8 +430,6 @@ SW_CASES = [(2, 32, 64, 8, 32, 'pool'), (3, 64, 128, 16, 64, 'pool'), (5, 96, 64
 def test_x3_stride2_weight_gradient(ops, case, aff):
     n, ci, co, hl, wl, kind = case
     up = kind == 'up'
-    if aff and not up:
-        pytest.skip('the affine-on-load operand exists for up layers only (the discriminator has no InstanceNorm)')
     g = torch.Generator().manual_seed(71 + ci + n + hl)
     hi, wi = (hl, wl) if up else (2 * hl, 2 * wl)
     x = torch.randn(n, ci, hi, wi, generator=g)
@@ -441,11 +439,27 @@ def test_x3_stride2_weight_gradient(ops, case, aff):
     geom = ops.Geom(n, ci, hi, wi, co, 3, 1, up=1) if up else ops.Geom(n, ci, hi, wi, co, 3, 1, pool=1)
     assert ops.x3_s2_wgrad_ok(geom)
     scale = 0.017
+    from gan_lab_amd._lib import GanlabLibraryError, launch_count
+    if aff and not up:
+        # The affine-on-load operand exists for up layers only (the discriminator has no InstanceNorm).  Asked for it on
+        # a pooling layer, the split-product kernel (GANLAB_EINVAL) and the exact-fp32 path (GANLAB_EUNSUPPORTED) must
+        # refuse with an error and launch nothing - never compute a form they do not implement.
+        before = launch_count()
+        with pytest.raises(GanlabLibraryError):
+            ops._wgrad_x3_s2(gy.cuda(), x.cuda(), s_.cuda(), t_.cuda(), torch.empty(co, ci, 3, 3, device='cuda'), geom, scale)
+        for x3 in (True, False):
+            prev = ops.set_x3(x3)
+            try:
+                with pytest.raises(GanlabLibraryError):
+                    ops.k_conv_wgrad_aff(gy.cuda(), x.cuda(), s_.cuda(), t_.cuda(), geom, scale)
+            finally:
+                ops.set_x3(prev)
+        assert launch_count() == before
+        return
     run = (lambda: ops.k_conv_wgrad_aff(gy.cuda(), x.cuda(), s_.cuda(), t_.cuda(), geom, scale)) if aff else \
         (lambda: ops.k_conv_wgrad(gy.cuda(), x.cuda(), geom, scale))
     gw3 = run()
     assert 'x3sw_reduce_kernel' in launched(ops)
-    from gan_lab_amd._lib import GanlabLibraryError
     prev = ops.set_x3(False)
     try:      # (the exact-fp32 affine-on-load weight gradient does not take 16-pixel-wide maps; the step never asks it to)
         try:

@@ -14,7 +14,7 @@ done
 for rep in 1 2; do
   for lib in libganlab_hip.so libganlab_hip_nodump.so; do
     tag=${lib#libganlab_hip}; tag=${tag%.so}; tag=${tag:-_dump}
-    GANLAB_HIP_LIB=$lib python bench.py --steps $steps --warmup 2 --no-cpu-baseline > ${out}_bench${tag}_$rep.json 2> ${out}_bench${tag}_$rep.err
+    GANLAB_HIP_LIB=$lib python bench.py --full --steps $steps --warmup 2 --no-cpu-baseline > ${out}_bench${tag}_$rep.json 2> ${out}_bench${tag}_$rep.err
   done
 done
 GANLAB_HIP_LIB=libganlab_hip.so python tools/step_layers.py > ${out}_step_layers_dump.txt 2>&1

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 for ctr in FETCH_SIZE WRITE_SIZE; do
   D=$OUT/${TAG}_tmp; rm -rf "$D"; mkdir -p "$D"
-  rocprofv3 --pmc $ctr --kernel-trace -d "$D" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-roofline \
+  rocprofv3 --pmc $ctr --kernel-trace -d "$D" -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-roofline \
       > /dev/null 2> "$OUT/${TAG}_rocprof.err" || true
   DB=$(find "$D" -name '*.db' | head -1)
   python3 "$ROOT/tools/pmc_dump.py" "$DB" "" > "$OUT/${TAG}_$ctr.txt" 2>&1 || true
@@ -36,7 +36,7 @@ for k, (n, kb, ns) in f.items():
     rows.append((rb + wb, k, n, rb, wb, ns))
     table[k] = {'launches': n, 'read_bytes_per_launch': rb / n, 'written_bytes_per_launch': wb / n,
                 'average_us_under_pmc': ns / n / 1e3}
-json.dump({'steps_profiled': STEPS, 'command': 'bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline',
+json.dump({'steps_profiled': STEPS, 'command': 'bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-roofline',
            'method': 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes; FETCH_SIZE x 2 x 1e3 (gfx950: KB, '
                      'counts half), WRITE_SIZE x 1e3', 'kernels': table}, open(sys.argv[3], 'w'), indent=1)
 print(f'kernel, launches ({STEPS} steps), HBM read GB per step, written GB per step, ms per step, average TB/s')
