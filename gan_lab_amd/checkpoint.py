@@ -210,7 +210,8 @@ def reference_checkpoint_dict(learner, g_names, d_names, extra=None):
     from torch import nn
     c = learner.config
     cpu = lambda sd: OrderedDict((k, v.detach().cpu().clone()) for k, v in sd.items())  # noqa: E731
-    cfg_state = {k: v for k, v in vars(c).items()}
+    # (config.diffaugment is this package's own field: left out while it is off, so the file is the reference's own)
+    cfg_state = {k: v for k, v in vars(c).items() if not (k == 'diffaugment' and v is None)}
     nl = {'leaky relu': lambda: nn.LeakyReLU(negative_slope=c.leakiness), 'tanh': nn.Tanh}.get(c.nonlinearity.casefold(),
                                                                                              nn.ReLU)()
     lagged = learner.materialize_lagged_generator() if c.use_ewma_gen else None

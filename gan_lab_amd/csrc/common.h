@@ -98,6 +98,20 @@ __device__ __forceinline__ double gl_block_sum_256d(double v, double* red) {
 #endif
 constexpr int GL_ACC_DUMP_TERMS = GL_ACC_DUMP_TERMS_V;
 
+// Philox4x32-10 (Salmon et al. 2011) on counter c with key (k0, k1), in place: the device random stream of randn_kernel
+// (pointwise.hip) and of the DiffAugment parameter draw (augment.hip)
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
+    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
 __device__ __forceinline__ float gl_lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // One output channel `co` of a 1x1 convolution with <= 4 input channels (fromRGB forward / toRGB input gradient), 4 pixels

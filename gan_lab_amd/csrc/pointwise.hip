@@ -1603,18 +1603,6 @@ __global__ void ewma_kernel(float* __restrict__ lag, const float* __restrict__ p
   GRID_STRIDE(i, n) lag[i] = p[i] * (1.f - beta) + lag[i] * beta;
 }
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
 // ``base``: device-resident stream position added to ``offset`` (step graphs, see adam_kernel)
 __global__ void randn_kernel(float* __restrict__ out, long long n, uint64_t seed, uint64_t offset,
                              const uint64_t* __restrict__ base) {

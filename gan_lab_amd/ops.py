@@ -1345,6 +1345,40 @@ def randn_dev(shape, seed, base, delta, device):
     return out
 
 
+def diffaug_params(n, h, w, seed, offset, device):
+    """(n, 8) DiffAugment parameter rows (b, s, c, tx, ty, ox, oy, 0) from the Philox stream at ``offset`` (2 counters per row;
+    csrc/augment.hip)."""
+    out = torch.empty((int(n), 8), dtype=torch.float32, device=device)
+    check(_lib.lib().ganlab_diffaug_params_f32(_p(out), int(n), int(h), int(w), int(seed) & (2 ** 64 - 1), int(offset), _st()),
+          'diffaug_params')
+    return out
+
+
+def diffaug_params_dev(n, h, w, seed, base, delta, device):
+    """``diffaug_params`` at stream position ``*base + delta`` (``base``: the step-scalar block of graphs.GraphedStep)."""
+    out = torch.empty((int(n), 8), dtype=torch.float32, device=device)
+    check(_lib.lib().ganlab_diffaug_params_dev_f32(_p(out), int(n), int(h), int(w), int(seed) & (2 ** 64 - 1), _p(base),
+                                                   int(delta), _st()), 'diffaug_params_dev')
+    return out
+
+
+def k_diffaug(x, params, policy, adjoint=False):
+    """DiffAugment of an (N, 3, H, W) batch (``adjoint``: the transpose of its linear part, applied to a cotangent)."""
+    x, params = _c(x, 'diff_augment input'), _c(params, 'diff_augment params')
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[3] % 4 != 0 or tuple(params.shape) != (x.shape[0], 8):
+        raise ValueError(f'diff_augment: needs an (N, 3, H, W) batch with W % 4 == 0 and (N, 8) params, got '
+                         f'{tuple(x.shape)} and {tuple(params.shape)}')
+    n, _, h, w = x.shape
+    L = _lib.lib()
+    nbytes = (L.ganlab_diffaug_bwd_workspace if adjoint else L.ganlab_diffaug_fwd_workspace)(n, h, w, int(policy))
+    ws = torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=x.device)
+    out = torch.empty_like(x)
+    fn = L.ganlab_diffaug_bwd_f32 if adjoint else L.ganlab_diffaug_fwd_f32
+    check(fn(_p(x), _p(params), _p(out), n, h, w, int(policy), _p(ws), ws.numel() * 4, _st()),
+          'diffaug_bwd' if adjoint else 'diffaug_fwd')
+    return out
+
+
 def lerp_rows(a, b, t):
     a, b, t = _c(a), _c(b), _c(t)
     out = torch.empty_like(a)
@@ -1994,6 +2028,32 @@ class _Resample(Function):
     def backward(ctx, g):
         mode, align, hin, win, adjoint = ctx.args
         return _Resample.apply(g, mode, align, hin, win, not adjoint), None, None, None, None, None
+
+
+class _DiffAugment(Function):
+    """DiffAugment (csrc/augment.hip): affine in x, so the backward is the adjoint of its linear part."""
+
+    @staticmethod
+    def forward(ctx, x, params, policy):
+        ctx.params, ctx.policy = params, policy
+        return k_diffaug(x, params, policy)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return _DiffAugmentAdjoint.apply(g, ctx.params, ctx.policy), None, None
+
+
+class _DiffAugmentAdjoint(Function):
+    @staticmethod
+    def forward(ctx, g, params, policy):
+        return k_diffaug(g, params, policy, adjoint=True)
+
+    @staticmethod
+    def backward(ctx, gg):
+        raise NotImplementedError('diff_augment: double backward is not implemented (the penalties differentiate at the '
+                                  'augmented batch, not through the augmentation)')
 
 
 class _Scale(Function):
@@ -3325,6 +3385,16 @@ def bce_logits_mean(x, target):
 
 def chnorm_penalty(g, gamma, scale):
     return _ChNormPenalty.apply(g, float(gamma), float(scale))
+
+
+def diff_augment(x, params, policy):
+    """DiffAugment (Zhao et al. 2020) of an (N, 3, H, W) fp32 batch on the GPU: ``params`` (N, 8) rows
+    (b, s, c, tx, ty, ox, oy, 0) (``rng.augment_params``), ``policy`` a bit mask (``augment.parse_policy``).  Differentiable
+    once in ``x``."""
+    for t, what in ((x, 'diff_augment input'), (params, 'diff_augment params')):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+            _c(t, what)                 # raises TypeError: there is no CPU path
+    return _DiffAugment.apply(x, params.detach(), int(policy))
 
 
 def layer_tail_deferred(x, bias=None, noise=None, noise_w=None, style=None, bias_scale=1.0, act=None, slope=0.2,

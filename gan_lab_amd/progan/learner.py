@@ -233,9 +233,10 @@ class ProGANLearner(GANLearner):
         n = xgenb.shape[0]
         return per_sample and (g == -1 or (n >= g and n % g == 0))
 
-    def d_step(self, xb, zb=None, defer_update=False, gen_kwargs=None, eps_interp=None):
+    def d_step(self, xb, zb=None, defer_update=False, gen_kwargs=None, eps_interp=None, aug_params=None):
         """One discriminator iteration (progan/learner.py:734-816).  ``xb``: real batch on the device,
-        already at the current resolution.  Returns the (device) loss scalar."""
+        already at the current resolution.  Returns the (device) loss scalar.  With DiffAugment on, the critic sees
+        augmented batches: ``aug_params`` rows [0, B) for the generated one, [B, 2B) for the real one (drawn when None)."""
         c = self.config
         self.arena_d.zero_grad()
         if zb is None:
@@ -246,6 +247,12 @@ class ProGANLearner(GANLearner):
         xb = self.fade_in_real(xb)
         gp = self.gradient_penalty
         xr = None
+        aug, n = self.diffaug, xgenb.shape[0]
+        if aug is not None and aug_params is None:
+            aug_params = aug.draw(n + xb.shape[0], xb.shape[2], xb.shape[3], xb.device)
+        pair = not (self.share_gp_forward and gp in ('r1', 'r2')) and self._pair_critic_batches(xgenb, xb)
+        if aug is not None and not pair:
+            xgenb, xb = aug(xgenb, aug_params[:n]), aug(xb, aug_params[n:])
         if self.share_gp_forward and gp in ('r1', 'r2'):
             # R1 penalises the gradient at the real batch itself (R2: at the fake batch): D(real) of the
             # adversarial term and D(real) of the penalty are the SAME forward, so evaluate it once and
@@ -255,13 +262,16 @@ class ProGANLearner(GANLearner):
             d_gen, d_real = (self.disc_model(xgenb), d_pen) if gp == 'r1' else (d_pen, self.disc_model(xb))
             loss = self.loss_func_disc(d_gen, d_real) + bp.gp_from_output(d_pen, xr, gp, c.lda, c.gamma)
         else:
-            if self._pair_critic_batches(xgenb, xb):
+            if pair:
                 # one critic pass over [generated; real]: the only layer that looks across samples, the minibatch-stddev
                 # statistic, works on CONTIGUOUS groups of 4 (custom_layers.py:117-140: x.view(G, group_size, ...)), which a
                 # batch that is a multiple of 4 keeps inside its own half - the outputs are the two separate passes'
                 # (progan/learner.py:786-800) and every critic parameter gets one gradient contribution from the pair
-                n = xgenb.shape[0]
-                out = self.disc_model(torch.cat((xgenb, xb.reshape(xgenb.shape))))
+                both = torch.cat((xgenb, xb.reshape(xgenb.shape)))
+                if aug is not None:             # one launch over the pair: per sample, the same as two
+                    both = aug(both, aug_params)
+                    xgenb, xb = both[:n], both[n:]
+                out = self.disc_model(both)
                 d_gen, d_real = out[:n], out[n:]
             else:
                 d_gen, d_real = self.disc_model(xgenb), self.disc_model(xb)
@@ -286,8 +296,9 @@ class ProGANLearner(GANLearner):
         self.reducer.finish()
         self.opt_disc.step()
 
-    def g_step(self, zb=None, d_update_pending=False, gen_kwargs=None):
-        """One generator iteration (progan/learner.py:857-916) + EWMA shadow update."""
+    def g_step(self, zb=None, d_update_pending=False, gen_kwargs=None, aug_params=None):
+        """One generator iteration (progan/learner.py:857-916) + EWMA shadow update.  ``aug_params``: the DiffAugment rows
+        of the generated batch (drawn when None)."""
         c = self.config
         self.arena_g.zero_grad()
         if zb is None:
@@ -296,6 +307,8 @@ class ProGANLearner(GANLearner):
         fake = self._gen_forward(zb, **(gen_kwargs or {}))   # needs G weights only -> overlaps the D all-reduce
         if d_update_pending:
             self._finish_d_update()
+        if self.diffaug is not None:
+            fake = self._augment(fake, aug_params)
         loss = self.loss_func_gen(self.disc_model(fake))
         self.reducer.arm(self.arena_g)           # buckets go out while the backward is still producing the others
         with ops.direct_param_grads(ops.direct_grads_enabled()):

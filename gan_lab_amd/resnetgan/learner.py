@@ -45,6 +45,9 @@ class GANLearner(object):
         _lib.lib()  # fail now, loudly, if the kernel library is missing
         from .. import ops
         ops.set_compute_dtype(getattr(config, 'compute_dtype', 'f32'))   # 'bf16': BASELINE config #2
+        # DiffAugment of every critic input (config.diffaugment; None = off: no draw, no launch, no stream advance)
+        from .. import augment
+        self.diffaug = augment.from_config(getattr(config, 'diffaugment', None))
 
         self.curr_dataset_batch_num = 0
         self.curr_epoch_num = 1
@@ -196,14 +199,24 @@ class GANLearner(object):
         return str(v).lower() not in ('0', 'false', 'no')
 
     # -- the hot path: one generator iteration, one critic iteration ------------------------------------
-    def g_step(self, zb=None):
-        """resnetgan/learner.py:545-597 (critic parameters frozen by the caller)."""
+    def _augment(self, x, params):
+        """The critic's view of ``x`` under ``self.diffaug`` with ``params`` (None: a fresh (N, 8) draw)."""
+        if params is None:
+            params = self.diffaug.draw(x.shape[0], x.shape[2], x.shape[3], x.device)
+        return self.diffaug(x, params)
+
+    def g_step(self, zb=None, aug_params=None):
+        """resnetgan/learner.py:545-597 (critic parameters frozen by the caller).  ``aug_params``: the DiffAugment rows
+        of the generated batch (tests; drawn when None)."""
         c = self.config
         self.arena_g.zero_grad()
         if zb is None:
             zb = gen_rand_latent_vars(num_samples=self.batch_size * c.gen_bs_mult, length=c.len_latent,
                                       distribution=self.latent_distribution, device=c.dev)
-        out = self.disc_model(self.gen_model(zb))
+        fake = self.gen_model(zb)
+        if self.diffaug is not None:
+            fake = self._augment(fake, aug_params)
+        out = self.disc_model(fake)
         # :573-578 - the minimax generator loss here is -BCE(D(G(z)), 0), like backprop_utils
         loss = self.loss_func_gen(out)
         self.reducer.arm(self.arena_g)
@@ -225,9 +238,10 @@ class GANLearner(object):
             self._pairable = (id(self.disc_model), ok)
         return ok
 
-    def d_step(self, xb, zb=None, eps_interp=None):
+    def d_step(self, xb, zb=None, eps_interp=None, aug_params=None):
         """resnetgan/learner.py:606-672: generator frozen but in train mode (its BatchNorm running
-        statistics keep moving, :621-622); no drift term on this path."""
+        statistics keep moving, :621-622); no drift term on this path.  ``aug_params``: the DiffAugment rows, [0, B) for
+        the generated batch and [B, 2B) for the real one (tests; drawn when None)."""
         c = self.config
         self.arena_d.zero_grad()
         if zb is None:
@@ -235,14 +249,22 @@ class GANLearner(object):
                                       distribution=self.latent_distribution, device=c.dev)
         with torch.no_grad():
             xgenb = self.gen_model(zb)
+        n = xgenb.shape[0]
+        if self.diffaug is not None and aug_params is None:
+            aug_params = self.diffaug.draw(n + xb.shape[0], xb.shape[2], xb.shape[3], xb.device)
         if self._pair_critic_batches(xgenb, xb):
             # one critic pass over [generated; real]: every critic layer is per-sample (LayerNorm), so the outputs are the
             # two separate passes' (resnetgan/learner.py:640-651) and each parameter gets ONE gradient contribution from
             # the pair instead of two - half the launches of the first-order critic work at this launch-bound size
-            n = xgenb.shape[0]
-            out = self.disc_model(torch.cat((xgenb, xb.reshape(xgenb.shape))))
+            both = torch.cat((xgenb, xb.reshape(xgenb.shape)))
+            if self.diffaug is not None:        # one launch over the pair: per sample, the same as two
+                both = self.diffaug(both, aug_params)
+                xgenb, xb = both[:n], both[n:]
+            out = self.disc_model(both)
             loss = self.loss_func_disc(out[:n], out[n:])
         else:
+            if self.diffaug is not None:
+                xgenb, xb = self.diffaug(xgenb, aug_params[:n]), self.diffaug(xb, aug_params[n:])
             loss = self.loss_func_disc(self.disc_model(xgenb), self.disc_model(xb))
         if self.gradient_penalty is not None:
             loss = loss + self.calc_gp(xgenb, xb, eps_interp=eps_interp)

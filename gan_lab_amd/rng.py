@@ -57,3 +57,15 @@ def randn(shape, device='cuda'):
         out = ops.randn(tuple(shape), _STATE['seed'], _STATE['offset'], device)
     _STATE['offset'] += (n + 3) // 4
     return out
+
+
+def augment_params(n, h, w, device='cuda'):
+    """(n, 8) DiffAugment parameter rows for (h, w) images (augment.py); advances the stream by 2 counters per row."""
+    n = int(n)
+    if _DEVICE_BASE['block'] is not None:
+        out = ops.diffaug_params_dev(n, h, w, _STATE['seed'], _DEVICE_BASE['block'], _STATE['offset'] - _DEVICE_BASE['start'],
+                                     device)
+    else:
+        out = ops.diffaug_params(n, h, w, _STATE['seed'], _STATE['offset'], device)
+    _STATE['offset'] += 2 * n
+    return out

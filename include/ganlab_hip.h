@@ -485,6 +485,29 @@ int ganlab_adam_dev_f32(float* p, const float* g, float* m, float* v, long long 
                         float beta2, float eps, float wd, void* stream);
 
 
+/* ---- DiffAugment (Zhao et al. 2020): differentiable augmentation of the critic's inputs (csrc/augment.hip) ---------------
+ * x, y: (N, 3, H, W), W % 4 == 0, N <= 65535.  params: (N, 8) rows (b, s, c, tx, ty, ox, oy, 0); policy: OR of the bits below,
+ * applied in the order color (brightness x + b, saturation around the per-pixel channel mean, contrast around the sample
+ * mean), translation by (tx, ty) rows / columns with zero fill, cutout of the ceil(H/2) x ceil(W/2) rectangle centred at
+ * (ox, oy).  The color part needs a per-sample reduction: workspace of *_workspace() bytes (0 without color). */
+#define GANLAB_DIFFAUG_COLOR 1
+#define GANLAB_DIFFAUG_TRANSLATION 2
+#define GANLAB_DIFFAUG_CUTOUT 4
+/* the (N, 8) parameter rows from the Philox stream: sample n uses counters offset + 2n and offset + 2n + 1, whatever the
+ * policy; u = (w >> 8) 2^-24, b = u - 0.5, s = 2u, c = 0.5 + u (rounded down), integers lo + floor(u (hi - lo + 1)) */
+int ganlab_diffaug_params_f32(float* out, int N, int H, int W, uint64_t seed, uint64_t offset, void* stream);
+/* ganlab_diffaug_params_f32 at stream position *base + delta (base: device uint64) */
+int ganlab_diffaug_params_dev_f32(float* out, int N, int H, int W, uint64_t seed, const void* base, uint64_t delta,
+                                  void* stream);
+size_t ganlab_diffaug_fwd_workspace(int N, int H, int W, int policy);
+size_t ganlab_diffaug_bwd_workspace(int N, int H, int W, int policy);
+/* y = A(x) */
+int ganlab_diffaug_fwd_f32(const float* x, const float* params, float* y, int N, int H, int W, int policy, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* gx = A^T(gy): the adjoint of the linear part of A */
+int ganlab_diffaug_bwd_f32(const float* gy, const float* params, float* gx, int N, int H, int W, int policy,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- real-image input path -----------------------------------------------------------
  * uint8 NHWC dataset images -> 2^k box downsample -> fp32 NCHW ((v/255 - mean[c]) / std[c]); replaces the host
  * chain PIL Image.resize(BOX) -> ToTensor -> Normalize (data_config.py:307-341, progan/learner.py:1099-1112).
