@@ -479,7 +479,11 @@ __global__ __launch_bounds__(512) void conv_x3_fwd_kernel(X3Args p) {
 bool x3_ok(const ganlab_conv_geom* g, int dgrad) {
   if (g == nullptr || g->ks != 3 || g->pad != 1 || g->up || g->pool) return false;
   const int CI = dgrad ? g->Cout : g->Cin, CO = dgrad ? g->Cin : g->Cout;
-  return CI % 64 == 0 && CO % X3_NT == 0 && g->Hin % 16 == 0 && g->Win % 16 == 0 && g->N > 0;
+  if (!(CI % 64 == 0 && CO % X3_NT == 0 && g->Hin % 16 == 0 && g->Win % 16 == 0 && g->N > 0)) return false;
+  // the launch's byte limits (buffer-resource ranges, 32-bit offsets): a geometry past them takes the exact kernels
+  const long long ntiles = (long long)g->N * (g->Win / 16) * (g->Hin / 16) * (CO / X3_NT);
+  return ntiles > 0 && ntiles <= 0x7fffffffLL && (long long)(CO / X3_NT) * (CI / 64 * 9) * X3_WSTAGE * 16 <= 0xffffffffLL &&
+         (long long)CI * g->Hin * g->Win * 4 <= 0x7fffffffLL && (long long)g->N * CI * 4 <= 0x7fffffffLL;
 }
 
 int x3_launch(int form, X3Args a, hipStream_t st) {
@@ -487,7 +491,7 @@ int x3_launch(int form, X3Args a, hipStream_t st) {
   const long long ntiles = (long long)a.N * a.tiles_x * a.tiles_y * a.tiles_co;
   if (ntiles <= 0 || ntiles > 0x7fffffffLL || (long long)a.tiles_co * (a.CI / 64 * 9) * X3_WSTAGE * 16 > 0xffffffffLL ||
       (long long)a.CI * a.H * a.W * 4 > 0x7fffffffLL || (long long)a.N * a.CI * 4 > 0x7fffffffLL)
-    return GANLAB_EINVAL;
+    return GANLAB_EINVAL;           // (x3_ok refuses these geometries already)
   a.ntiles = (int)ntiles;
   const unsigned grid = (unsigned)(ntiles < 256 ? ntiles : 256);       // one workgroup per CU (146 KB of LDS), persistent
   switch (form) {

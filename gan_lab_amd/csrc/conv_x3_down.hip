@@ -324,7 +324,10 @@ bool xd_ok(const ganlab_conv_geom* g, int dgrad) {
   if (!dgrad && ((g->Hin | g->Win) & 1)) return false;
   const int Hl = dgrad ? g->Hin : g->Hin / 2, Wl = dgrad ? g->Win : g->Win / 2;
   if ((long long)CI * Hl * Wl * 16 > 0x7fffffffLL) return false;
-  return CI % 16 == 0 && CO % XD_NT == 0 && Hl % 8 == 0 && Wl % 16 == 0;
+  if (!(CI % 16 == 0 && CO % XD_NT == 0 && Hl % 8 == 0 && Wl % 16 == 0)) return false;
+  // xd_launch's limits: tile count, weight image
+  const long long ntiles = (long long)g->N * (Wl / 16) * (Hl / 8) * (CO / XD_NT);
+  return ntiles > 0 && ntiles <= 0x7fffffffLL && (long long)(CO / XD_NT) * (CI / 8 * 4) * XD_WSTEP * 16 <= 0xffffffffLL;
 }
 
 int xd_launch(const float* x, const void* wp, const float* bias, float* y, int N, int CI, int CO, int Hl, int Wl, float bias_scale,

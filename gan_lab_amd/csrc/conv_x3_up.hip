@@ -363,7 +363,10 @@ bool xu_ok(const ganlab_conv_geom* g, int dgrad) {
   if (dgrad && ((g->Hin | g->Win) & 1)) return false;
   const int Hl = dgrad ? g->Hin / 2 : g->Hin, Wl = dgrad ? g->Win / 2 : g->Win;      // the up layer's input; the pooled layer's OUTPUT
   if ((long long)CI * Hl * Wl * 4 > 0x7fffffffLL || (long long)g->N * CI * 4 > 0x7fffffffLL) return false;
-  return CI % 64 == 0 && CO % 32 == 0 && Hl % 8 == 0 && Wl % 16 == 0;
+  if (!(CI % 64 == 0 && CO % 32 == 0 && Hl % 8 == 0 && Wl % 16 == 0)) return false;
+  // xu_launch's limits: tile count, weight image (CO / 32 images of CI / 8 k-steps, either form)
+  const long long ntiles = (long long)g->N * (Wl / 16) * (Hl / 8) * (CO / 32);
+  return ntiles > 0 && ntiles <= 0x7fffffffLL && (long long)(CO / 32) * (CI / 8) * XU_WSTEP * 16 <= 0xffffffffLL;
 }
 
 int xu_launch(bool aff, XUArgs a, hipStream_t st) {

@@ -32,8 +32,8 @@ def launched(ops):
     return _lib.last_launch()[0] or ''
 
 
-# N, Cin, Cout, H, W: multi-tile per workgroup (more tiles than CUs), one / two / eight 64-channel double chunks, 2+ co tiles,
-# non-square, the ring wrapping across tiles with an odd number of stages per tile (64 channels)
+# N, Cin, Cout, H, W: one / two / three / four / eight 64-channel double chunks, 2+ co tiles, non-square.  At most 160 tiles: one
+# tile per workgroup - the persistent k-loop across tiles is tests/test_gpu_x3_persistent.py's
 X3_CASES = [(2, 64, 64, 16, 16), (3, 128, 192, 32, 16), (2, 256, 128, 16, 48), (1, 512, 64, 16, 16), (5, 64, 128, 64, 64),
             (9, 128, 64, 32, 32)]
 
@@ -283,32 +283,38 @@ def test_x3_pooled_layer_input_gradient(ops, case):
 
 
 def test_x3_s2_batched_repack_equals_single_pack(ops):
+    """ganlab_pack_many's stride-2 X3 kinds write the bits of the single-pack entry points: ks = 4, the transposed form
+    (ganlab_conv_s2_x3_pack), and ks = 5, the strided form (ganlab_conv_s2_down_x3_pack) - re-packed after every optimiser step."""
     from gan_lab_amd import _lib
     L = _lib.lib()
     g = torch.Generator().manual_seed(4)
-    jobs = [(128, 64, 1), (128, 64, 0), (32, 64, 1), (64, 32, 0)]       # Cout, Cin, up (the last two: the 32-channel layout)
+    # Cout, Cin, up, ks.  ks = 4: the last two are the 32-channel layout.  ks = 5: up = 0 a pooled layer's forward (Cout % 128),
+    # up = 1 an up layer's input gradient (Cin % 128); two 128-channel output tiles and 16 / 32-channel contractions among them
+    jobs = [(128, 64, 1, 4), (128, 64, 0, 4), (32, 64, 1, 4), (64, 32, 0, 4),
+            (128, 64, 0, 5), (256, 32, 0, 5), (64, 128, 1, 5), (16, 256, 1, 5)]
+    single = {4: L.ganlab_conv_s2_x3_pack, 5: L.ganlab_conv_s2_down_x3_pack}
     arr = (_lib.PackDesc * len(jobs))()
     singles, outs, keep, blocks = [], [], [], 0
-    for i, (co, ci, up) in enumerate(jobs):
+    for i, (co, ci, up, ks) in enumerate(jobs):
         wt = torch.randn(co, ci, 3, 3, generator=g).cuda()
         keep.append(wt)
-        n = L.ganlab_conv_s2_x3_pack(None, None, co, ci, up, 0.41, None)
+        n = single[ks](None, None, co, ci, up, 0.41, None)
         assert n == 48 * co * ci
         one = torch.zeros(n, dtype=torch.bfloat16, device='cuda')
-        assert L.ganlab_conv_s2_x3_pack(wt.data_ptr(), one.data_ptr(), co, ci, up, 0.41, None) == n
+        assert single[ks](wt.data_ptr(), one.data_ptr(), co, ci, up, 0.41, None) == n
         out = torch.zeros(n, dtype=torch.bfloat16, device='cuda')
         singles.append(one)
         outs.append(out)
         d = arr[i]
         d.src, d.dst, d.kind, d.Cout, d.Cin, d.ks, d.mode, d.up, d.scale, d.total, d.block0 = \
-            wt.data_ptr(), out.data_ptr(), 3, co, ci, 4, 0, up, 0.41, n, blocks
+            wt.data_ptr(), out.data_ptr(), 3, co, ci, ks, 0, up, 0.41, n, blocks
         blocks += (co * ci + 255) // 256
     tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).cuda()
     _lib.check(L.ganlab_pack_many(tab.data_ptr(), len(jobs), blocks, None), 'pack_many')
     torch.cuda.synchronize()
-    for one, out in zip(singles, outs):
-        assert torch.equal(one.view(torch.int16), out.view(torch.int16))
-        assert int((one.view(torch.int16) != 0).sum()) > one.numel() // 2       # (every position written)
+    for job, one, out in zip(jobs, singles, outs):
+        assert torch.equal(one.view(torch.int16), out.view(torch.int16)), job
+        assert int((one.view(torch.int16) != 0).sum()) > one.numel() // 2, job       # (every position written)
 
 
 # ---- weight gradient -------------------------------------------------------------------------------------------------------------

@@ -534,3 +534,72 @@ def test_mark_packs_stale_keeps_the_pack_generation():
     finally:
         ops._PACK_CACHE.clear(); ops._PACK_TABLES.clear(); ops._PACK_RANGES.clear()
         ops._PACK_CACHE.update(saved[0]); ops._PACK_TABLES.update(saved[1]); ops._PACK_RANGES.update(saved[2])
+
+
+# ---- the split-product kernels' support predicates agree with their launchers' limits -----------------------------------------
+# Each launcher refuses (GANLAB_EINVAL) a geometry past one of its byte / index limits: 32-bit buffer ranges and offsets, the tile
+# count.  The predicate (ops.x3_ok and kin) must refuse it first, so the layer falls back to the exact kernels instead of failing.
+# Restated here in the kernels' GEMM roles (CI contracted, CO written; H, W: conv_x3 plane, Hl, Wl: the low resolution).
+_I31, _U32 = 0x7fffffff, 0xffffffff
+
+
+def _x3_launch_ok(n, ci, co, h, w):           # x3_launch (conv_x3.hip): 64 x 16 x 16 tiles, 9 stages of 24 KB per 64 channels
+    return (n * (w // 16) * (h // 16) * (co // 64) <= _I31 and (co // 64) * (ci // 64 * 9) * 24576 <= _U32 and
+            ci * h * w * 4 <= _I31 and n * ci * 4 <= _I31)
+
+
+def _xu_launch_ok(n, ci, co, hl, wl):         # xu_launch (conv_x3_up.hip): co / 32 images of ci / 8 k-steps of 24 KB
+    return (n * (wl // 16) * (hl // 8) * (co // 32) <= _I31 and (co // 32) * (ci // 8) * 24576 <= _U32 and
+            ci * hl * wl * 4 <= _I31 and n * ci * 4 <= _I31)
+
+
+def _xd_launch_ok(n, ci, co, hl, wl):         # xd_launch (conv_x3_down.hip): co / 128 tiles of ci / 2 k-steps of 24 KB
+    return (n * (wl // 16) * (hl // 8) * (co // 128) <= _I31 and (co // 128) * (ci // 2) * 24576 <= _U32 and
+            ci * hl * wl * 16 <= _I31)
+
+
+def _x3_geoms(n, ci, co, h, w):
+    return {'fwd': (0, (n, ci, h, w, co, 3, 1, 0, 0)), 'dgrad': (1, (n, co, h, w, ci, 3, 1, 0, 0))}
+
+
+def _xu_geoms(n, ci, co, hl, wl):     # an up layer's forward; a pooled layer's input gradient
+    return {'fwd': (0, (n, ci, hl, wl, co, 3, 1, 1, 0)), 'dgrad': (1, (n, co, 2 * hl, 2 * wl, ci, 3, 1, 0, 1))}
+
+
+def _xd_geoms(n, ci, co, hl, wl):     # a pooled layer's forward; an up layer's input gradient
+    return {'fwd': (0, (n, ci, 2 * hl, 2 * wl, co, 3, 1, 0, 1)), 'dgrad': (1, (n, co, hl, wl, ci, 3, 1, 1, 0))}
+
+
+# kernel, limit, (N, CI, CO, H, W) just under the limit, the same just over it
+_X3_LIMIT_CASES = [
+    ('x3', 'plane bytes', (1, 64, 64, 2048, 4080), (1, 64, 64, 2048, 4096)),
+    ('x3', 'affine table bytes', (2 ** 23 - 1, 64, 64, 16, 16), (2 ** 23, 64, 64, 16, 16)),
+    ('x3', 'weight image bytes', (1, 64, 1242752, 16, 16), (1, 64, 1242816, 16, 16)),
+    ('x3', 'tile count', (2 ** 22, 64, 32704, 16, 16), (2 ** 22, 64, 32768, 16, 16)),
+    ('xu', 'plane bytes', (1, 64, 64, 2048, 4080), (1, 64, 64, 2048, 4096)),
+    ('xu', 'affine table bytes', (2 ** 23 - 1, 64, 64, 8, 16), (2 ** 23, 64, 64, 8, 16)),
+    ('xu', 'weight image bytes', (1, 64, 699040, 8, 16), (1, 64, 699072, 8, 16)),
+    ('xu', 'tile count', (2 ** 22, 64, 32 * 511, 8, 16), (2 ** 22, 64, 32 * 512, 8, 16)),
+    ('xd', 'plane bytes', (1, 16, 128, 2048, 4080), (1, 16, 128, 2048, 4096)),
+    ('xd', 'weight image bytes', (1, 16, 2796160, 8, 16), (1, 16, 2796288, 8, 16)),
+    ('xd', 'tile count', (2 ** 24, 16, 128 * 127, 8, 16), (2 ** 24, 16, 128 * 128, 8, 16)),
+]
+
+
+@pytest.mark.parametrize('case', _X3_LIMIT_CASES, ids=lambda c: f'{c[0]}-{c[1].replace(" ", "_")}')
+def test_x3_support_predicates_refuse_what_the_launchers_refuse(case):
+    """Only the predicates run (pure host code): no allocation, no launch."""
+    from gan_lab_amd import _lib
+    if not os.path.exists(_lib.SO_PATH):
+        _lib.build()
+    L = _lib.lib()
+    kernel, limit, under, over = case
+    pred = {'x3': L.ganlab_conv_x3_supported, 'xu': L.ganlab_conv_s2_x3_supported,
+            'xd': L.ganlab_conv_s2_down_x3_supported}[kernel]
+    launch_ok = {'x3': _x3_launch_ok, 'xu': _xu_launch_ok, 'xd': _xd_launch_ok}[kernel]
+    geoms = {'x3': _x3_geoms, 'xu': _xu_geoms, 'xd': _xd_geoms}[kernel]
+    assert launch_ok(*under) and not launch_ok(*over)
+    for shape, want in ((under, 1), (over, 0)):
+        for role, (dgrad, fields) in geoms(*shape).items():
+            g = _lib.ConvGeom(*fields)
+            assert pred(ctypes.byref(g), dgrad) == want, (kernel, limit, role, shape)

@@ -178,6 +178,24 @@ def s2_wgrad_report(batch, rounds, reps):
         del x, gy
 
 
+def switched(fn, on):
+    """fn with the split-product kernels switched on / off around it"""
+    def f():
+        prev = ops.set_x3(on)
+        try:
+            return fn()
+        finally:
+            ops.set_x3(prev)
+    return f
+
+
+def kernels_of(fn):
+    """fn()'s result and the kernels it launched"""
+    c0 = _lib.launch_count()
+    out = fn()
+    return out, [k or '' for k, _ in _lib.launches_since(c0)]
+
+
 def times(batch, rounds, reps, forms=False):
     for ci, co, hw in LAYERS:
         x = torch.randn(batch, ci, hw, hw, device='cuda')
@@ -185,27 +203,25 @@ def times(batch, rounds, reps, forms=False):
         g = ops.Geom(batch, ci, hw, hw, co, 3, 1)
         wp3 = pack_x3(w, 0, 0.05)
         fl = ops.conv_flops(g)
-        fns = {'fp32': lambda: ops.k_conv_fwd(x, w, None, g, 0.05), 'x3': lambda: fwd_x3(x, wp3, None, g)}
+        # the baseline is the exact-fp32 kernel: with the split-product kernels on, ops.k_conv_fwd would dispatch to them
+        fns = {'fp32': switched(lambda: ops.k_conv_fwd(x, w, None, g, 0.05), False), 'x3': lambda: fwd_x3(x, wp3, None, g)}
         if forms and not ops.conv_tail_shape_ok(x.shape, w):
             continue
         if forms:
-            def sw(fn, on):
-                def f():
-                    prev = ops.set_x3(on)
-                    try:
-                        return fn()
-                    finally:
-                        ops.set_x3(prev)
-                return f
             gy = torch.randn(*g.out_shape, device='cuda')
             s_, t_ = torch.rand(batch, ci, device='cuda') + 0.5, torch.randn(batch, ci, device='cuda')
             mask = lambda: ops.k_conv_dgrad_mask(gy, w, x, g, 0.05, 0.2)
             aff = lambda: ops.k_conv_fwd_aff(x, s_, t_, w, g, 0.05)
             bias, nz, nw = torch.randn(co, device='cuda'), torch.randn(batch, 1, hw, hw, device='cuda'), torch.randn(co, device='cuda')
             tail = lambda: ops._ConvModTail.apply(x, s_, t_, w, bias, nz, nw, None, 0.05, 1.0, ops.ACT_LRELU, 0.2, 1e-8)
-            fns = {'fp32': sw(mask, False), 'x3': sw(mask, True), 'aff fp32': sw(aff, False), 'aff x3': sw(aff, True),
-                   'tail fp32': sw(tail, False), 'tail x3': sw(tail, True)}
-        d = 0.0 if forms else (fns['fp32']() - fns['x3']()).abs().max().item()
+            fns = {'fp32': switched(mask, False), 'x3': switched(mask, True), 'aff fp32': switched(aff, False),
+                   'aff x3': switched(aff, True), 'tail fp32': switched(tail, False), 'tail x3': switched(tail, True)}
+        outs = {}
+        for k in ('fp32', 'x3'):      # the two columns ran different kernels: the exact ones, the split-product one
+            outs[k], names = kernels_of(fns[k])
+            assert any('conv_x3_fwd_kernel' in n for n in names) == (k == 'x3'), (k, names)
+        d = 0.0 if forms else (outs['fp32'] - outs['x3']).abs().max().item()
+        del outs
         ms = {k: [] for k in fns}
         for k in fns:
             for _ in range(5):
