@@ -227,6 +227,11 @@ SIGNATURES = {
     'ganlab_diffaug_bwd_workspace': (_c_sz, [_c_int, _c_int, _c_int, _c_int]),
     'ganlab_diffaug_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_sz, _c_p]),
     'ganlab_diffaug_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_sz, _c_p]),
+    'ganlab_ada_params_f32': (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_p, _c_int, _c_u64, _c_u64, _c_p]),
+    'ganlab_ada_params_dev_f32': (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_p, _c_int, _c_u64, _c_p, _c_u64, _c_p]),
+    'ganlab_ada_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),
+    'ganlab_ada_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),
+    'ganlab_ada_update_f32': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_f, _c_f, _c_p]),
     'ganlab_adam_dev_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_f, _c_f, _c_f, _c_f, _c_p]),
     'ganlab_step_scalars_size': (_c_int, []),
     'ganlab_set_step_scalars': (_c_int, [_c_p, _c_u64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),

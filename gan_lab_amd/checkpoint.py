@@ -202,6 +202,14 @@ def torch_adam_state_dict(fused_adam, named_params, ordered_names):
     return {'state': state, 'param_groups': [pg]}
 
 
+def saved_config_fields(cfg):
+    """``cfg`` (a dict of config fields) as a checkpoint stores it: while ``ada`` is None none of the ``ada*`` fields is
+    written, so files saved without ADA are what they were before the option existed."""
+    if cfg.get('ada') is not None:
+        return cfg
+    return {k: v for k, v in cfg.items() if not (k == 'ada' or k.startswith('ada_'))}
+
+
 def reference_checkpoint_dict(learner, g_names, d_names, extra=None):
     """The dict ``ProGANLearner.save_model`` of the reference writes (progan/learner.py:1257-1298; ``extra``: the
     StyleGAN additions, stylegan/learner.py:455-464), built from a product learner.  Tensors are moved to the CPU;
@@ -210,8 +218,8 @@ def reference_checkpoint_dict(learner, g_names, d_names, extra=None):
     from torch import nn
     c = learner.config
     cpu = lambda sd: OrderedDict((k, v.detach().cpu().clone()) for k, v in sd.items())  # noqa: E731
-    # (config.diffaugment is this package's own field: left out while it is off, so the file is the reference's own)
-    cfg_state = {k: v for k, v in vars(c).items() if not (k == 'diffaugment' and v is None)}
+    # (config.diffaugment and config.ada* are this package's own fields: left out while off, so the file is the reference's own)
+    cfg_state = saved_config_fields({k: v for k, v in vars(c).items() if not (k == 'diffaugment' and v is None)})
     nl = {'leaky relu': lambda: nn.LeakyReLU(negative_slope=c.leakiness), 'tanh': nn.Tanh}.get(c.nonlinearity.casefold(),
                                                                                              nn.ReLU)()
     lagged = learner.materialize_lagged_generator() if c.use_ewma_gen else None

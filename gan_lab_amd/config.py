@@ -10,7 +10,9 @@ bs//2 and 1024 -> bs//4) and pickles the Namespace to ``<this dir>/.config.p`` w
 New, optional fields (ignored by the reference): ``log_every``, ``compute_dtype`` ('f32' = the reference's
 arithmetic, 'bf16' = BASELINE config #2: bf16-compute 3x3 convolutions with fp32 storage / masters), ``diffaugment``
 (None = off, or a DiffAugment policy such as 'color,translation,cutout' applied to every critic input: augment.py;
-validated when the learner is built).
+validated when the learner is built), ``ada`` (None = off, or an ADA policy such as 'blit,geom,color': ada.py) with
+``ada_p`` (initial, or fixed, augmentation probability), ``ada_target`` (the r_t the controller steers to; None =
+fixed p), ``ada_interval`` (critic iterations per adjustment) and ``ada_kimg`` (thousands of images for p to travel 0 -> 1).
 """
 import argparse
 import os
@@ -26,6 +28,11 @@ BS = 64
 NIMG_TRANSITION = 600000
 _HERE = os.path.abspath(os.path.dirname(__file__))
 _MODELS = {'resnetgan': 'ResNet GAN', 'resnet gan': 'ResNet GAN', 'progan': 'ProGAN', 'stylegan': 'StyleGAN'}
+
+
+def _float_or_none(v):
+    """CLI type of an optional float: 'none' (any case) -> None."""
+    return None if v is None or str(v).casefold() == 'none' else float(v)
 
 
 def _spec(model_type):
@@ -48,6 +55,8 @@ def _spec(model_type):
         ('save_model_dir', Path, Path(_HERE + '/models/')), ('num_workers', int, 0),
         ('pin_memory', bool, dev == 'cuda'), ('log_every', int, 50), ('compute_dtype', str.casefold, 'f32'),
         ('diffaugment', str, None),
+        ('ada', str, None), ('ada_p', float, 0.0), ('ada_target', _float_or_none, 0.6), ('ada_interval', int, 4),
+        ('ada_kimg', float, 500.0),
     ]
     if model_type == 'ResNet GAN':
         rows += [('batch_size', int, BS), ('num_main_iters', int, 300000), ('num_disc_iters', int, 5),

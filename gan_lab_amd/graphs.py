@@ -136,7 +136,7 @@ class _StepGraphs(object):
         L = self.L
         return (getattr(L, '_graph_gen', 0), ops.pack_generation(), L.batch_size, tuple(real.shape[1:]), real.device,
                 ops.get_compute_dtype(), bool(L.gen_model.training), bool(L.disc_model.training),
-                getattr(getattr(L, 'diffaug', None), 'mask', 0))
+                getattr(getattr(L, 'diffaug', None), 'mask', 0), getattr(getattr(L, 'ada', None), 'mask', 0))
 
     def _check(self, sig):
         if sig != self.sig:

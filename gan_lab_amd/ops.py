@@ -1379,6 +1379,58 @@ def k_diffaug(x, params, policy, adjoint=False):
     return out
 
 
+ADA_ROW, ADA_COUNTERS = 32, 8        # GANLAB_ADA_ROW, GANLAB_ADA_COUNTERS (include/ganlab_hip.h)
+
+
+def ada_params(n, h, w, state, policy, seed, offset, device):
+    """(n, 32) ADA parameter rows (M, G, C, gates and raw geometric draws; csrc/ada.hip) from the Philox stream at ``offset``
+    (8 counters per row).  ``state``: the device block whose first float is p; ``policy``: bit mask (``ada.parse_policy``)."""
+    state = _c(state, 'ada_params state')
+    out = torch.empty((int(n), ADA_ROW), dtype=torch.float32, device=device)
+    check(_lib.lib().ganlab_ada_params_f32(_p(out), int(n), int(h), int(w), _p(state), int(policy), int(seed) & (2 ** 64 - 1),
+                                           int(offset), _st()), 'ada_params')
+    return out
+
+
+def ada_params_dev(n, h, w, state, policy, seed, base, delta, device):
+    """``ada_params`` at stream position ``*base + delta`` (``base``: the step-scalar block of graphs.GraphedStep)."""
+    state = _c(state, 'ada_params state')
+    out = torch.empty((int(n), ADA_ROW), dtype=torch.float32, device=device)
+    check(_lib.lib().ganlab_ada_params_dev_f32(_p(out), int(n), int(h), int(w), _p(state), int(policy),
+                                               int(seed) & (2 ** 64 - 1), _p(base), int(delta), _st()), 'ada_params_dev')
+    return out
+
+
+def k_ada(x, params, adjoint=False):
+    """ADA warp + color matrix of an (N, 3, H, W) batch (``adjoint``: the transpose of its linear part, applied to a
+    cotangent)."""
+    x, params = _c(x, 'ada_augment input'), _c(params, 'ada_augment params')
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[3] % 4 != 0 or tuple(params.shape) != (x.shape[0], ADA_ROW):
+        raise ValueError(f'ada_augment: needs an (N, 3, H, W) batch with W % 4 == 0 and (N, {ADA_ROW}) params, got '
+                         f'{tuple(x.shape)} and {tuple(params.shape)}')
+    n, _, h, w = x.shape
+    out = torch.empty_like(x)
+    L = _lib.lib()
+    fn = L.ganlab_ada_bwd_f32 if adjoint else L.ganlab_ada_fwd_f32
+    check(fn(_p(x), _p(params), _p(out), n, h, w, _st()), 'ada_bwd' if adjoint else 'ada_fwd')
+    return out
+
+
+def ada_update(state, logits, interval, step_size, target):
+    """The ADA controller (csrc/ada.hip) on the device block ``state`` = (p, acc_sum, acc_n, calls); ``logits`` None only
+    counts the call.  In place, no host read: capturable."""
+    state = _c(state, 'ada_update state')
+    if tuple(state.shape) != (4,):
+        raise ValueError(f'ada_update: state must be 4 floats (p, acc_sum, acc_n, calls), got {tuple(state.shape)}')
+    n = 0
+    if logits is not None:
+        logits = _c(logits, 'ada_update logits').reshape(-1)
+        n = logits.numel()
+    check(_lib.lib().ganlab_ada_update_f32(_p(state), _p(logits) if n else None, n, int(interval), float(step_size),
+                                           float(target), _st()), 'ada_update')
+    return state
+
+
 def lerp_rows(a, b, t):
     a, b, t = _c(a), _c(b), _c(t)
     out = torch.empty_like(a)
@@ -2053,6 +2105,32 @@ class _DiffAugmentAdjoint(Function):
     @staticmethod
     def backward(ctx, gg):
         raise NotImplementedError('diff_augment: double backward is not implemented (the penalties differentiate at the '
+                                  'augmented batch, not through the augmentation)')
+
+
+class _AdaAugment(Function):
+    """ADA warp + color matrix (csrc/ada.hip): affine in x, so the backward is the adjoint of its linear part."""
+
+    @staticmethod
+    def forward(ctx, x, params):
+        ctx.params = params
+        return k_ada(x, params)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return _AdaAugmentAdjoint.apply(g, ctx.params), None
+
+
+class _AdaAugmentAdjoint(Function):
+    @staticmethod
+    def forward(ctx, g, params):
+        return k_ada(g, params, adjoint=True)
+
+    @staticmethod
+    def backward(ctx, gg):
+        raise NotImplementedError('ada_augment: double backward is not implemented (the penalties differentiate at the '
                                   'augmented batch, not through the augmentation)')
 
 
@@ -3395,6 +3473,16 @@ def diff_augment(x, params, policy):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
             _c(t, what)                 # raises TypeError: there is no CPU path
     return _DiffAugment.apply(x, params.detach(), int(policy))
+
+
+def ada_augment(x, params):
+    """ADA (Karras et al. 2020) of an (N, 3, H, W) fp32 batch on the GPU: affine bilinear warp with zero fill, then a 3x4
+    color matrix, per sample from the (N, 32) ``params`` rows (``rng.ada_params`` or ``ada.rows_from_matrices``).
+    Differentiable once in ``x``."""
+    for t, what in ((x, 'ada_augment input'), (params, 'ada_augment params')):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+            _c(t, what)                 # raises TypeError: there is no CPU path
+    return _AdaAugment.apply(x, params.detach())
 
 
 def layer_tail_deferred(x, bias=None, noise=None, noise_w=None, style=None, bias_scale=1.0, act=None, slope=0.2,

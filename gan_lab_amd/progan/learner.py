@@ -247,7 +247,7 @@ class ProGANLearner(GANLearner):
         xb = self.fade_in_real(xb)
         gp = self.gradient_penalty
         xr = None
-        aug, n = self.diffaug, xgenb.shape[0]
+        aug, n = self.critic_aug, xgenb.shape[0]
         if aug is not None and aug_params is None:
             aug_params = aug.draw(n + xb.shape[0], xb.shape[2], xb.shape[3], xb.device)
         pair = not (self.share_gp_forward and gp in ('r1', 'r2')) and self._pair_critic_batches(xgenb, xb)
@@ -278,6 +278,7 @@ class ProGANLearner(GANLearner):
             loss = self.loss_func_disc(d_gen, d_real)
             if gp is not None:
                 loss = loss + self.calc_gp(xgenb, xb, eps_interp=eps_interp)
+        self._ada_update(d_real)
         if self.eps:
             loss = loss + bp.drift_loss(d_real, c.eps_drift)
         # RCCL mean all-reduce of the flat gradient arena: each ~32 MiB bucket is launched from inside the backward sweep
@@ -307,7 +308,7 @@ class ProGANLearner(GANLearner):
         fake = self._gen_forward(zb, **(gen_kwargs or {}))   # needs G weights only -> overlaps the D all-reduce
         if d_update_pending:
             self._finish_d_update()
-        if self.diffaug is not None:
+        if self.critic_aug is not None:
             fake = self._augment(fake, aug_params)
         loss = self.loss_func_gen(self.disc_model(fake))
         self.reducer.arm(self.arena_g)           # buckets go out while the backward is still producing the others
@@ -744,7 +745,8 @@ class ProGANLearner(GANLearner):
         if parallel.rank() == 0:
             g_names, d_names = self._param_name_sets()
             if reference_format:
-                ck = ckpt.reference_checkpoint_dict(self, g_names, d_names, extra=self._extra_checkpoint_fields())
+                ck = ckpt.reference_checkpoint_dict(self, g_names, d_names, extra=dict(self._extra_checkpoint_fields(),
+                                                                                      **self._ada_checkpoint_fields()))
                 ckpt.save_atomic(ck, save_path, foreign=True)
             else:
                 ckpt.save_atomic(self._plain_checkpoint_dict(), save_path)
@@ -752,12 +754,13 @@ class ProGANLearner(GANLearner):
             parallel.barrier()
 
     def _plain_checkpoint_dict(self):
+        from .. import checkpoint as ckpt
         cpu = lambda sd: {k: v.detach().cpu() for k, v in sd.items()}  # noqa: E731
         lagged = self.materialize_lagged_generator() if self.config.use_ewma_gen else None
         tcpu = lambda v: None if v is None else v.detach().cpu()  # noqa: E731
         ck = {
-            'config': {k: v for k, v in vars(self.config).items() if not k.startswith('_') and
-                       isinstance(v, (int, float, str, bool, dict, list, tuple, type(None)))},
+            'config': ckpt.saved_config_fields({k: v for k, v in vars(self.config).items() if not k.startswith('_') and
+                                                isinstance(v, (int, float, str, bool, dict, list, tuple, type(None)))}),
             'curr_res': self.gen_model.curr_res,
             'alpha': self.gen_model.alpha,
             'gen_model_state_dict': cpu(self.gen_model.state_dict()),
@@ -789,6 +792,7 @@ class ProGANLearner(GANLearner):
             'rng_state': dict(rng._STATE),
         }
         ck.update({k: (tcpu(v) if torch.is_tensor(v) else v) for k, v in self._extra_checkpoint_fields().items()})
+        ck.update(self._ada_checkpoint_fields())
         return ck
 
     def load_model(self, load_path, dev_of_saved_model='cpu'):
@@ -824,6 +828,7 @@ class ProGANLearner(GANLearner):
                     if k in self.lagged_params:
                         self.lagged_params[k].copy_(v.to(self.config.dev))
         self._restore_extra_fields(ck)
+        self._restore_ada(ck)
         for attr in ('loss', 'gradient_penalty'):
             if ck.get(attr) is not None:
                 setattr(self, attr, ck[attr])

@@ -48,6 +48,11 @@ class GANLearner(object):
         # DiffAugment of every critic input (config.diffaugment; None = off: no draw, no launch, no stream advance)
         from .. import augment
         self.diffaug = augment.from_config(getattr(config, 'diffaugment', None))
+        # ADA (config.ada; None = off likewise): the other augmentation of the critic inputs, at the same hook points, with
+        # its probability and controller statistics in a device block (ada.py); the two exclude each other
+        from .. import ada
+        self.ada = ada.from_config(config)
+        self.critic_aug = self.diffaug if self.diffaug is not None else self.ada
 
         self.curr_dataset_batch_num = 0
         self.curr_epoch_num = 1
@@ -200,10 +205,22 @@ class GANLearner(object):
 
     # -- the hot path: one generator iteration, one critic iteration ------------------------------------
     def _augment(self, x, params):
-        """The critic's view of ``x`` under ``self.diffaug`` with ``params`` (None: a fresh (N, 8) draw)."""
+        """The critic's view of ``x`` under ``self.critic_aug`` (DiffAugment or ADA) with ``params`` (None: a fresh draw)."""
         if params is None:
-            params = self.diffaug.draw(x.shape[0], x.shape[2], x.shape[3], x.device)
-        return self.diffaug(x, params)
+            params = self.critic_aug.draw(x.shape[0], x.shape[2], x.shape[3], x.device)
+        return self.critic_aug(x, params)
+
+    def _ada_update(self, d_real):
+        """After the critic's forward of a D step: feed sign(D(real)) to the ADA controller (adaptive p only)."""
+        if self.ada is not None and self.ada.adaptive:
+            self.ada.update(d_real.detach())
+
+    def _ada_checkpoint_fields(self):
+        return {} if self.ada is None else {'ada_state': self.ada.state_dict()}
+
+    def _restore_ada(self, ck):
+        if self.ada is not None and ck.get('ada_state') is not None:
+            self.ada.load_state_dict(ck['ada_state'])
 
     def g_step(self, zb=None, aug_params=None):
         """resnetgan/learner.py:545-597 (critic parameters frozen by the caller).  ``aug_params``: the DiffAugment rows
@@ -214,7 +231,7 @@ class GANLearner(object):
             zb = gen_rand_latent_vars(num_samples=self.batch_size * c.gen_bs_mult, length=c.len_latent,
                                       distribution=self.latent_distribution, device=c.dev)
         fake = self.gen_model(zb)
-        if self.diffaug is not None:
+        if self.critic_aug is not None:
             fake = self._augment(fake, aug_params)
         out = self.disc_model(fake)
         # :573-578 - the minimax generator loss here is -BCE(D(G(z)), 0), like backprop_utils
@@ -249,23 +266,25 @@ class GANLearner(object):
                                       distribution=self.latent_distribution, device=c.dev)
         with torch.no_grad():
             xgenb = self.gen_model(zb)
-        n = xgenb.shape[0]
-        if self.diffaug is not None and aug_params is None:
-            aug_params = self.diffaug.draw(n + xb.shape[0], xb.shape[2], xb.shape[3], xb.device)
+        n, aug = xgenb.shape[0], self.critic_aug
+        if aug is not None and aug_params is None:
+            aug_params = aug.draw(n + xb.shape[0], xb.shape[2], xb.shape[3], xb.device)
         if self._pair_critic_batches(xgenb, xb):
             # one critic pass over [generated; real]: every critic layer is per-sample (LayerNorm), so the outputs are the
             # two separate passes' (resnetgan/learner.py:640-651) and each parameter gets ONE gradient contribution from
             # the pair instead of two - half the launches of the first-order critic work at this launch-bound size
             both = torch.cat((xgenb, xb.reshape(xgenb.shape)))
-            if self.diffaug is not None:        # one launch over the pair: per sample, the same as two
-                both = self.diffaug(both, aug_params)
+            if aug is not None:        # one launch over the pair: per sample, the same as two
+                both = aug(both, aug_params)
                 xgenb, xb = both[:n], both[n:]
             out = self.disc_model(both)
-            loss = self.loss_func_disc(out[:n], out[n:])
+            d_gen, d_real = out[:n], out[n:]
         else:
-            if self.diffaug is not None:
-                xgenb, xb = self.diffaug(xgenb, aug_params[:n]), self.diffaug(xb, aug_params[n:])
-            loss = self.loss_func_disc(self.disc_model(xgenb), self.disc_model(xb))
+            if aug is not None:
+                xgenb, xb = aug(xgenb, aug_params[:n]), aug(xb, aug_params[n:])
+            d_gen, d_real = self.disc_model(xgenb), self.disc_model(xb)
+        loss = self.loss_func_disc(d_gen, d_real)
+        self._ada_update(d_real)
         if self.gradient_penalty is not None:
             loss = loss + self.calc_gp(xgenb, xb, eps_interp=eps_interp)
         self.reducer.arm(self.arena_d)
@@ -353,8 +372,8 @@ class GANLearner(object):
         tcpu = lambda v: None if v is None else v.detach().cpu()  # noqa: E731
         sched_steps = max(self.scheduler_gen._step_count - 1, 0) if (self.sched_bool and self.scheduler_gen) else 0
         ck = {
-            'config': {k: v for k, v in vars(self.config).items() if not k.startswith('_') and
-                       isinstance(v, (int, float, str, bool, dict, list, tuple, type(None)))},
+            'config': ckpt.saved_config_fields({k: v for k, v in vars(self.config).items() if not k.startswith('_') and
+                                                isinstance(v, (int, float, str, bool, dict, list, tuple, type(None)))}),
             'gen_model_state_dict': {k: v.detach().cpu() for k, v in self.gen_model.state_dict().items()},
             'disc_model_state_dict': {k: v.detach().cpu() for k, v in self.disc_model.state_dict().items()},
             'opt_gen_state_dict': self.opt_gen.export_moments(self.gen_model.named_parameters()),
@@ -367,6 +386,7 @@ class GANLearner(object):
             'not_trained_yet': self.not_trained_yet,
             'ds_mean': tcpu(self.ds_mean), 'ds_std': tcpu(self.ds_std), 'valid_z': tcpu(self.valid_z),
         }
+        ck.update(self._ada_checkpoint_fields())
         if parallel.rank() == 0:            # replicas are identical: one writer, atomically; everyone waits for the file
             ckpt.save_atomic(ck, save_path)
         if sync:
@@ -390,6 +410,7 @@ class GANLearner(object):
             self.ds_mean, self.ds_std = ck['ds_mean'].float().cpu(), ck['ds_std'].float().cpu()
         if ck.get('valid_z') is not None:
             self.valid_z = ck['valid_z'].to(self.config.dev)
+        self._restore_ada(ck)
         self.pretrained_model = True
 
     # -- gradient penalty (resnetgan/learner.py:780-827) ------------------------------------------------

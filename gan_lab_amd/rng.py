@@ -69,3 +69,16 @@ def augment_params(n, h, w, device='cuda'):
         out = ops.diffaug_params(n, h, w, _STATE['seed'], _STATE['offset'], device)
     _STATE['offset'] += 2 * n
     return out
+
+
+def ada_params(n, h, w, state, policy, device='cuda'):
+    """(n, 32) ADA parameter rows for (h, w) images at the probability held in the device block ``state`` (ada.py);
+    advances the stream by 8 counters per row."""
+    n = int(n)
+    if _DEVICE_BASE['block'] is not None:
+        out = ops.ada_params_dev(n, h, w, state, policy, _STATE['seed'], _DEVICE_BASE['block'],
+                                 _STATE['offset'] - _DEVICE_BASE['start'], device)
+    else:
+        out = ops.ada_params(n, h, w, state, policy, _STATE['seed'], _STATE['offset'], device)
+    _STATE['offset'] += ops.ADA_COUNTERS * n
+    return out

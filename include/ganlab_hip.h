@@ -508,6 +508,34 @@ int ganlab_diffaug_fwd_f32(const float* x, const float* params, float* y, int N,
 int ganlab_diffaug_bwd_f32(const float* gy, const float* params, float* gx, int N, int H, int W, int policy,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- ADA (Karras et al. 2020): adaptive discriminator augmentation of the critic's inputs (csrc/ada.hip) ----------------
+ * x, y: (N, 3, H, W), W % 4 == 0, N <= 65535.  params: (N, GANLAB_ADA_ROW) rows - M (6: 2x3, output pixel -> source position in
+ * centred pixel units), G (4: the inverse of M[:, :2]), C (12: 3x4 color matrix), then the gate mask and the raw geometric draws
+ * (quarter turns, tx, ty, isotropic z, pre-rotation, anisotropic z, post-rotation, shift zx, zy).  The transform is an affine
+ * bilinear warp with zero fill followed by the color matrix; the policy only decides which gates the parameter draw may open.
+ * state: 4 device floats (p, acc_sum, acc_n, calls) - the augmentation probability and the controller's accumulators. */
+#define GANLAB_ADA_BLIT 1
+#define GANLAB_ADA_GEOM 2
+#define GANLAB_ADA_COLOR 4
+#define GANLAB_ADA_ROW 32
+#define GANLAB_ADA_COUNTERS 8
+/* the parameter rows from the Philox stream: sample n uses counters offset + 8n .. offset + 8n + 7, whatever the policy; p is
+ * read from state[0] on the device.  Word-to-parameter mapping: csrc/ada.hip, DESIGN.md "ADA" */
+int ganlab_ada_params_f32(float* out, int N, int H, int W, const float* state, int policy, uint64_t seed, uint64_t offset,
+                          void* stream);
+/* ganlab_ada_params_f32 at stream position *base + delta (base: device uint64) */
+int ganlab_ada_params_dev_f32(float* out, int N, int H, int W, const float* state, int policy, uint64_t seed,
+                              const void* base, uint64_t delta, void* stream);
+/* y = A(x) */
+int ganlab_ada_fwd_f32(const float* x, const float* params, float* y, int N, int H, int W, void* stream);
+/* gx = A^T(gy): the adjoint of the linear part of A, as a gather (G must be the inverse of M[:, :2]) */
+int ganlab_ada_bwd_f32(const float* gy, const float* params, float* gx, int N, int H, int W, void* stream);
+/* controller: acc_sum += sum(sign(logits)), acc_n += N, calls += 1; when interval > 0 and calls >= interval:
+ * p = clamp(p + sign(acc_sum / acc_n - target) * step_size, 0, 1) and the other three are cleared.  interval <= 0 only
+ * accumulates; N == 0 (logits may be null) only counts - together they let a host all-reduce sit between the two. */
+int ganlab_ada_update_f32(float* state, const float* logits, int N, int interval, float step_size, float target,
+                          void* stream);
+
 /* ---- real-image input path -----------------------------------------------------------
  * uint8 NHWC dataset images -> 2^k box downsample -> fp32 NCHW ((v/255 - mean[c]) / std[c]); replaces the host
  * chain PIL Image.resize(BOX) -> ToTensor -> Normalize (data_config.py:307-341, progan/learner.py:1099-1112).
