@@ -218,8 +218,12 @@ def reference_checkpoint_dict(learner, g_names, d_names, extra=None):
     from torch import nn
     c = learner.config
     cpu = lambda sd: OrderedDict((k, v.detach().cpu().clone()) for k, v in sd.items())  # noqa: E731
-    # (config.diffaugment and config.ada* are this package's own fields: left out while off, so the file is the reference's own)
-    cfg_state = saved_config_fields({k: v for k, v in vars(c).items() if not (k == 'diffaugment' and v is None)})
+    # (config.diffaugment, config.ada* and config.swd_* are this package's own fields: left out while off, so the file is the
+    # reference's own)
+    from . import swd
+    swd_off = not swd.wanted(getattr(c, 'gen_metrics', None))
+    cfg_state = saved_config_fields({k: v for k, v in vars(c).items() if not (k == 'diffaugment' and v is None) and
+                                     not (swd_off and k.startswith('swd_'))})
     nl = {'leaky relu': lambda: nn.LeakyReLU(negative_slope=c.leakiness), 'tanh': nn.Tanh}.get(c.nonlinearity.casefold(),
                                                                                              nn.ReLU)()
     lagged = learner.materialize_lagged_generator() if c.use_ewma_gen else None

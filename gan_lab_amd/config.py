@@ -12,7 +12,10 @@ arithmetic, 'bf16' = BASELINE config #2: bf16-compute 3x3 convolutions with fp32
 (None = off, or a DiffAugment policy such as 'color,translation,cutout' applied to every critic input: augment.py;
 validated when the learner is built), ``ada`` (None = off, or an ADA policy such as 'blit,geom,color': ada.py) with
 ``ada_p`` (initial, or fixed, augmentation probability), ``ada_target`` (the r_t the controller steers to; None =
-fixed p), ``ada_interval`` (critic iterations per adjustment) and ``ada_kimg`` (thousands of images for p to travel 0 -> 1).
+fixed p), ``ada_interval`` (critic iterations per adjustment) and ``ada_kimg`` (thousands of images for p to travel 0 -> 1);
+``'swd'`` as an entry of ``gen_metrics`` (the sliced Wasserstein distance of swd.py between the validation reals and the generated
+validation images) with ``swd_nhoods`` (neighbourhoods per image and level), ``swd_dir_repeats`` x ``swd_dirs_per_repeat``
+(projection directions) and ``swd_seed``, validated when the learner is built.
 """
 import argparse
 import os
@@ -57,6 +60,7 @@ def _spec(model_type):
         ('diffaugment', str, None),
         ('ada', str, None), ('ada_p', float, 0.0), ('ada_target', _float_or_none, 0.6), ('ada_interval', int, 4),
         ('ada_kimg', float, 500.0),
+        ('swd_nhoods', int, 128), ('swd_dir_repeats', int, 4), ('swd_dirs_per_repeat', int, 128), ('swd_seed', int, 0),
     ]
     if model_type == 'ResNet GAN':
         rows += [('batch_size', int, BS), ('num_main_iters', int, 300000), ('num_disc_iters', int, 5),

@@ -1431,6 +1431,161 @@ def ada_update(state, logits, interval, step_size, target):
     return state
 
 
+# ---- sliced Wasserstein distance (csrc/swd.hip; composed in gan_lab_amd/swd.py) ----------------------------------------------
+SWD_DESC = 147                       # GANLAB_SWD_DESC (include/ganlab_hip.h)
+
+
+def _ct(t, dtype, what):
+    """``_c`` for the non-fp32 operands of the SWD kernels (int32 centres, fp64 partials and statistics)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+        raise TypeError(f'gan_lab_amd.ops: {what} must be a {dtype} tensor on the GPU (got {type(t).__name__}, '
+                        f'{getattr(t, "device", None)}, {getattr(t, "dtype", None)}); the HIP path has no CPU fallback')
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _swd_planes(x, what):
+    x = _c(x, what)
+    if x.dim() < 2 or x.shape[-1] % 2 or x.shape[-2] % 2 or min(x.shape[-2:]) < 4:
+        raise ValueError(f'{what}: needs (..., H, W) planes with even H, W >= 4, got {tuple(x.shape)}')
+    return x
+
+
+def swd_down(x):
+    """Pyramid step down: the 5x5 binomial filter with mirror boundary, every second pixel kept."""
+    x = _swd_planes(x, 'swd_down input')
+    h, w = x.shape[-2:]
+    out = torch.empty(x.shape[:-2] + (h // 2, w // 2), dtype=torch.float32, device=x.device)
+    check(_lib.lib().ganlab_swd_down_f32(_p(x), _p(out), x.numel() // (h * w), h, w, _st()), 'swd_down')
+    return out
+
+
+def swd_band(g0, g1):
+    """Laplacian band ``g0 - up(g1)`` (zero-insert upsample and its filter are never materialised)."""
+    g0, g1 = _swd_planes(g0, 'swd_band fine level'), _c(g1, 'swd_band coarse level')
+    h, w = g0.shape[-2:]
+    if tuple(g1.shape) != tuple(g0.shape[:-2]) + (h // 2, w // 2):
+        raise ValueError(f'swd_band: coarse level must be {tuple(g0.shape[:-2]) + (h // 2, w // 2)}, got {tuple(g1.shape)}')
+    out = torch.empty_like(g0)
+    check(_lib.lib().ganlab_swd_band_f32(_p(g0), _p(g1), _p(out), g0.numel() // (h * w), h, w, _st()), 'swd_band')
+    return out
+
+
+def swd_gather(band, pos, desc, partials):
+    """Descriptor rows of an (N, 3, S, S) level at the (N, n, 2) int32 centres ``pos`` into ``desc`` ((N n, 147) rows of a
+    preallocated set buffer) and the per-image fp64 channel sums into ``partials`` ((N, 6))."""
+    band, pos = _c(band, 'swd_gather level'), _ct(pos, torch.int32, 'swd_gather positions')
+    if band.dim() != 4 or band.shape[1] != 3 or band.shape[2] != band.shape[3] or band.shape[2] < 7 or pos.dim() != 3 or \
+            pos.shape[0] != band.shape[0] or pos.shape[2] != 2:
+        raise ValueError(f'swd_gather: needs an (N, 3, S, S) level with S >= 7 and (N, n, 2) positions, got '
+                         f'{tuple(band.shape)} and {tuple(pos.shape)}')
+    n_img, n = pos.shape[:2]
+    _c(desc, 'swd_gather descriptors'), _ct(partials, torch.float64, 'swd_gather partials')
+    if not desc.is_contiguous() or not partials.is_contiguous() or tuple(desc.shape) != (n_img * n, SWD_DESC) or \
+            tuple(partials.shape) != (n_img, 6):
+        raise ValueError(f'swd_gather: outputs must be contiguous ({n_img * n}, {SWD_DESC}) and ({n_img}, 6), got '
+                         f'{tuple(desc.shape)} and {tuple(partials.shape)}')
+    check(_lib.lib().ganlab_swd_gather_f32(_p(band), _p(pos), _p(desc), _p(partials), n_img, n, band.shape[2], _st()),
+          'swd_gather')
+    return desc
+
+
+def swd_stats(partials, per_image):
+    """(6,) fp64: per-channel mean, then population standard deviation, from the (images, 6) partials of ``swd_gather``
+    (``per_image`` values per channel and image); reduced in a fixed order."""
+    partials = _ct(partials, torch.float64, 'swd_stats partials')
+    if partials.dim() != 2 or partials.shape[1] != 6 or partials.shape[0] < 1:
+        raise ValueError(f'swd_stats: partials must be (images, 6), got {tuple(partials.shape)}')
+    out = torch.empty(6, dtype=torch.float64, device=partials.device)
+    check(_lib.lib().ganlab_swd_stats_f64(_p(partials), partials.shape[0], int(per_image), _p(out), _st()), 'swd_stats')
+    return out
+
+
+def swd_project(desc, dirs, stats, out=None):
+    """(D, M) projections of the normalised descriptors: ``dirs @ ((desc - mean) / std).T`` with the per-channel ``stats`` of
+    ``swd_stats`` applied as the rows are loaded (fp32 MFMA)."""
+    desc, dirs, stats = _c(desc, 'swd_project descriptors'), _c(dirs, 'swd_project directions'), \
+        _ct(stats, torch.float64, 'swd_project statistics')
+    if desc.dim() != 2 or desc.shape[1] != SWD_DESC or dirs.dim() != 2 or dirs.shape[1] != SWD_DESC or stats.numel() != 6:
+        raise ValueError(f'swd_project: needs (M, {SWD_DESC}) descriptors, (D, {SWD_DESC}) directions and 6 statistics, got '
+                         f'{tuple(desc.shape)}, {tuple(dirs.shape)}, {tuple(stats.shape)}')
+    m, d = desc.shape[0], dirs.shape[0]
+    if out is None:
+        out = torch.empty((d, m), dtype=torch.float32, device=desc.device)
+    elif tuple(_c(out, 'swd_project output').shape) != (d, m) or not out.is_contiguous():
+        raise ValueError(f'swd_project: output must be a contiguous ({d}, {m}) tensor, got {tuple(out.shape)}')
+    check(_lib.lib().ganlab_swd_project_f32(_p(desc), _p(dirs), _p(stats), _p(out), m, d, _st()), 'swd_project')
+    return out
+
+
+_SWD_WS = {}
+
+
+def _swd_workspace(nbytes, device):
+    ws = _SWD_WS.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = _SWD_WS[device] = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+    return ws
+
+
+def swd_sort(x, out=None):
+    """Each row of a (D, M) buffer sorted ascending (rocPRIM radix sorts inside the library)."""
+    x = _c(x, 'swd_sort input')
+    if x.dim() != 2 or x.numel() == 0:
+        raise ValueError(f'swd_sort: needs a non-empty (D, M) tensor, got {tuple(x.shape)}')
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(_c(out, 'swd_sort output').shape) != tuple(x.shape) or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
+        raise ValueError('swd_sort: output must be a contiguous tensor of the input\'s shape that does not alias it')
+    d, m = x.shape
+    L = _lib.lib()
+    nbytes = L.ganlab_swd_sort_workspace(d, m)
+    if nbytes == 0:
+        raise ValueError(f'swd_sort: a ({d}, {m}) buffer is refused (D * M must stay below 2^32 - 1)')
+    ws = _swd_workspace(nbytes, x.device)
+    check(L.ganlab_swd_sort_f32(_p(x), _p(out), d, m, _p(ws), ws.numel(), _st()), 'swd_sort')
+    return out
+
+
+def swd_distance(a, b):
+    """0-d fp64 device tensor: mean |a - b| over two sorted (D, M) buffers (fp64 partials, fixed order)."""
+    a, b = _c(a, 'swd_distance a'), _c(b, 'swd_distance b')
+    if a.dim() != 2 or a.shape != b.shape or a.numel() == 0:
+        raise ValueError(f'swd_distance: needs two equal non-empty (D, M) tensors, got {tuple(a.shape)} and {tuple(b.shape)}')
+    d, m = a.shape
+    L = _lib.lib()
+    ws = torch.empty(L.ganlab_swd_distance_workspace(d, m), dtype=torch.uint8, device=a.device)
+    out = torch.empty(1, dtype=torch.float64, device=a.device)
+    check(L.ganlab_swd_distance_f64(_p(a), _p(b), _p(out), d, m, _p(ws), ws.numel(), _st()), 'swd_distance')
+    return out[0]
+
+
+def swd_positions(n_images, n_per_image, size, seed, offset, device):
+    """(n_images, n_per_image, 2) int32 patch centres uniform in [3, size - 4] from the Philox stream at ``offset``
+    (ceil(n_per_image / 2) counters per image)."""
+    if int(size) < 7 or int(n_images) < 1 or int(n_per_image) < 1:
+        raise ValueError(f'swd_positions: needs size >= 7 and positive counts, got {n_images}, {n_per_image}, {size}')
+    if torch.device(device).type != 'cuda':
+        raise TypeError(f'gan_lab_amd.ops: swd_positions draws on the GPU (got device {device!r}); the HIP path has no CPU '
+                        f'fallback')
+    out = torch.empty((int(n_images), int(n_per_image), 2), dtype=torch.int32, device=device)
+    check(_lib.lib().ganlab_swd_positions_i32(_p(out), int(n_images), int(n_per_image), int(size), int(seed) & (2 ** 64 - 1),
+                                              int(offset), _st()), 'swd_positions')
+    return out
+
+
+def swd_directions(n_dirs, seed, offset, device):
+    """(n_dirs, 147) unit-norm Gaussian directions from the Philox stream at ``offset`` (147 counters per direction)."""
+    if int(n_dirs) < 1:
+        raise ValueError(f'swd_directions: needs a positive count, got {n_dirs}')
+    if torch.device(device).type != 'cuda':
+        raise TypeError(f'gan_lab_amd.ops: swd_directions draws on the GPU (got device {device!r}); the HIP path has no CPU '
+                        f'fallback')
+    out = torch.empty((int(n_dirs), SWD_DESC), dtype=torch.float32, device=device)
+    check(_lib.lib().ganlab_swd_directions_f32(_p(out), int(n_dirs), int(seed) & (2 ** 64 - 1), int(offset), _st()),
+          'swd_directions')
+    return out
+
+
 def lerp_rows(a, b, t):
     a, b, t = _c(a), _c(b), _c(t)
     out = torch.empty_like(a)

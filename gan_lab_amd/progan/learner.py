@@ -22,7 +22,7 @@ import warnings
 import torch
 from torch import nn
 
-from .. import ops, parallel, rng
+from .. import ops, parallel, rng, swd
 from .._int import LearnerConfigCopy
 from ..optim import EwmaTracker, ParamArena
 from ..resnetgan.learner import GANLearner
@@ -487,7 +487,8 @@ class ProGANLearner(GANLearner):
                         if gen_iter == num_gen_iters - 1 and z_valid_dl is not None and c.gen_metrics and \
                                 ((itr + 1) % c.num_iters_valid == 0 or itr == 0):     # (:921-928)
                             vals = self.compute_metrics(metrics=c.gen_metrics, metrics_type='Generator',
-                                                        z_valid_dl=z_valid_dl, valid_dl=None)
+                                                        z_valid_dl=z_valid_dl,
+                                                        valid_dl=valid_dl if swd.wanted(c.gen_metrics) else None)
                             if parallel.rank() == 0:
                                 print('|\n', 'Generator Validation Metrics:\n', *vals)
                     if num_gen_iters == 0:
@@ -554,6 +555,12 @@ class ProGANLearner(GANLearner):
             raise Exception('Invalid metrics_type. Only "generator", "critic", or "discriminator" are accepted.')
         metrics = [m.casefold() for m in metrics]
         want_grid = 'image grid' in metrics and metrics_type == 'generator'
+        want_swd = 'swd' in metrics
+        if want_swd and metrics_type != 'generator':
+            raise ValueError("'swd' is a generator metric: it compares the generated validation images with the validation "
+                             "reals and cannot be listed among the critic's metrics (config.disc_metrics)")
+        if want_swd and valid_dl is None:
+            raise ValueError("'swd' needs the validation reals: pass valid_dl (train(train_dl, valid_dl, z_valid_dl))")
         if want_grid and (self.ds_mean is None or self.data_config is None):
             self._update_data_config(raise_exception=True)
         self.disc_model.eval()
@@ -571,12 +578,24 @@ class ProGANLearner(GANLearner):
                                                    replacement=False)
                 self._grid_fill = 0
             self._img_grid_constructed = False
-            table = {m: torch.zeros(self.batch_size, n_batches, device=c.dev) for m in metrics}
+            table = {m: torch.zeros(self.batch_size, n_batches, device=c.dev) for m in metrics if m != 'swd'}
+            swd_eval, swd_left = self._swd_begin(n_z, valid_dl) if want_swd else (None, 0)
             for n, zbatch in enumerate(z_valid_dl):
                 zb = zbatch[0].to(c.dev).float()
                 gen_labels = zbatch[1].cpu() if len(zbatch) > 1 else None
                 k = len(zb)
                 xgen = self.gen_model(zb)
+                if swd_left > 0:
+                    # whole batches only, so that both sets hold the same images count; the generator evaluated is the one
+                    # this method evaluates, the reals follow its fade-in
+                    xb = next(valid_iter)[0].to(c.dev).float()
+                    if k == len(xb) and k <= swd_left:
+                        swd_eval.feed_fake(self._swd_fakes(zb, xgen))
+                        swd_eval.feed_real(self.fade_in_real(xb))
+                        swd_left -= k
+                    else:
+                        raise ValueError(f"'swd': validation latents and reals must come in equal batches (got {k} and "
+                                         f"{len(xb)} with {swd_left} images to go)")
                 y_fake = None
                 if 'fake realness' in metrics:
                     y_fake = self.disc_model(xgen)
@@ -609,12 +628,58 @@ class ProGANLearner(GANLearner):
             else:
                 self.disc_metrics_num += 1
             vals = {m: float(t.sum() / n_z) for m, t in table.items() if m != 'image grid'}
+            swd_lines = []
+            if want_swd:
+                vals['swd'], swd_lines = self._swd_finish(swd_eval)
         finally:
             self.gen_model.train()
             self.disc_model.train()
         self.last_metrics[metrics_type] = vals
-        width = '%-' + str(max(len(m) for m in metrics) + 3) + 's'
-        return ['    ' + (width % (m + ':')) + '%.4g' % vals[m] + '\n' for m in metrics if m != 'image grid']
+        names = metrics + [name for name, _ in swd_lines]
+        width = '%-' + str(max(len(m) for m in names) + 3) + 's'
+        return ['    ' + (width % (m + ':')) + '%.4g' % vals[m] + '\n' for m in metrics if m not in ('image grid', 'swd')] + \
+            ['    ' + (width % (name + ':')) + (v if isinstance(v, str) else '%.4g' % v) + '\n' for name, v in swd_lines]
+
+    def _swd_begin(self, n_z, valid_dl):
+        """The evaluation object of this resolution (buffers are kept across validation points of one resolution) and the
+        number of images per set: min(latents, reals) truncated to whole batches.  Below 16x16 the pyramid has no level:
+        (None, 0)."""
+        c = self.config
+        res = int(self.gen_model.curr_res)
+        if res < swd.MIN_RES:
+            return None, 0
+        n_use = min(n_z, len(valid_dl.dataset)) // self.batch_size * self.batch_size
+        if n_use < 1:
+            raise ValueError(f"'swd' needs at least one whole batch of {self.batch_size} validation latents and reals (got "
+                             f"{n_z} and {len(valid_dl.dataset)})")
+        key = (res, n_use)
+        if getattr(self, '_swd_eval', None) is None or self._swd_eval[0] != key:
+            self._swd_eval = (key, swd.SlicedWasserstein(res, n_use, nhoods_per_image=c.swd_nhoods,
+                                                         dir_repeats=c.swd_dir_repeats,
+                                                         dirs_per_repeat=c.swd_dirs_per_repeat, seed=c.swd_seed, device=c.dev))
+        self._swd_eval[1].reset()
+        return self._swd_eval[1], n_use
+
+    def _swd_fakes(self, zb, xgen):
+        """The images SWD scores for the latents ``zb``: the time-averaged generator's when ``use_ewma_gen`` is on (the
+        samples a user would draw), else ``xgen`` of the snapshot generator.  The extra forward's per-layer noise is drawn
+        at the process stream's position, which is then put back: the metric leaves the training stream where it was."""
+        if not self.config.use_ewma_gen:
+            return xgen
+        offset = rng._STATE['offset']
+        try:
+            return self.gen_model_lagged(zb)
+        finally:
+            rng._STATE['offset'] = offset
+
+    def _swd_finish(self, swd_eval):
+        """(the dict kept in last_metrics, [(line name, value)])."""
+        if swd_eval is None:
+            res = int(self.gen_model.curr_res)
+            return {'levels': [], 'swd': [], 'mean': float('nan')}, \
+                [('swd', f'nan (the pyramid starts at {swd.MIN_RES}x{swd.MIN_RES}; the current resolution is {res}x{res})')]
+        out = swd_eval.result()
+        return out, [(f'swd {r}x{r}', v) for r, v in zip(out['levels'], out['swd'])] + [('swd mean', out['mean'])]
 
     def _collect_grid_inputs(self, zb, gen_labels, n):
         """Pick the img_grid_sz^2 randomly chosen validation latents (fixed across calls, :311-330)."""

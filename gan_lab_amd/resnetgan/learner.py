@@ -53,6 +53,9 @@ class GANLearner(object):
         from .. import ada
         self.ada = ada.from_config(config)
         self.critic_aug = self.diffaug if self.diffaug is not None else self.ada
+        # the sliced Wasserstein metric's options ('swd' in config.gen_metrics; swd.py): checked here, used by compute_metrics
+        from .. import swd
+        swd.validate_config(config)
 
         self.curr_dataset_batch_num = 0
         self.curr_epoch_num = 1

@@ -82,3 +82,31 @@ def ada_params(n, h, w, state, policy, device='cuda'):
         out = ops.ada_params(n, h, w, state, policy, _STATE['seed'], _STATE['offset'], device)
     _STATE['offset'] += ops.ADA_COUNTERS * n
     return out
+
+
+def swd_positions(n_images, n_per_image, size, device='cuda', seed=None, offset=None):
+    """(n_images, n_per_image, 2) int32 patch centres uniform in [3, size - 4] for the sliced Wasserstein metric (swd.py);
+    ceil(n_per_image / 2) counters per image.  By default drawn from, and advancing, the process stream; with an explicit
+    ``seed`` / ``offset`` the draw is a pure function of them and the process stream is left alone - an evaluation uses the
+    same centres for the real and the fake set, and must not move the training stream."""
+    n_images, per = int(n_images), (int(n_per_image) + 1) // 2
+    if seed is None and offset is None:
+        if _DEVICE_BASE['block'] is not None:
+            raise RuntimeError('rng.swd_positions: not available while a step graph is being captured')
+        out = ops.swd_positions(n_images, n_per_image, size, _STATE['seed'], _STATE['offset'], device)
+        _STATE['offset'] += per * n_images
+        return out
+    return ops.swd_positions(n_images, n_per_image, size, _STATE['seed'] if seed is None else seed, offset or 0, device)
+
+
+def swd_directions(n_dirs, device='cuda', seed=None, offset=None):
+    """(n_dirs, 147) unit-norm Gaussian projection directions (swd.py); 147 counters per direction.  ``seed`` / ``offset``
+    as in ``swd_positions``."""
+    n_dirs = int(n_dirs)
+    if seed is None and offset is None:
+        if _DEVICE_BASE['block'] is not None:
+            raise RuntimeError('rng.swd_directions: not available while a step graph is being captured')
+        out = ops.swd_directions(n_dirs, _STATE['seed'], _STATE['offset'], device)
+        _STATE['offset'] += ops.SWD_DESC * n_dirs
+        return out
+    return ops.swd_directions(n_dirs, _STATE['seed'] if seed is None else seed, offset or 0, device)

@@ -536,6 +536,36 @@ int ganlab_ada_bwd_f32(const float* gy, const float* params, float* gx, int N, i
 int ganlab_ada_update_f32(float* state, const float* logits, int N, int interval, float step_size, float target,
                           void* stream);
 
+/* ---- sliced Wasserstein distance between Laplacian-pyramid patch descriptors (Karras et al. 2018; csrc/swd.hip)
+ * Planes are fp32, H and W even.  f = [1,4,6,4,1]/16 with mirror boundary (the edge sample is not repeated). */
+#define GANLAB_SWD_DESC 147
+/* y (planes, H/2, W/2) = (f (x) f)(x)[::2, ::2] */
+int ganlab_swd_down_f32(const float* x, float* y, long long planes, int H, int W, void* stream);
+/* out (planes, H, W) = g0 - up(g1); g1: (planes, H/2, W/2); up = zeros at the odd positions, then (2f) (x) (2f) */
+int ganlab_swd_band_f32(const float* g0, const float* g1, float* out, long long planes, int H, int W, void* stream);
+/* band: (N, 3, S, S); pos: (N, n, 2) int32 centres (y, x), clamped to [3, S-4]; desc: (N n, 147) rows in (channel, dy, dx) order
+ * (the caller passes the address of its first row); partials: (N, 6) doubles per image - sum of v per channel, then of v^2 */
+int ganlab_swd_gather_f32(const float* band, const int* pos, float* desc, double* partials, int N, int n, int S, void* stream);
+/* (images, 6) partials -> out[0..2] = per-channel mean, out[3..5] = population standard deviation over images * per_image
+ * values per channel; fixed order */
+int ganlab_swd_stats_f64(const double* partials, long long images, long long per_image, double* out, void* stream);
+/* out (D, M), out[d][m] = sum_k dirs[d][k] (desc[m][k] - mean[c(k)]) / std[c(k)]; desc (M, 147), dirs (D, 147), stats as written
+ * by ganlab_swd_stats_f64.  A zero std gives NaN. */
+int ganlab_swd_project_f32(const float* desc, const float* dirs, const double* stats, float* out, long long M, int D,
+                           void* stream);
+/* ascending sort of each of the `segments` rows of an (segments, M) buffer; out must not alias in; segments * M < 2^32 - 1 */
+size_t ganlab_swd_sort_workspace(int segments, long long M);
+int ganlab_swd_sort_f32(const float* in, float* out, int segments, long long M, void* workspace, size_t workspace_bytes,
+                        void* stream);
+/* out[0] = sum |a - b| / (D M) over two (D, M) buffers, fp64, fixed order */
+size_t ganlab_swd_distance_workspace(int D, long long M);
+int ganlab_swd_distance_f64(const float* a, const float* b, double* out, int D, long long M, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* (N, n, 2) centres uniform in [3, S-4] from the Philox stream: image i uses counters offset + i ceil(n / 2) .. */
+int ganlab_swd_positions_i32(int* out, int N, int n, int S, uint64_t seed, uint64_t offset, void* stream);
+/* (D, 147) unit-norm Gaussian directions: direction d uses counters offset + 147 d .. offset + 147 d + 146 */
+int ganlab_swd_directions_f32(float* out, int D, uint64_t seed, uint64_t offset, void* stream);
+
 /* ---- real-image input path -----------------------------------------------------------
  * uint8 NHWC dataset images -> 2^k box downsample -> fp32 NCHW ((v/255 - mean[c]) / std[c]); replaces the host
  * chain PIL Image.resize(BOX) -> ToTensor -> Normalize (data_config.py:307-341, progan/learner.py:1099-1112).
