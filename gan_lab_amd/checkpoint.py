@@ -210,6 +210,17 @@ def saved_config_fields(cfg):
     return {k: v for k, v in cfg.items() if not (k == 'ada' or k.startswith('ada_'))}
 
 
+def reference_config_fields(config):
+    """The config fields a reference-format checkpoint stores: ``diffaugment``, ``ada*``, ``swd_*`` and ``msssim_*`` are this
+    package's own and are left out while their feature is off, so the file is the reference's own."""
+    from . import msssim, swd
+    swd_off = not swd.wanted(getattr(config, 'gen_metrics', None))
+    msssim_off = not msssim.wanted(getattr(config, 'gen_metrics', None))
+    return saved_config_fields({k: v for k, v in vars(config).items() if not (k == 'diffaugment' and v is None) and
+                                not (swd_off and k.startswith('swd_')) and
+                                not (msssim_off and k.startswith('msssim_'))})
+
+
 def reference_checkpoint_dict(learner, g_names, d_names, extra=None):
     """The dict ``ProGANLearner.save_model`` of the reference writes (progan/learner.py:1257-1298; ``extra``: the
     StyleGAN additions, stylegan/learner.py:455-464), built from a product learner.  Tensors are moved to the CPU;
@@ -218,12 +229,7 @@ def reference_checkpoint_dict(learner, g_names, d_names, extra=None):
     from torch import nn
     c = learner.config
     cpu = lambda sd: OrderedDict((k, v.detach().cpu().clone()) for k, v in sd.items())  # noqa: E731
-    # (config.diffaugment, config.ada* and config.swd_* are this package's own fields: left out while off, so the file is the
-    # reference's own)
-    from . import swd
-    swd_off = not swd.wanted(getattr(c, 'gen_metrics', None))
-    cfg_state = saved_config_fields({k: v for k, v in vars(c).items() if not (k == 'diffaugment' and v is None) and
-                                     not (swd_off and k.startswith('swd_'))})
+    cfg_state = reference_config_fields(c)
     nl = {'leaky relu': lambda: nn.LeakyReLU(negative_slope=c.leakiness), 'tanh': nn.Tanh}.get(c.nonlinearity.casefold(),
                                                                                              nn.ReLU)()
     lagged = learner.materialize_lagged_generator() if c.use_ewma_gen else None

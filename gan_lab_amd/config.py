@@ -15,7 +15,12 @@ validated when the learner is built), ``ada`` (None = off, or an ADA policy such
 fixed p), ``ada_interval`` (critic iterations per adjustment) and ``ada_kimg`` (thousands of images for p to travel 0 -> 1);
 ``'swd'`` as an entry of ``gen_metrics`` (the sliced Wasserstein distance of swd.py between the validation reals and the generated
 validation images) with ``swd_nhoods`` (neighbourhoods per image and level), ``swd_dir_repeats`` x ``swd_dirs_per_repeat``
-(projection directions) and ``swd_seed``, validated when the learner is built.
+(projection directions) and ``swd_seed``, validated when the learner is built; ``'msssim'`` as an entry of ``gen_metrics`` (the
+multi-scale structural similarity of msssim.py between adjacent pairs of the generated validation images: the paper's
+mode-collapse indicator, lower = more diverse) with ``msssim_range``, the dynamic range L behind C1 = (0.01 L)^2 and
+C2 = (0.03 L)^2.  Images are scored in the network's own space, normalised by the dataset's mean and standard deviation, so the
+natural range depends on the dataset: the default 2.0 fits images spanning [-1, 1]; compare a run's ``msssim fake`` with its own
+``msssim real`` line rather than with numbers from another dataset or range.
 """
 import argparse
 import os
@@ -61,6 +66,7 @@ def _spec(model_type):
         ('ada', str, None), ('ada_p', float, 0.0), ('ada_target', _float_or_none, 0.6), ('ada_interval', int, 4),
         ('ada_kimg', float, 500.0),
         ('swd_nhoods', int, 128), ('swd_dir_repeats', int, 4), ('swd_dirs_per_repeat', int, 128), ('swd_seed', int, 0),
+        ('msssim_range', float, 2.0),
     ]
     if model_type == 'ResNet GAN':
         rows += [('batch_size', int, BS), ('num_main_iters', int, 300000), ('num_disc_iters', int, 5),

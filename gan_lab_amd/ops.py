@@ -1586,6 +1586,73 @@ def swd_directions(n_dirs, seed, offset, device):
     return out
 
 
+# ---- multi-scale structural similarity (csrc/msssim.hip; composed in gan_lab_amd/msssim.py) -------------------------------------
+MSSSIM_LEVELS = 5                    # GANLAB_MSSSIM_LEVELS (include/ganlab_hip.h)
+
+
+def _msssim_images(t, side, what):
+    """A (k, 3, side, side) fp32 GPU tensor whose images are contiguous (3, side, side) blocks a fixed number of floats apart:
+    a whole batch, or every second image of one (``x[0::2]``).  Never copied: the kernel takes the stride."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        raise TypeError(f'gan_lab_amd.ops: {what} must be a float32 tensor on the GPU (got {type(t).__name__}, '
+                        f'{getattr(t, "device", None)}, {getattr(t, "dtype", None)}); the HIP path has no CPU fallback')
+    if t.dim() != 4 or tuple(t.shape[1:]) != (3, side, side) or t.shape[0] < 1 or \
+            tuple(t.stride()[1:]) != (side * side, side, 1) or \
+            (t.shape[0] > 1 and t.stride(0) < 3 * side * side):
+        raise ValueError(f'{what}: needs (k, 3, {side}, {side}) images, each contiguous, got shape {tuple(t.shape)} strides '
+                         f'{tuple(t.stride())}')
+    return t
+
+
+def msssim_workspace(pairs, res, device):
+    """The fp64 per-tile partials of an evaluation of ``pairs`` pairs at ``res`` x ``res`` (all five levels), uninitialised."""
+    if torch.device(device).type != 'cuda':
+        raise TypeError(f'gan_lab_amd.ops: msssim_workspace allocates on the GPU (got device {device!r}); the HIP path has no '
+                        f'CPU fallback')
+    nbytes = _lib.lib().ganlab_msssim_workspace(int(pairs), int(res))
+    if nbytes == 0:
+        raise ValueError(f'msssim_workspace: needs pairs >= 1 and a power-of-two resolution in [16, 16384], got {pairs}, {res}')
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def msssim_level(a, b, level, res, c1, c2, workspace, first, pairs, next_a=None, next_b=None):
+    """Level ``level`` (side ``res >> level``) of pairs ``first ..`` of an evaluation of ``pairs`` pairs: their (cs, ssim) tile
+    partials go into ``workspace``, the 2 x 2 means of both images into ``next_a`` / ``next_b`` (None at the last level)."""
+    side = int(res) >> int(level)
+    a, b = _msssim_images(a, side, 'msssim_level a'), _msssim_images(b, side, 'msssim_level b')
+    count = a.shape[0]
+    workspace = _ct(workspace, torch.float64, 'msssim_level workspace')
+    if b.shape[0] != count or (count > 1 and a.stride(0) != b.stride(0)):
+        raise ValueError(f'msssim_level: a and b must hold the same number of images at the same stride, got '
+                         f'{tuple(a.shape)} / {a.stride(0)} and {tuple(b.shape)} / {b.stride(0)}')
+    if (next_a is None) != (next_b is None):
+        raise ValueError('msssim_level: next_a and next_b come together')
+    nstride = 0
+    if next_a is not None:
+        next_a = _msssim_images(next_a, side // 2, 'msssim_level next_a')
+        next_b = _msssim_images(next_b, side // 2, 'msssim_level next_b')
+        if next_a.shape[0] != count or next_b.shape[0] != count or (count > 1 and next_a.stride(0) != next_b.stride(0)):
+            raise ValueError(f'msssim_level: next_a and next_b must hold {count} images at one stride, got '
+                             f'{tuple(next_a.shape)} and {tuple(next_b.shape)}')
+        nstride = next_a.stride(0) if count > 1 else 3 * (side // 2) ** 2
+    stride = a.stride(0) if count > 1 else 3 * side * side
+    check(_lib.lib().ganlab_msssim_level_f32(_p(a), _p(b), stride, _p(next_a), _p(next_b), nstride, int(first), count,
+                                             int(pairs), int(res), int(level), float(c1), float(c2), _p(workspace),
+                                             workspace.numel() * 8, _st()), 'msssim_level')
+
+
+def msssim_finish(workspace, pairs, res, table, values, out):
+    """The evaluation's partials -> ``table`` (pairs, 5, 2) = (CS_i, SSIM_i) clamped at 0, ``values`` (pairs,) = the weighted
+    products, ``out`` (6,) = mean value, mean CS_0..3, mean SSIM_4; all fp64, fixed order."""
+    workspace = _ct(workspace, torch.float64, 'msssim_finish workspace')
+    for t, shape, what in ((table, (pairs, MSSSIM_LEVELS, 2), 'table'), (values, (pairs,), 'values'), (out, (6,), 'out')):
+        if tuple(_ct(t, torch.float64, f'msssim_finish {what}').shape) != shape or not t.is_contiguous():
+            raise ValueError(f'msssim_finish: {what} must be a contiguous {shape} tensor, got {tuple(t.shape)}')
+    check(_lib.lib().ganlab_msssim_finish_f64(_p(workspace), workspace.numel() * 8, int(pairs), int(res), _p(table), _p(values),
+                                              _p(out), _st()), 'msssim_finish')
+    return out
+
+
 def lerp_rows(a, b, t):
     a, b, t = _c(a), _c(b), _c(t)
     out = torch.empty_like(a)

@@ -22,7 +22,7 @@ import warnings
 import torch
 from torch import nn
 
-from .. import ops, parallel, rng, swd
+from .. import msssim, ops, parallel, rng, swd
 from .._int import LearnerConfigCopy
 from ..optim import EwmaTracker, ParamArena
 from ..resnetgan.learner import GANLearner
@@ -488,7 +488,8 @@ class ProGANLearner(GANLearner):
                                 ((itr + 1) % c.num_iters_valid == 0 or itr == 0):     # (:921-928)
                             vals = self.compute_metrics(metrics=c.gen_metrics, metrics_type='Generator',
                                                         z_valid_dl=z_valid_dl,
-                                                        valid_dl=valid_dl if swd.wanted(c.gen_metrics) else None)
+                                                        valid_dl=valid_dl if swd.wanted(c.gen_metrics) or
+                                                        msssim.wanted(c.gen_metrics) else None)
                             if parallel.rank() == 0:
                                 print('|\n', 'Generator Validation Metrics:\n', *vals)
                     if num_gen_iters == 0:
@@ -561,6 +562,13 @@ class ProGANLearner(GANLearner):
                              "reals and cannot be listed among the critic's metrics (config.disc_metrics)")
         if want_swd and valid_dl is None:
             raise ValueError("'swd' needs the validation reals: pass valid_dl (train(train_dl, valid_dl, z_valid_dl))")
+        want_ms = 'msssim' in metrics
+        if want_ms and metrics_type != 'generator':
+            raise ValueError("'msssim' is a generator metric: it compares generated validation images with each other and "
+                             "cannot be listed among the critic's metrics (config.disc_metrics)")
+        if want_ms and self.batch_size % 2:
+            raise ValueError(f"'msssim' scores adjacent pairs of a validation minibatch: config.batch_size must be even at "
+                             f"this resolution, got {self.batch_size}")
         if want_grid and (self.ds_mean is None or self.data_config is None):
             self._update_data_config(raise_exception=True)
         self.disc_model.eval()
@@ -578,24 +586,39 @@ class ProGANLearner(GANLearner):
                                                    replacement=False)
                 self._grid_fill = 0
             self._img_grid_constructed = False
-            table = {m: torch.zeros(self.batch_size, n_batches, device=c.dev) for m in metrics if m != 'swd'}
+            table = {m: torch.zeros(self.batch_size, n_batches, device=c.dev) for m in metrics if m not in ('swd', 'msssim')}
             swd_eval, swd_left = self._swd_begin(n_z, valid_dl) if want_swd else (None, 0)
+            ms_fake, ms_real, ms_fake_left, ms_real_left = self._msssim_begin(n_z, valid_dl) if want_ms else (None, None, 0, 0)
             for n, zbatch in enumerate(z_valid_dl):
                 zb = zbatch[0].to(c.dev).float()
                 gen_labels = zbatch[1].cpu() if len(zbatch) > 1 else None
                 k = len(zb)
                 xgen = self.gen_model(zb)
-                if swd_left > 0:
+                ms_fake_now = ms_fake_left > 0 and k == self.batch_size
+                ms_real_now = ms_real_left > 0 and k == self.batch_size
+                if swd_left > 0 or ms_fake_now or ms_real_now:
                     # whole batches only, so that both sets hold the same images count; the generator evaluated is the one
-                    # this method evaluates, the reals follow its fade-in
-                    xb = next(valid_iter)[0].to(c.dev).float()
-                    if k == len(xb) and k <= swd_left:
-                        swd_eval.feed_fake(self._swd_fakes(zb, xgen))
-                        swd_eval.feed_real(self.fade_in_real(xb))
+                    # this method evaluates, the reals follow its fade-in.  'swd' and 'msssim' share the scored fakes (one
+                    # extra forward, not two) and the faded-in reals
+                    xb = xr = None
+                    if swd_left > 0 or ms_real_now:
+                        xb = next(valid_iter)[0].to(c.dev).float()
+                        if k != len(xb) or (swd_left > 0 and k > swd_left):
+                            which = "'swd'" if swd_left > 0 else "'msssim'"
+                            raise ValueError(f"{which}: validation latents and reals must come in equal batches (got {k} and "
+                                             f"{len(xb)} with {swd_left if swd_left > 0 else ms_real_left} images to go)")
+                        xr = self.fade_in_real(xb)
+                    scored = self._swd_fakes(zb, xgen) if swd_left > 0 or ms_fake_now else None
+                    if swd_left > 0:
+                        swd_eval.feed_fake(scored)
+                        swd_eval.feed_real(xr)
                         swd_left -= k
-                    else:
-                        raise ValueError(f"'swd': validation latents and reals must come in equal batches (got {k} and "
-                                         f"{len(xb)} with {swd_left} images to go)")
+                    if ms_fake_now:
+                        ms_fake.feed(scored)
+                        ms_fake_left -= k
+                    if ms_real_now:
+                        ms_real.feed(xr)
+                        ms_real_left -= k
                 y_fake = None
                 if 'fake realness' in metrics:
                     y_fake = self.disc_model(xgen)
@@ -631,13 +654,17 @@ class ProGANLearner(GANLearner):
             swd_lines = []
             if want_swd:
                 vals['swd'], swd_lines = self._swd_finish(swd_eval)
+            if want_ms:
+                vals['msssim'], ms_lines = self._msssim_finish(ms_fake, ms_real)
+                swd_lines = swd_lines + ms_lines
         finally:
             self.gen_model.train()
             self.disc_model.train()
         self.last_metrics[metrics_type] = vals
         names = metrics + [name for name, _ in swd_lines]
         width = '%-' + str(max(len(m) for m in names) + 3) + 's'
-        return ['    ' + (width % (m + ':')) + '%.4g' % vals[m] + '\n' for m in metrics if m not in ('image grid', 'swd')] + \
+        return ['    ' + (width % (m + ':')) + '%.4g' % vals[m] + '\n' for m in metrics
+                if m not in ('image grid', 'swd', 'msssim')] + \
             ['    ' + (width % (name + ':')) + (v if isinstance(v, str) else '%.4g' % v) + '\n' for name, v in swd_lines]
 
     def _swd_begin(self, n_z, valid_dl):
@@ -661,7 +688,7 @@ class ProGANLearner(GANLearner):
         return self._swd_eval[1], n_use
 
     def _swd_fakes(self, zb, xgen):
-        """The images SWD scores for the latents ``zb``: the time-averaged generator's when ``use_ewma_gen`` is on (the
+        """The images SWD and MS-SSIM score for the latents ``zb``: the time-averaged generator's when ``use_ewma_gen`` is on (the
         samples a user would draw), else ``xgen`` of the snapshot generator.  The extra forward's per-layer noise is drawn
         at the process stream's position, which is then put back: the metric leaves the training stream where it was."""
         if not self.config.use_ewma_gen:
@@ -680,6 +707,43 @@ class ProGANLearner(GANLearner):
                 [('swd', f'nan (the pyramid starts at {swd.MIN_RES}x{swd.MIN_RES}; the current resolution is {res}x{res})')]
         out = swd_eval.result()
         return out, [(f'swd {r}x{r}', v) for r, v in zip(out['levels'], out['swd'])] + [('swd mean', out['mean'])]
+
+    def _msssim_begin(self, n_z, valid_dl):
+        """(evaluation of the fakes, evaluation of the reals or None, images to feed to each) at this resolution; buffers are
+        kept across validation points of one resolution.  Whole batches only (a batch is an even number of images, so pairs
+        never straddle batches).  Below 16x16 there is no fifth level: (None, None, 0, 0)."""
+        c = self.config
+        res = int(self.gen_model.curr_res)
+        if res < msssim.MIN_RES:
+            return None, None, 0, 0
+        bs = self.batch_size
+        n_fake = n_z // bs * bs
+        if n_fake < 1:
+            raise ValueError(f"'msssim' needs at least one whole batch of {bs} validation latents (got {n_z})")
+        n_real = min(n_z, len(valid_dl.dataset)) // bs * bs if valid_dl is not None else 0
+        key = (res, n_fake, n_real)
+        if getattr(self, '_msssim_eval', None) is None or self._msssim_eval[0] != key:
+            make = lambda n: msssim.MultiScaleSSIM(res, n, data_range=c.msssim_range, device=c.dev)  # noqa: E731
+            self._msssim_eval = (key, make(n_fake), make(n_real) if n_real else None)
+        _, fake, real = self._msssim_eval
+        fake.reset()
+        if real is not None:
+            real.reset()
+        return fake, real, n_fake, n_real
+
+    def _msssim_finish(self, fake, real):
+        """(the dict kept in last_metrics, [(line name, value)]).  'msssim real' scores the faded-in validation reals: the
+        number to compare 'msssim fake' against."""
+        if fake is None:
+            res = int(self.gen_model.curr_res)
+            return {'msssim': float('nan'), 'pairs': 0, 'per_level': [[], float('nan')]}, \
+                [('msssim', f'nan (five levels need {msssim.MIN_RES}x{msssim.MIN_RES}; the current resolution is {res}x{res})')]
+        out = fake.result()
+        lines = [('msssim fake', out['msssim'])]
+        if real is not None:
+            out['real'] = real.result()
+            lines.append(('msssim real', out['real']['msssim']))
+        return out, lines
 
     def _collect_grid_inputs(self, zb, gen_labels, n):
         """Pick the img_grid_sz^2 randomly chosen validation latents (fixed across calls, :311-330)."""

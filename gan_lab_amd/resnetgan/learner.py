@@ -56,6 +56,9 @@ class GANLearner(object):
         # the sliced Wasserstein metric's options ('swd' in config.gen_metrics; swd.py): checked here, used by compute_metrics
         from .. import swd
         swd.validate_config(config)
+        # ... and the multi-scale structural similarity's ('msssim' in config.gen_metrics; msssim.py)
+        from .. import msssim
+        msssim.validate_config(config)
 
         self.curr_dataset_batch_num = 0
         self.curr_epoch_num = 1

@@ -566,6 +566,27 @@ int ganlab_swd_positions_i32(int* out, int N, int n, int S, uint64_t seed, uint6
 /* (D, 147) unit-norm Gaussian directions: direction d uses counters offset + 147 d .. offset + 147 d + 146 */
 int ganlab_swd_directions_f32(float* out, int D, uint64_t seed, uint64_t offset, void* stream);
 
+/* ---- multi-scale structural similarity between pairs of images (Wang et al. 2003; the diversity metric of Karras et al. 2018;
+ * csrc/msssim.hip).  An evaluation holds P pairs of (3, R, R) fp32 images, R a power of two in [16, 16384], and
+ * runs five levels of side S = R >> level.  The window of a level has min(11, S) taps, sigma = 1.5 taps / 11 (computed in double
+ * on the host, rounded to fp32), and is applied in valid mode. */
+#define GANLAB_MSSSIM_LEVELS 5
+#define GANLAB_MSSSIM_WINDOW 11
+/* bytes of the per-tile fp64 partials of all five levels of P pairs (0: refused) */
+size_t ganlab_msssim_workspace(int P, int R);
+/* One level of pairs first .. first + count - 1 of the evaluation: image a of pair first + j starts at a + j pair_stride floats
+ * (b likewise; each image is a contiguous (3, S, S) block).  Writes the pairs' (cs, ssim) tile partials into their place in the
+ * workspace and, unless next_a / next_b are NULL (they must be at the last level), the 2 x 2 mean ((x00 + x01) + (x10 + x11)) / 4 of
+ * both images as (3, S/2, S/2) blocks next_pair_stride floats apart.  c1 = (0.01 L)^2, c2 = (0.03 L)^2. */
+int ganlab_msssim_level_f32(const float* a, const float* b, long long pair_stride, float* next_a, float* next_b,
+                            long long next_pair_stride, int first, int count, int P, int R, int level, float c1, float c2,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* After every level of every pair: table (P, 5, 2) doubles = (CS_i, SSIM_i), the means over channels and pixels clamped below at 0;
+ * values (P) = prod_{i<4} CS_i^w_i x SSIM_4^w_4, w = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333); out[0] = mean of values,
+ * out[1..4] = mean CS_0..3, out[5] = mean SSIM_4, each summed over the pairs in index order.  fp64, fixed order. */
+int ganlab_msssim_finish_f64(const void* workspace, size_t workspace_bytes, int P, int R, double* table, double* values,
+                             double* out, void* stream);
+
 /* ---- real-image input path -----------------------------------------------------------
  * uint8 NHWC dataset images -> 2^k box downsample -> fp32 NCHW ((v/255 - mean[c]) / std[c]); replaces the host
  * chain PIL Image.resize(BOX) -> ToTensor -> Normalize (data_config.py:307-341, progan/learner.py:1099-1112).
