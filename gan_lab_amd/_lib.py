@@ -247,6 +247,10 @@ SIGNATURES = {
     'ganlab_msssim_level_f32': (_c_int, [_c_p, _c_p, _c_ll, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_f,
                                          _c_p, _c_sz, _c_p]),
     'ganlab_msssim_finish_f64': (_c_int, [_c_p, _c_sz, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p]),
+    'ganlab_spectrum_workspace': (_c_sz, [_c_int, _c_int]),
+    'ganlab_spectrum_scratch': (_c_sz, [_c_int, _c_int]),
+    'ganlab_spectrum_feed_f32': (_c_int, [_c_p, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_sz, _c_p, _c_sz, _c_p]),
+    'ganlab_spectrum_finish_f64': (_c_int, [_c_p, _c_p, _c_sz, _c_int, _c_int, _c_p, _c_sz, _c_p]),
     'ganlab_adam_dev_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_f, _c_f, _c_f, _c_f, _c_p]),
     'ganlab_step_scalars_size': (_c_int, []),
     'ganlab_set_step_scalars': (_c_int, [_c_p, _c_u64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),

@@ -20,7 +20,12 @@ multi-scale structural similarity of msssim.py between adjacent pairs of the gen
 mode-collapse indicator, lower = more diverse) with ``msssim_range``, the dynamic range L behind C1 = (0.01 L)^2 and
 C2 = (0.03 L)^2.  Images are scored in the network's own space, normalised by the dataset's mean and standard deviation, so the
 natural range depends on the dataset: the default 2.0 fits images spanning [-1, 1]; compare a run's ``msssim fake`` with its own
-``msssim real`` line rather than with numbers from another dataset or range.
+``msssim real`` line rather than with numbers from another dataset or range; ``'spectrum'`` as an entry of ``gen_metrics`` (the
+radial power-spectrum distance of spectrum.py between the generated validation images and the validation reals, in dB over all
+radii and over the upper half of them: the number that moves when an upsample, a blur or a low-precision plane bends the
+high-frequency tail) with ``spectrum_window``: ``'hann'`` (the default) tapers each image with a periodic Hann window before the
+transform, so that the jump between opposite image borders does not leak a 1/f^2 cross into every radius; ``'none'`` transforms
+the image as it is (right for periodic textures, and the setting under which a circular shift leaves the profile unchanged).
 """
 import argparse
 import os
@@ -66,7 +71,7 @@ def _spec(model_type):
         ('ada', str, None), ('ada_p', float, 0.0), ('ada_target', _float_or_none, 0.6), ('ada_interval', int, 4),
         ('ada_kimg', float, 500.0),
         ('swd_nhoods', int, 128), ('swd_dir_repeats', int, 4), ('swd_dirs_per_repeat', int, 128), ('swd_seed', int, 0),
-        ('msssim_range', float, 2.0),
+        ('msssim_range', float, 2.0), ('spectrum_window', str.casefold, 'hann'),
     ]
     if model_type == 'ResNet GAN':
         rows += [('batch_size', int, BS), ('num_main_iters', int, 300000), ('num_disc_iters', int, 5),

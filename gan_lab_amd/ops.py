@@ -1653,6 +1653,80 @@ def msssim_finish(workspace, pairs, res, table, values, out):
     return out
 
 
+# ---- radial power spectrum (csrc/spectrum.hip; composed in gan_lab_amd/spectrum.py) ---------------------------------------------
+SPECTRUM_MIN_RES, SPECTRUM_MAX_RES = 16, 1024        # GANLAB_SPECTRUM_MIN_RES / _MAX_RES (include/ganlab_hip.h)
+SPECTRUM_WINDOWS = {'none': 0, 'hann': 1}            # GANLAB_SPECTRUM_WINDOW_*
+
+
+def _spectrum_size(query, count, res, what):
+    nbytes = query(int(count), int(res))
+    if nbytes == 0:
+        raise ValueError(f'{what}: needs a count >= 1 and a power-of-two resolution in [{SPECTRUM_MIN_RES}, {SPECTRUM_MAX_RES}], '
+                         f'got {count}, {res}')
+    return nbytes
+
+
+def spectrum_scratch_bytes(count, res):
+    """Bytes of scratch a feed of ``count`` images at ``res`` x ``res`` needs (a host call)."""
+    return _spectrum_size(_lib.lib().ganlab_spectrum_scratch, count, res, 'spectrum_scratch_bytes')
+
+
+def _spectrum_alloc(nbytes, device, what):
+    if torch.device(device).type != 'cuda':
+        raise TypeError(f'gan_lab_amd.ops: {what} allocates on the GPU (got device {device!r}); the HIP path has no CPU fallback')
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def spectrum_workspace(n_images, res, device):
+    """The (n_images, res / 2 + 1) fp64 per-image profiles of an evaluation, uninitialised."""
+    if torch.device(device).type != 'cuda':
+        raise TypeError(f'gan_lab_amd.ops: spectrum_workspace allocates on the GPU (got device {device!r}); the HIP path has no '
+                        f'CPU fallback')
+    nbytes = _spectrum_size(_lib.lib().ganlab_spectrum_workspace, n_images, res, 'spectrum_workspace')
+    return _spectrum_alloc(nbytes, device, 'spectrum_workspace').view(int(n_images), int(res) // 2 + 1)
+
+
+def spectrum_scratch(count, res, device):
+    """Scratch for feeds of up to ``count`` images: tables, half spectra and per-tile bin sums, uninitialised."""
+    if torch.device(device).type != 'cuda':
+        raise TypeError(f'gan_lab_amd.ops: spectrum_scratch allocates on the GPU (got device {device!r}); the HIP path has no '
+                        f'CPU fallback')
+    return _spectrum_alloc((spectrum_scratch_bytes(count, res) + 7) // 8 * 8, device, 'spectrum_scratch')
+
+
+def spectrum_feed(x, res, window, scratch, workspace, first, n_images):
+    """The profiles of the (k, 3, res, res) fp32 images ``x``, images ``first ..`` of an evaluation of ``n_images``, into their
+    rows of ``workspace``.  ``window``: 'hann' or 'none'."""
+    x = _msssim_images(x, int(res), 'spectrum_feed x')
+    if window not in SPECTRUM_WINDOWS:
+        raise ValueError(f'spectrum_feed: window must be one of {sorted(SPECTRUM_WINDOWS)}, got {window!r}')
+    scratch = _ct(scratch, torch.float64, 'spectrum_feed scratch')
+    workspace = _ct(workspace, torch.float64, 'spectrum_feed workspace')
+    count = x.shape[0]
+    stride = x.stride(0) if count > 1 else 3 * int(res) ** 2
+    check(_lib.lib().ganlab_spectrum_feed_f32(_p(x), stride, int(first), count, int(n_images), int(res), SPECTRUM_WINDOWS[window],
+                                              _p(scratch), scratch.numel() * 8, _p(workspace), workspace.numel() * 8, _st()),
+          'spectrum_feed')
+
+
+def spectrum_finish(workspace_a, workspace_b, n_images, res, out):
+    """``out`` = set a's profile S[0 .. res/2] and its decibels; with ``workspace_b`` also set b's two rows, then the distances
+    'spectrum' and 'hf': 4 (res / 2 + 1) + 2 fp64 values, else 2 (res / 2 + 1)."""
+    workspace_a = _ct(workspace_a, torch.float64, 'spectrum_finish workspace_a')
+    if workspace_b is not None:
+        workspace_b = _ct(workspace_b, torch.float64, 'spectrum_finish workspace_b')
+        if workspace_b.numel() != workspace_a.numel():
+            raise ValueError(f'spectrum_finish: the two workspaces must have one size, got {workspace_a.numel()} and '
+                             f'{workspace_b.numel()}')
+    nb = int(res) // 2 + 1
+    need = 4 * nb + 2 if workspace_b is not None else 2 * nb
+    if _ct(out, torch.float64, 'spectrum_finish out').numel() != need or not out.is_contiguous():
+        raise ValueError(f'spectrum_finish: out must be a contiguous tensor of {need} values, got {tuple(out.shape)}')
+    check(_lib.lib().ganlab_spectrum_finish_f64(_p(workspace_a), _p(workspace_b), workspace_a.numel() * 8, int(n_images), int(res),
+                                                _p(out), out.numel() * 8, _st()), 'spectrum_finish')
+    return out
+
+
 def lerp_rows(a, b, t):
     a, b, t = _c(a), _c(b), _c(t)
     out = torch.empty_like(a)

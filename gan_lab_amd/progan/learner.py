@@ -22,7 +22,7 @@ import warnings
 import torch
 from torch import nn
 
-from .. import msssim, ops, parallel, rng, swd
+from .. import msssim, ops, parallel, rng, spectrum, swd
 from .._int import LearnerConfigCopy
 from ..optim import EwmaTracker, ParamArena
 from ..resnetgan.learner import GANLearner
@@ -489,7 +489,8 @@ class ProGANLearner(GANLearner):
                             vals = self.compute_metrics(metrics=c.gen_metrics, metrics_type='Generator',
                                                         z_valid_dl=z_valid_dl,
                                                         valid_dl=valid_dl if swd.wanted(c.gen_metrics) or
-                                                        msssim.wanted(c.gen_metrics) else None)
+                                                        msssim.wanted(c.gen_metrics) or
+                                                        spectrum.wanted(c.gen_metrics) else None)
                             if parallel.rank() == 0:
                                 print('|\n', 'Generator Validation Metrics:\n', *vals)
                     if num_gen_iters == 0:
@@ -569,6 +570,12 @@ class ProGANLearner(GANLearner):
         if want_ms and self.batch_size % 2:
             raise ValueError(f"'msssim' scores adjacent pairs of a validation minibatch: config.batch_size must be even at "
                              f"this resolution, got {self.batch_size}")
+        want_sp = 'spectrum' in metrics
+        if want_sp and metrics_type != 'generator':
+            raise ValueError("'spectrum' is a generator metric: it compares the generated validation images with the validation "
+                             "reals and cannot be listed among the critic's metrics (config.disc_metrics)")
+        if want_sp and valid_dl is None:
+            raise ValueError("'spectrum' needs the validation reals: pass valid_dl (train(train_dl, valid_dl, z_valid_dl))")
         if want_grid and (self.ds_mean is None or self.data_config is None):
             self._update_data_config(raise_exception=True)
         self.disc_model.eval()
@@ -586,9 +593,11 @@ class ProGANLearner(GANLearner):
                                                    replacement=False)
                 self._grid_fill = 0
             self._img_grid_constructed = False
-            table = {m: torch.zeros(self.batch_size, n_batches, device=c.dev) for m in metrics if m not in ('swd', 'msssim')}
+            table = {m: torch.zeros(self.batch_size, n_batches, device=c.dev) for m in metrics
+                     if m not in ('swd', 'msssim', 'spectrum')}
             swd_eval, swd_left = self._swd_begin(n_z, valid_dl) if want_swd else (None, 0)
             ms_fake, ms_real, ms_fake_left, ms_real_left = self._msssim_begin(n_z, valid_dl) if want_ms else (None, None, 0, 0)
+            sp_fake, sp_real, sp_left = self._spectrum_begin(n_z, valid_dl) if want_sp else (None, None, 0)
             for n, zbatch in enumerate(z_valid_dl):
                 zb = zbatch[0].to(c.dev).float()
                 gen_labels = zbatch[1].cpu() if len(zbatch) > 1 else None
@@ -596,23 +605,28 @@ class ProGANLearner(GANLearner):
                 xgen = self.gen_model(zb)
                 ms_fake_now = ms_fake_left > 0 and k == self.batch_size
                 ms_real_now = ms_real_left > 0 and k == self.batch_size
-                if swd_left > 0 or ms_fake_now or ms_real_now:
+                both_left = max(swd_left, sp_left)       # 'swd' and 'spectrum' score the same two sets of equal size
+                if both_left > 0 or ms_fake_now or ms_real_now:
                     # whole batches only, so that both sets hold the same images count; the generator evaluated is the one
-                    # this method evaluates, the reals follow its fade-in.  'swd' and 'msssim' share the scored fakes (one
-                    # extra forward, not two) and the faded-in reals
+                    # this method evaluates, the reals follow its fade-in.  'swd', 'msssim' and 'spectrum' share the scored
+                    # fakes (one extra forward, not three) and the faded-in reals
                     xb = xr = None
-                    if swd_left > 0 or ms_real_now:
+                    if both_left > 0 or ms_real_now:
                         xb = next(valid_iter)[0].to(c.dev).float()
-                        if k != len(xb) or (swd_left > 0 and k > swd_left):
-                            which = "'swd'" if swd_left > 0 else "'msssim'"
+                        if k != len(xb) or (both_left > 0 and k > both_left):
+                            which = "'swd'" if swd_left > 0 else "'spectrum'" if sp_left > 0 else "'msssim'"
                             raise ValueError(f"{which}: validation latents and reals must come in equal batches (got {k} and "
-                                             f"{len(xb)} with {swd_left if swd_left > 0 else ms_real_left} images to go)")
+                                             f"{len(xb)} with {both_left if both_left > 0 else ms_real_left} images to go)")
                         xr = self.fade_in_real(xb)
-                    scored = self._swd_fakes(zb, xgen) if swd_left > 0 or ms_fake_now else None
+                    scored = self._swd_fakes(zb, xgen) if both_left > 0 or ms_fake_now else None
                     if swd_left > 0:
                         swd_eval.feed_fake(scored)
                         swd_eval.feed_real(xr)
                         swd_left -= k
+                    if sp_left > 0:
+                        sp_fake.feed(scored)
+                        sp_real.feed(xr)
+                        sp_left -= k
                     if ms_fake_now:
                         ms_fake.feed(scored)
                         ms_fake_left -= k
@@ -657,6 +671,9 @@ class ProGANLearner(GANLearner):
             if want_ms:
                 vals['msssim'], ms_lines = self._msssim_finish(ms_fake, ms_real)
                 swd_lines = swd_lines + ms_lines
+            if want_sp:
+                vals['spectrum'], sp_lines = self._spectrum_finish(sp_fake, sp_real)
+                swd_lines = swd_lines + sp_lines
         finally:
             self.gen_model.train()
             self.disc_model.train()
@@ -664,7 +681,7 @@ class ProGANLearner(GANLearner):
         names = metrics + [name for name, _ in swd_lines]
         width = '%-' + str(max(len(m) for m in names) + 3) + 's'
         return ['    ' + (width % (m + ':')) + '%.4g' % vals[m] + '\n' for m in metrics
-                if m not in ('image grid', 'swd', 'msssim')] + \
+                if m not in ('image grid', 'swd', 'msssim', 'spectrum')] + \
             ['    ' + (width % (name + ':')) + (v if isinstance(v, str) else '%.4g' % v) + '\n' for name, v in swd_lines]
 
     def _swd_begin(self, n_z, valid_dl):
@@ -688,7 +705,7 @@ class ProGANLearner(GANLearner):
         return self._swd_eval[1], n_use
 
     def _swd_fakes(self, zb, xgen):
-        """The images SWD and MS-SSIM score for the latents ``zb``: the time-averaged generator's when ``use_ewma_gen`` is on (the
+        """The images SWD, MS-SSIM and the power spectrum score for the latents ``zb``: the time-averaged generator's when ``use_ewma_gen`` is on (the
         samples a user would draw), else ``xgen`` of the snapshot generator.  The extra forward's per-layer noise is drawn
         at the process stream's position, which is then put back: the metric leaves the training stream where it was."""
         if not self.config.use_ewma_gen:
@@ -744,6 +761,38 @@ class ProGANLearner(GANLearner):
             out['real'] = real.result()
             lines.append(('msssim real', out['real']['msssim']))
         return out, lines
+
+    def _spectrum_begin(self, n_z, valid_dl):
+        """(evaluation of the fakes, evaluation of the reals, images per set) at this resolution: min(latents, reals) truncated to
+        whole batches, as SWD counts them; buffers are kept across validation points of one resolution.  Outside
+        [16, 1024] the kernels have no transform: (None, None, 0)."""
+        c = self.config
+        res = int(self.gen_model.curr_res)
+        if res < spectrum.MIN_RES or res > spectrum.MAX_RES:
+            return None, None, 0
+        n_use = min(n_z, len(valid_dl.dataset)) // self.batch_size * self.batch_size
+        if n_use < 1:
+            raise ValueError(f"'spectrum' needs at least one whole batch of {self.batch_size} validation latents and reals (got "
+                             f"{n_z} and {len(valid_dl.dataset)})")
+        key = (res, n_use)
+        if getattr(self, '_spectrum_eval', None) is None or self._spectrum_eval[0] != key:
+            make = lambda: spectrum.PowerSpectrum(res, n_use, window=c.spectrum_window, device=c.dev)  # noqa: E731
+            self._spectrum_eval = (key, make(), make())
+        _, fake, real = self._spectrum_eval
+        fake.reset()
+        real.reset()
+        return fake, real, n_use
+
+    def _spectrum_finish(self, fake, real):
+        """(the dict kept in last_metrics: both profiles in dB, for plotting, and the two distances; [(line name, value)])."""
+        if fake is None:
+            res = int(self.gen_model.curr_res)
+            nan = float('nan')
+            return {'spectrum': nan, 'hf': nan, 'fake_db': [], 'real_db': [], 'images': 0}, \
+                [('spectrum', f'nan (the transform covers {spectrum.MIN_RES}x{spectrum.MIN_RES} to '
+                              f'{spectrum.MAX_RES}x{spectrum.MAX_RES}; the current resolution is {res}x{res})')]
+        out = spectrum.distance(fake, real)
+        return out, [('spectrum', out['spectrum']), ('spectrum hf', out['hf'])]
 
     def _collect_grid_inputs(self, zb, gen_labels, n):
         """Pick the img_grid_sz^2 randomly chosen validation latents (fixed across calls, :311-330)."""

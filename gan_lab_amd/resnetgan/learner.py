@@ -59,6 +59,9 @@ class GANLearner(object):
         # ... and the multi-scale structural similarity's ('msssim' in config.gen_metrics; msssim.py)
         from .. import msssim
         msssim.validate_config(config)
+        # ... and the radial power-spectrum distance's ('spectrum' in config.gen_metrics; spectrum.py)
+        from .. import spectrum
+        spectrum.validate_config(config)
 
         self.curr_dataset_batch_num = 0
         self.curr_epoch_num = 1

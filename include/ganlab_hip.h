@@ -587,6 +587,30 @@ int ganlab_msssim_level_f32(const float* a, const float* b, long long pair_strid
 int ganlab_msssim_finish_f64(const void* workspace, size_t workspace_bytes, int P, int R, double* table, double* values,
                              double* out, void* stream);
 
+/* ---- radial power spectrum of a set of images (Durall et al. 2020, Dzanic et al. 2020; csrc/spectrum.hip).
+ * An evaluation holds N (3, R, R) fp32 images, R a power of two in [16, 1024] (any other R: GANLAB_EUNSUPPORTED).  Per image:
+ * y = x w[i] w[j] (periodic Hann window, or none), P[u,v] = sum_c |DFT2(y_c)[u,v]|^2 / (3 R^2 W), W = (sum_i w[i]^2 / R)^2, and
+ * A[k], k = 0 .. R/2, = the mean of P over the signed frequencies (ku, kv) in [-R/2, R/2)^2 with
+ * (2k-1)^2 <= 4 (ku^2 + kv^2) < (2k+1)^2 (bin 0: DC alone).  The FFT is fp32 in LDS, every sum of |F|^2 is fp64 in a fixed order. */
+#define GANLAB_SPECTRUM_MIN_RES 16
+#define GANLAB_SPECTRUM_MAX_RES 1024
+#define GANLAB_SPECTRUM_WINDOW_NONE 0
+#define GANLAB_SPECTRUM_WINDOW_HANN 1
+/* bytes of the N per-image profiles, (N, R/2 + 1) doubles (0: refused) */
+size_t ganlab_spectrum_workspace(int N, int R);
+/* bytes of the scratch one feed of count images needs: the window and twiddle tables, the half spectrum (3, R, R/2 + 1) complex
+ * fp32 per image between the row and the column pass, and the per-tile fp64 bin sums (0: refused) */
+size_t ganlab_spectrum_scratch(int count, int R);
+/* Profiles of images first .. first + count - 1 of the evaluation into their rows of the workspace; image j is the contiguous
+ * (3, R, R) block at x + j image_stride floats.  The scratch may be reused by the next call on the same stream. */
+int ganlab_spectrum_feed_f32(const float* x, long long image_stride, int first, int count, int N, int R, int window,
+                             void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* Once all N images are in: out[0 .. R/2] = S[k], the mean of A_n[k] over the images in index order; out[R/2+1 .. R+1] =
+ * 10 log10(max(S[k], 1e-30)).  With workspace_b (a second evaluation of N images; else NULL) the same two rows of set b follow,
+ * then spectrum = sqrt(mean_{k=1..R/2} (dB_b[k] - dB_a[k])^2) and hf = the same over k = R/4+1 .. R/2: 4 (R/2 + 1) + 2 doubles. */
+int ganlab_spectrum_finish_f64(const void* workspace_a, const void* workspace_b, size_t workspace_bytes, int N, int R, double* out,
+                               size_t out_bytes, void* stream);
+
 /* ---- real-image input path -----------------------------------------------------------
  * uint8 NHWC dataset images -> 2^k box downsample -> fp32 NCHW ((v/255 - mean[c]) / std[c]); replaces the host
  * chain PIL Image.resize(BOX) -> ToTensor -> Normalize (data_config.py:307-341, progan/learner.py:1099-1112).
