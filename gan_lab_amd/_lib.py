@@ -39,6 +39,15 @@ class PackDesc(ctypes.Structure):
                 ('mode', _c_int), ('up', _c_int), ('scale', _c_f), ('reserved', _c_int), ('total', _c_ll),
                 ('block0', _c_ll)]
 
+class SnJob(ctypes.Structure):
+    """Mirror of `ganlab_sn_job` (include/ganlab_hip.h): one layer of the spectral-normalisation job table."""
+    _fields_ = [('w', _c_p), ('w_sn', _c_p), ('g_sn', _c_p), ('gw', _c_p), ('u', _c_p), ('v', _c_p), ('sigma', _c_p),
+                ('tpart', _c_p), ('s', _c_p), ('dpart', _c_p), ('R', _c_int), ('K', _c_int), ('blk_t0', _c_ll),
+                ('blk_s0', _c_ll), ('blk_e0', _c_ll)]
+
+
+SN_ROW_CHUNK, SN_COL_TILE, SN_ELEM_BLOCK = 16, 1024, 2048      # GANLAB_SN_* (include/ganlab_hip.h)
+
 # name -> (restype, argtypes): must list every function declared in include/ganlab_hip.h
 SIGNATURES = {
     'ganlab_abi_version': (_c_int, []),
@@ -215,6 +224,8 @@ SIGNATURES = {
     'ganlab_sum_workspace': (_c_sz, [_c_ll]),
     'ganlab_bce_logits_fwd_f32': (_c_int, [_c_p, _c_p, _c_int, _c_f, _c_p]),
     'ganlab_bce_logits_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_f, _c_p]),
+    'ganlab_hinge_fwd_f32': (_c_int, [_c_p, _c_p, _c_int, _c_f, _c_f, _c_p]),
+    'ganlab_hinge_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_f, _c_f, _c_p]),
     'ganlab_chnorm_penalty_fwd_f32': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_ll, _c_f, _c_f, _c_p, _c_sz, _c_p]),
     'ganlab_chnorm_penalty_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_ll, _c_f, _c_f, _c_p]),
     'ganlab_adam_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
@@ -252,6 +263,9 @@ SIGNATURES = {
     'ganlab_spectrum_feed_f32': (_c_int, [_c_p, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_sz, _c_p, _c_sz, _c_p]),
     'ganlab_spectrum_finish_f64': (_c_int, [_c_p, _c_p, _c_sz, _c_int, _c_int, _c_p, _c_sz, _c_p]),
     'ganlab_adam_dev_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_f, _c_f, _c_f, _c_f, _c_p]),
+    'ganlab_sn_job_size': (_c_int, []),
+    'ganlab_sn_refresh': (_c_int, [_c_p, _c_int, _c_ll, _c_ll, _c_ll, _c_int, _c_f, _c_p]),
+    'ganlab_sn_backward': (_c_int, [_c_p, _c_int, _c_ll, _c_p]),
     'ganlab_step_scalars_size': (_c_int, []),
     'ganlab_set_step_scalars': (_c_int, [_c_p, _c_u64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
 }
@@ -294,6 +308,9 @@ def lib():
         if handle.ganlab_pack_desc_size() != ctypes.sizeof(PackDesc):
             raise GanlabLibraryError(f'PackDesc mirror is {ctypes.sizeof(PackDesc)} bytes, the library\'s '
                                      f'ganlab_pack_desc {handle.ganlab_pack_desc_size()}: header and binding disagree')
+        if handle.ganlab_sn_job_size() != ctypes.sizeof(SnJob):
+            raise GanlabLibraryError(f'SnJob mirror is {ctypes.sizeof(SnJob)} bytes, the library\'s '
+                                     f'ganlab_sn_job {handle.ganlab_sn_job_size()}: header and binding disagree')
         _LIB = handle
     return _LIB
 

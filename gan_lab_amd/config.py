@@ -25,7 +25,11 @@ radial power-spectrum distance of spectrum.py between the generated validation i
 radii and over the upper half of them: the number that moves when an upsample, a blur or a low-precision plane bends the
 high-frequency tail) with ``spectrum_window``: ``'hann'`` (the default) tapers each image with a periodic Hann window before the
 transform, so that the jump between opposite image borders does not leak a 1/f^2 cross into every radius; ``'none'`` transforms
-the image as it is (right for periodic textures, and the setting under which a circular shift leaves the profile unchanged).
+the image as it is (right for periodic textures, and the setting under which a circular shift leaves the profile unchanged);
+``spectral_norm`` (ResNet GAN only; False = off): every Conv2dEx / LinearEx weight of the critic is divided by its largest
+singular value, estimated by one power iteration per critic update (spectral_norm.py; excludes ``use_equalized_lr``; validated
+when the learner is built), and ``loss='hinge'`` (ResNet GAN only) is the loss usually trained with it - with both on,
+``gradient_penalty=None`` is a sane setting.
 """
 import argparse
 import os
@@ -78,7 +82,7 @@ def _spec(model_type):
                  ('lr_base', float, .0001), ('lr_sched', str.casefold, None), ('beta2', float, .9),
                  ('res_samples', int, 64), ('res_dataset', int, 64), ('blur_type', str.casefold, None),
                  ('eps_drift', float, 0.), ('len_latent', int, 128), ('nonlinearity', str.casefold, 'relu'),
-                 ('leakiness', float, .01), ('use_equalized_lr', bool, False)]
+                 ('leakiness', float, .01), ('use_equalized_lr', bool, False), ('spectral_norm', bool, False)]
     else:
         rows += [('batch_size', int, BS),
                  ('bs_dict', dict, {4: BS, 8: BS, 16: BS, 32: BS, 64: BS, 128: BS, 256: BS, 512: BS // 2,

@@ -1539,6 +1539,21 @@ __global__ void bce_bwd_kernel(const float* __restrict__ x, const float* __restr
   }
 }
 
+__global__ __launch_bounds__(256) void hinge_fwd_kernel(const float* __restrict__ x, float* __restrict__ out, int n,
+                                                        float a, float b) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) s += fmaxf(a + b * x[i], 0.f);
+  s = gl_block_sum_256(s, red);
+  if (threadIdx.x == 0) out[0] = s / (float)n;
+}
+
+__global__ void hinge_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gout, float* __restrict__ gx,
+                                 int n, float a, float b) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) gx[i] = (a + b * x[i] > 0.f) ? gout[0] * b / (float)n : 0.f;
+}
+
 __global__ __launch_bounds__(256) void chnorm_pen_stage1(const float* __restrict__ g, float* __restrict__ part,
                                                          int N, int C, long long HW, float gamma) {
   __shared__ float red[4];
@@ -2207,6 +2222,18 @@ int ganlab_bce_logits_fwd_f32(const float* x, float* out, int n, float target, v
 int ganlab_bce_logits_bwd_f32(const float* x, const float* gout, float* gx, int n, float target, void* stream) {
   if (!x || !gout || !gx || n <= 0) return GANLAB_EINVAL;
   GL_LAUNCH(bce_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, ST, x, gout, gx, n, target);
+  return GL_CHECK_LAUNCH();
+}
+
+int ganlab_hinge_fwd_f32(const float* x, float* out, int n, float a, float b, void* stream) {
+  if (!x || !out || n <= 0) return GANLAB_EINVAL;
+  GL_LAUNCH(hinge_fwd_kernel, dim3(1), dim3(256), 0, ST, x, out, n, a, b);
+  return GL_CHECK_LAUNCH();
+}
+
+int ganlab_hinge_bwd_f32(const float* x, const float* gout, float* gx, int n, float a, float b, void* stream) {
+  if (!x || !gout || !gx || n <= 0) return GANLAB_EINVAL;
+  GL_LAUNCH(hinge_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, ST, x, gout, gx, n, a, b);
   return GL_CHECK_LAUNCH();
 }
 

@@ -1727,6 +1727,68 @@ def spectrum_finish(workspace_a, workspace_b, n_images, res, out):
     return out
 
 
+# ---- spectral normalisation: every weight of a critic per launch (csrc/spectral.hip) -----------------------------------
+SN_EPS = 1e-12      # torch.nn.utils.spectral_norm's eps
+
+
+class SnTable(object):
+    """Device-resident job table of ``ganlab_sn_refresh`` / ``ganlab_sn_backward``.  ``layers``: one dict per weight with
+    the float32 GPU tensors ``w`` (the parameter, viewed as (shape[0], -1)), ``w_sn``, ``g_sn``, ``gw`` (same numel), ``u``
+    (shape[0]), ``v`` (numel / shape[0]) and ``sigma`` (1); every one contiguous and 16-byte aligned.  Built and uploaded once
+    (outside any capture), together with the scratch the passes use; keeps the tensors it points at alive."""
+
+    def __init__(self, layers):
+        if not layers:
+            raise ValueError('SnTable: no layers')
+        RC, TC, EB = _lib.SN_ROW_CHUNK, _lib.SN_COL_TILE, _lib.SN_ELEM_BLOCK
+        self.layers = [dict(d) for d in layers]
+        dev = self.layers[0]['w'].device
+        geo, need = [], 0
+        for d in self.layers:
+            w = d['w']
+            R = int(w.shape[0])
+            K = w.numel() // R
+            want = {'w': R * K, 'w_sn': R * K, 'g_sn': R * K, 'gw': R * K, 'u': R, 'v': K, 'sigma': 1}
+            for name, n in want.items():
+                t = d[name]
+                _c(t, f'SnTable {name}')
+                if not t.is_contiguous() or t.numel() != n or t.data_ptr() % 16 or t.device != dev:
+                    raise ValueError(f'SnTable: {name} must be contiguous, 16-byte aligned, on {dev}, with {n} elements '
+                                     f'(got {tuple(t.shape)} at {t.data_ptr():#x} on {t.device})')
+            nrc, nct, neb = (R + RC - 1) // RC, (K + TC - 1) // TC, (R * K + EB - 1) // EB
+            offs = []
+            for n in (nrc * K, R, neb):
+                offs.append(need)
+                need += (n + 3) // 4 * 4
+            geo.append((R, K, nrc * nct, (R + 3) // 4, neb, offs))
+        self.scratch = torch.zeros(need, dtype=torch.float32, device=dev)
+        arr = (_lib.SnJob * len(self.layers))()
+        bt = bs = be = 0
+        base = self.scratch.data_ptr()
+        for j, d, (R, K, nt, ns, ne, offs) in zip(arr, self.layers, geo):
+            j.w, j.w_sn, j.g_sn, j.gw = d['w'].data_ptr(), d['w_sn'].data_ptr(), d['g_sn'].data_ptr(), d['gw'].data_ptr()
+            j.u, j.v, j.sigma = d['u'].data_ptr(), d['v'].data_ptr(), d['sigma'].data_ptr()
+            j.tpart, j.s, j.dpart = base + 4 * offs[0], base + 4 * offs[1], base + 4 * offs[2]
+            j.R, j.K, j.blk_t0, j.blk_s0, j.blk_e0 = R, K, bt, bs, be
+            bt, bs, be = bt + nt, bs + ns, be + ne
+        self.blocks = (bt, bs, be)
+        self.n = len(self.layers)
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+
+
+def sn_refresh(table, iterate):
+    """One power iteration (``iterate``) of every layer of ``table``, then sigma = u^T W v and W_sn = W / sigma: 4 launches,
+    2 without the iteration.  The caller reports the rewritten W_sn range (``bump_weight_epoch``)."""
+    bt, bs, be = table.blocks
+    check(_lib.lib().ganlab_sn_refresh(table.table.data_ptr(), table.n, bt, bs, be, 1 if iterate else 0, SN_EPS, _st()),
+          'sn_refresh')
+
+
+def sn_backward(table):
+    """gW += (g_sn - <g_sn, W_sn> u v^T) / sigma for every layer of ``table`` (2 launches)."""
+    check(_lib.lib().ganlab_sn_backward(table.table.data_ptr(), table.n, table.blocks[2], _st()), 'sn_backward')
+
+
 def lerp_rows(a, b, t):
     a, b, t = _c(a), _c(b), _c(t)
     out = torch.empty_like(a)
@@ -3532,6 +3594,46 @@ class _BceMean(Function):
         return gx, None
 
 
+class _HingeMean(Function):
+    """mean(max(a + b*x, 0)) -> 0-dim tensor (the hinge loss terms: backprop_utils.hinge_loss_disc)."""
+
+    @staticmethod
+    def forward(ctx, x, a, b):
+        x = _c(x)
+        out = _new((), x)
+        check(_lib.lib().ganlab_hinge_fwd_f32(_p(x), _p(out), x.numel(), a, b, _st()), 'hinge_fwd')
+        ctx.save_for_backward(x)
+        ctx.a, ctx.b = a, b
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, = ctx.saved_tensors
+        return _HingeBwd.apply(x, gout, ctx.a, ctx.b), None, None
+
+
+class _HingeBwd(Function):
+    """gx = gout * [a + b*x > 0] * b / n: piecewise constant in x (its derivative towards x is zero), linear in gout."""
+
+    @staticmethod
+    def forward(ctx, x, gout, a, b):
+        gx = torch.empty_like(x)
+        g1 = _c(gout).reshape(1)
+        check(_lib.lib().ganlab_hinge_bwd_f32(_p(x), _p(g1), _p(gx), x.numel(), a, b, _st()), 'hinge_bwd')
+        ctx.save_for_backward(x)
+        ctx.a, ctx.b = a, b
+        return gx
+
+    @staticmethod
+    def backward(ctx, gg):
+        x, = ctx.saved_tensors
+        ggout = None
+        if ctx.needs_input_grad[1]:
+            one = torch.ones(1, dtype=torch.float32, device=x.device)
+            ggout = sum_all(mul(_c(gg), _HingeBwd.apply(x, one, ctx.a, ctx.b)))
+        return torch.zeros_like(x), ggout, None, None
+
+
 class _ChNormPenalty(Function):
     """scale * sum_{n,hw} (||g[n,:,hw]||_2 - gamma)^2  (WGAN-GP, resnetgan/learner.py:817-823)."""
 
@@ -3755,6 +3857,11 @@ def sumsq_all(x, scale=1.0):
 
 def bce_logits_mean(x, target):
     return _BceMean.apply(x, float(target))
+
+
+def hinge_mean(x, a, b):
+    """mean(relu(a + b*x)) with its first derivative; the double backward towards ``x`` is zero."""
+    return _HingeMean.apply(x, float(a), float(b))
 
 
 def chnorm_penalty(g, gamma, scale):

@@ -92,10 +92,26 @@ class Generator64PixResnet(_ResnetGenerator):
         )
 
 
+def _init_spectral_norm(critic, spectral_norm):
+    """``spectral_norm=True``: every Conv2dEx / LinearEx of the critic gets its ``weight_u`` / ``weight_v`` buffers; the
+    normalised weights themselves come from a ``spectral_norm.SpectralNorm`` manager built over the critic's arena."""
+    critic.spectral_norm = bool(spectral_norm)
+    if critic.spectral_norm:
+        from ..spectral_norm import register_uv
+        register_uv(critic)
+
+
+def _check_spectral_norm(critic):
+    if critic.spectral_norm and critic.sn is None:
+        raise RuntimeError('this critic was built with spectral_norm=True: attach a spectral_norm.SpectralNorm manager '
+                           '(it owns the normalised weights) before calling it')
+
+
 class Discriminator32PixResnet(GAN):
     """32-pixel ResNet discriminator / critic (architectures.py:103-133)."""
 
-    def __init__(self, fmap=FMAP_D * 2, pooler=None, blur_type=None, nl=None, num_classes=0, equalized_lr=False):
+    def __init__(self, fmap=FMAP_D * 2, pooler=None, blur_type=None, nl=None, num_classes=0, equalized_lr=False,
+                 spectral_norm=False):
         super().__init__(32)
         from ..utils.custom_layers import AvgPool2x
         pooler = _own_resampler(pooler) if pooler is not None else AvgPool2x()
@@ -114,18 +130,21 @@ class Discriminator32PixResnet(GAN):
             Lambda(lambda x: x.view(-1, fmap)),
         )
         self.linear1 = LinearEx(nin_feat=fmap, nout_feat=1, init='Xavier', equalized_lr=equalized_lr)
+        _init_spectral_norm(self, spectral_norm)
 
     def features(self, x):
         return _run(self.resblocks, self.conv1(self.view1(x)))
 
     def forward(self, x):
+        _check_spectral_norm(self)
         return self.linear1(self.features(x)).view(-1)
 
 
 class Discriminator64PixResnet(GAN):
     """64-pixel ResNet discriminator / critic (architectures.py:157-187)."""
 
-    def __init__(self, fmap=FMAP_D, pooler=None, blur_type=None, nl=None, num_classes=0, equalized_lr=False):
+    def __init__(self, fmap=FMAP_D, pooler=None, blur_type=None, nl=None, num_classes=0, equalized_lr=False,
+                 spectral_norm=False):
         super().__init__(64)
         from ..utils.custom_layers import AvgPool2x
         pooler = _own_resampler(pooler) if pooler is not None else AvgPool2x()
@@ -145,11 +164,13 @@ class Discriminator64PixResnet(GAN):
         )
         self.linear1 = LinearEx(nin_feat=RES_FEATURE_SPACE ** 2 * 8 * fmap, nout_feat=1, init='Xavier',
                                 equalized_lr=equalized_lr)
+        _init_spectral_norm(self, spectral_norm)
 
     def features(self, x):
         return _run(self.resblocks, self.conv1(self.view1(x)))
 
     def forward(self, x):
+        _check_spectral_norm(self)
         return self.linear1(self.features(x)).view(-1)
 
 

@@ -10,6 +10,8 @@ Two roles, as in the reference:
 Every tensor op of the step runs in the hand-written kernels (gan_lab_amd.ops); parameters, gradients
 and Adam moments live in flat arenas (optim.py); with torch.distributed initialised the gradients are
 mean-all-reduced over RCCL (BatchNorm statistics stay per rank, like DDP without SyncBN).
+``config.spectral_norm`` (ResNet GAN only) normalises every critic weight by its largest singular value
+(spectral_norm.py) and ``loss='hinge'`` is its usual partner; both are off by default.
 Validation metrics, image grids and plotting (:249-461, :950-1046) are outside the hot path."""
 import os
 import warnings
@@ -97,6 +99,7 @@ class GANLearner(object):
 
         self.gen_model = None
         self.disc_model = None
+        self.sn = None          # spectral_norm.SpectralNorm of the ResNet GAN critic (config.spectral_norm)
         self._gradient_penalty = config.gradient_penalty
         self._optimizer = config.optimizer.casefold()
         self.opt_gen = self.opt_disc = None
@@ -140,8 +143,10 @@ class GANLearner(object):
         self.gen_model = gen_cls(len_latent=c.len_latent, fmap=fmap_g, upsampler=self.gen_model_upsampler,
                                  blur_type=c.blur_type, nl=self.nl, num_classes=self.num_classes_gen,
                                  equalized_lr=c.use_equalized_lr)
+        from .. import spectral_norm
+        sn_kw = {'spectral_norm': True} if spectral_norm.validate_config(config) else {}
         self.disc_model = disc_cls(fmap=fmap_d, pooler=self.disc_model_downsampler, blur_type=c.blur_type,
-                                   nl=self.nl, num_classes=self.num_classes_disc, equalized_lr=c.use_equalized_lr)
+                                   nl=self.nl, num_classes=self.num_classes_disc, equalized_lr=c.use_equalized_lr, **sn_kw)
         self.gen_model.to(c.dev)
         self.disc_model.to(c.dev)
         from .. import rng
@@ -167,6 +172,15 @@ class GANLearner(object):
         self.arena_d = ParamArena(self.disc_model.named_parameters(), self.config.dev)
         parallel.broadcast_params(self.arena_g.flat)
         parallel.broadcast_params(self.arena_d.flat)
+        if getattr(self.disc_model, 'spectral_norm', False):
+            # the critic's normalised weights, u / v / sigma and their job table (spectral_norm.py): built over the new arena;
+            # a new critic runs torch's 15 initial power iterations, a rebuild (checkpoint load) keeps the u, v it was given
+            from ..spectral_norm import INIT_ITERS, SpectralNorm
+            first = self.sn is None
+            self.sn = SpectralNorm(self.disc_model, self.arena_d, init_iters=INIT_ITERS if first else 0)
+            if parallel.is_dist():
+                parallel.broadcast_params(self.sn.uv)       # u, v travel with the parameters
+                self.sn.refresh(iterate=False)
 
     def _set_optimizer(self):
         """resnetgan/learner.py:884-908: Adam through configure_adam_for_gan; the others are not implemented
@@ -199,6 +213,8 @@ class GANLearner(object):
     def set_requires_grad_disc(self, flag):
         for p in self.disc_model.parameters():
             p.requires_grad_(flag)
+        if getattr(self, 'sn', None) is not None:
+            self.sn.requires_grad_(flag)
 
     @property
     def use_step_graph(self):
@@ -236,6 +252,8 @@ class GANLearner(object):
         of the generated batch (tests; drawn when None)."""
         c = self.config
         self.arena_g.zero_grad()
+        if self.sn is not None:
+            self.sn.refresh(iterate=False)      # the critic's weights moved: sigma and W_sn follow, u and v stay
         if zb is None:
             zb = gen_rand_latent_vars(num_samples=self.batch_size * c.gen_bs_mult, length=c.len_latent,
                                       distribution=self.latent_distribution, device=c.dev)
@@ -270,6 +288,8 @@ class GANLearner(object):
         the generated batch and [B, 2B) for the real one (tests; drawn when None)."""
         c = self.config
         self.arena_d.zero_grad()
+        if self.sn is not None:
+            self.sn.refresh(iterate=True)       # ONE power iteration per critic update (spectral_norm.py)
         if zb is None:
             zb = gen_rand_latent_vars(num_samples=self.batch_size, length=c.len_latent,
                                       distribution=self.latent_distribution, device=c.dev)
@@ -296,9 +316,15 @@ class GANLearner(object):
         self._ada_update(d_real)
         if self.gradient_penalty is not None:
             loss = loss + self.calc_gp(xgenb, xb, eps_interp=eps_interp)
-        self.reducer.arm(self.arena_d)
+        # With spectral normalisation the normalised layers' gradients reach the arena only in ``sn.backward()``, after the
+        # sweep: no bucket of the critic arena may leave from inside the backward, so the reducer is not armed and
+        # ``allreduce`` sends the whole arena afterwards.
+        if self.sn is None:
+            self.reducer.arm(self.arena_d)
         with ops.direct_param_grads(ops.direct_grads_enabled()):
             loss.backward()
+        if self.sn is not None:
+            self.sn.backward()
         self.reducer.allreduce(self.arena_d.gflat)
         self.opt_disc.step()
         return loss.detach()
@@ -372,9 +398,14 @@ class GANLearner(object):
                     print(f'\nTraining interrupted. Saved latest checkpoint into "{c.save_model_dir}/".\n')
             raise
 
-    def save_model(self, save_path, sync=True):
+    def save_model(self, save_path, sync=True, reference_format=False):
         """Checkpoint as plain data (key names follow resnetgan/learner.py:1076-1140).  ``sync=False``: no barrier
-        behind rank 0's write (the interrupt path)."""
+        behind rank 0's write (the interrupt path).  ``reference_format``: this learner writes plain-data checkpoints only;
+        with spectral normalisation on the request is refused as a ValueError (the reference cannot hold u, v)."""
+        from .. import spectral_norm
+        spectral_norm.check_save_format(bool(getattr(self.config, 'spectral_norm', False)), reference_format)
+        if reference_format:
+            raise NotImplementedError('the ResNet GAN learner writes plain-data checkpoints only')
         if self.not_trained_yet:
             raise Exception('Please train your model for atleast 1 iteration before saving.')
         from .. import checkpoint as ckpt
@@ -471,9 +502,10 @@ class GANLearner(object):
         self._set_loss()
 
     def _set_loss(self):
-        if self._loss not in ('wgan', 'nonsaturating', 'minimax',):
+        if self._loss not in ('wgan', 'nonsaturating', 'minimax',) and \
+                not (self._loss == 'hinge' and self._model == 'ResNet GAN'):
             raise ValueError("config does not support this loss.\nCurrently supported Loss Functions are: "
-                             "[ 'wgan', 'nonsaturating', 'minimax' ]")
+                             "[ 'wgan', 'nonsaturating', 'minimax' ] (ResNet GAN: also 'hinge')")
         # the BCE targets are constants folded into the loss kernels (no cached ones/zeros tensors,
         # cf. resnetgan/learner.py:937-938)
         self.loss_func_gen = lambda outb: bp.loss_gen(self._loss, outb)

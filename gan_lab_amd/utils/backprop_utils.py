@@ -32,6 +32,16 @@ def minimax_loss_disc(outb, yb):
     return ops.bce_logits_mean(outb, 0.0) + ops.bce_logits_mean(yb, 1.0)
 
 
+def hinge_loss_disc(outb, yb):
+    """mean(relu(1 - D(real))) + mean(relu(1 + D(fake)))  (Lim & Ye 2017; the SNGAN critic loss)."""
+    return ops.hinge_mean(yb, 1.0, -1.0) + ops.hinge_mean(outb, 1.0, 1.0)
+
+
+def hinge_loss_gen(outb):
+    """-mean(D(fake)): the generator's side of the hinge loss."""
+    return -ops.sum_all(outb, 1.0 / outb.numel())
+
+
 def loss_disc(kind, d_fake, d_real):
     """D adversarial loss as assembled in the train loop (progan/learner.py:791-800)."""
     kind = kind.casefold()
@@ -39,8 +49,10 @@ def loss_disc(kind, d_fake, d_real):
         return wasserstein_distance_disc(d_fake, d_real)
     if kind in ('nonsaturating', 'minimax'):
         return minimax_loss_disc(d_fake, d_real)
+    if kind == 'hinge':
+        return hinge_loss_disc(d_fake, d_real)
     raise ValueError("config does not support this loss.\nCurrently supported Loss Functions are: "
-                     "[ 'wgan', 'nonsaturating', 'minimax' ]")
+                     "[ 'wgan', 'nonsaturating', 'minimax', 'hinge' ]")
 
 
 def loss_gen(kind, d_fake):
@@ -52,8 +64,10 @@ def loss_gen(kind, d_fake):
         return nonsaturating_loss_gen(d_fake)
     if kind == 'minimax':
         return minimax_loss_gen(d_fake)
+    if kind == 'hinge':
+        return hinge_loss_gen(d_fake)
     raise ValueError("config does not support this loss.\nCurrently supported Loss Functions are: "
-                     "[ 'wgan', 'nonsaturating', 'minimax' ]")
+                     "[ 'wgan', 'nonsaturating', 'minimax', 'hinge' ]")
 
 
 def drift_loss(d_real, eps_drift):

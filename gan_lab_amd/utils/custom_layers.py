@@ -318,6 +318,8 @@ class Conv2dEx(nn.Module):
         self.bias = None
         if include_bias:
             self.conv2d.bias.data.fill_(0)
+        # the tensor to convolve with instead of ``conv2d.weight`` (spectral_norm.SpectralNorm: its slice of W / sigma)
+        self.weight_override = None
 
     @property
     def scale(self):
@@ -332,7 +334,8 @@ class Conv2dEx(nn.Module):
         if bias_mod is not None:
             assert bias is None
             bias, bias_scale = bias_mod.bias, (bias_mod.lrmul if bias_mod.use_lrmul else 1.0)
-        return ops.conv2d(x, self.conv2d.weight, bias, scale=self.scale, padding=self.padding, up=up,
+        weight = self.conv2d.weight if self.weight_override is None else self.weight_override
+        return ops.conv2d(x, weight, bias, scale=self.scale, padding=self.padding, up=up,
                           bias_scale=bias_scale, act=act, slope=slope, pool=pool, blur=blur,
                           defer_act_grad=defer_act_grad, in_act_slope=in_act_slope, in_blur_handoff=in_blur_handoff,
                           in_rgb_handoff=in_rgb_handoff)
@@ -379,6 +382,7 @@ class LinearEx(nn.Module):
         self.bias = None
         if include_bias:
             self.linear.bias.data.fill_(0)
+        self.weight_override = None      # as in Conv2dEx
 
     @property
     def scale(self):
@@ -386,7 +390,8 @@ class LinearEx(nn.Module):
         return s * (self.lrmul if self.use_lrmul else 1.0)
 
     def forward(self, x, act=None, slope=0.2):
-        return ops.linear(x, self.linear.weight, self.linear.bias, scale=self.scale,
+        weight = self.linear.weight if self.weight_override is None else self.weight_override
+        return ops.linear(x, weight, self.linear.bias, scale=self.scale,
                           bias_scale=self.lrmul if self.use_lrmul else 1.0, act=act, slope=slope)
 
 

@@ -454,6 +454,10 @@ size_t ganlab_sum_workspace(long long n);
 /* BCE-with-logits vs a constant target t, mean over n (progan/learner.py:793-800, :886-896) */
 int ganlab_bce_logits_fwd_f32(const float* x, float* out, int n, float target, void* stream);
 int ganlab_bce_logits_bwd_f32(const float* x, const float* gout, float* gx, int n, float target, void* stream);
+/* hinge term of a constant-target loss: out[0] = mean(max(a + b*x, 0)); bwd: gx = gout[0] * (a + b*x > 0 ? b : 0) / n
+ * (loss_D = hinge(1, -1)(D(real)) + hinge(1, +1)(D(fake)); piecewise linear: its second derivative is zero) */
+int ganlab_hinge_fwd_f32(const float* x, float* out, int n, float a, float b, void* stream);
+int ganlab_hinge_bwd_f32(const float* x, const float* gout, float* gx, int n, float a, float b, void* stream);
 /* WGAN-GP style penalty on channel-norms (resnetgan/learner.py:817-825):
  * out[0] = scale * sum_{n,hw} (sqrt(sum_c g^2) - gamma)^2 ;  bwd: gg = gout*scale*2*(s-gamma)*g/s */
 int ganlab_chnorm_penalty_fwd_f32(const float* g, float* out, int N, int C, long long HW, float gamma,
@@ -760,6 +764,39 @@ size_t ganlab_mod_torgb_cross_workspace(int N);
 /* out[n][68]: [ci 16][4] = sum_px x[n,ci]*gy[n,co], then [64 + co] = sum_px gy[n,co]   (Cin <= 16, Cout <= 4) */
 int ganlab_mod_torgb_cross_f32(const float* x, const float* gy, float* out, int N, int Cin, int Cout, long long HW,
                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- spectral normalisation of every weight of a critic, batched over the layers (csrc/spectral.hip) -------------------
+ * torch.nn.utils.spectral_norm with one power iteration, for a parameter W viewed as Wm = (R, K) row-major:
+ *   iterate:  t = Wm^T u ; v = t / max(|t|, eps) ; s = Wm v ; u = s / max(|s|, eps)
+ *   always:   sigma = u^T Wm v ; W_sn = W / sigma
+ *   backward: gW += (g_sn - <g_sn, W_sn> u v^T) / sigma            (u, v constants; accumulates)
+ * `jobs_device`: device copy of n_layers jobs.  Every pointer is 16-byte aligned; w, w_sn, g_sn, gw hold R*K floats, u R,
+ * v K, sigma 1; scratch: tpart ceil(R / GANLAB_SN_ROW_CHUNK) * K floats, s R, dpart ceil(R*K / GANLAB_SN_ELEM_BLOCK).
+ * Job i owns, in its three block spaces, blocks [blk_t0, +ceil(R / ROW_CHUNK) * ceil(K / COL_TILE)), [blk_s0, +ceil(R / 4))
+ * and [blk_e0, +ceil(R*K / ELEM_BLOCK)); jobs are sorted by each of them and blocks_t / blocks_s / blocks_e are the totals.
+ * Launches per call: 4 (iterate) or 2 for a refresh, 2 for the backward, whatever n_layers is.  Fixed-order sums, no
+ * atomics: bitwise reproducible.  Nothing is read back by the host (graph-capturable). */
+#define GANLAB_SN_ROW_CHUNK 16
+#define GANLAB_SN_COL_TILE 1024
+#define GANLAB_SN_ELEM_BLOCK 2048
+typedef struct ganlab_sn_job {
+  const float* w;        /* the parameter (R*K floats, OIHW or (out, in)) */
+  float* w_sn;           /* W / sigma: what the convolutions / linears read */
+  const float* g_sn;     /* d loss / d W_sn */
+  float* gw;             /* the parameter's gradient slot: accumulated into */
+  float* u;
+  float* v;
+  float* sigma;
+  float* tpart;
+  float* s;
+  float* dpart;
+  int R, K;
+  long long blk_t0, blk_s0, blk_e0;
+} ganlab_sn_job;
+int ganlab_sn_job_size(void);
+int ganlab_sn_refresh(const ganlab_sn_job* jobs_device, int n_layers, long long blocks_t, long long blocks_s,
+                      long long blocks_e, int iterate, float eps, void* stream);
+int ganlab_sn_backward(const ganlab_sn_job* jobs_device, int n_layers, long long blocks_e, void* stream);
 
 #ifdef __cplusplus
 }
