@@ -266,6 +266,16 @@ SIGNATURES = {
     'ganlab_sn_job_size': (_c_int, []),
     'ganlab_sn_refresh': (_c_int, [_c_p, _c_int, _c_ll, _c_ll, _c_ll, _c_int, _c_f, _c_p]),
     'ganlab_sn_backward': (_c_int, [_c_p, _c_int, _c_ll, _c_p]),
+    'ganlab_attn_supported': (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    'ganlab_attn_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    'ganlab_attn_bwd_workspace': (_c_sz, [_c_int, _c_int]),
+    'ganlab_attn_bwd_f32': (_c_int, [_c_p] * 9 + [_c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_sz, _c_p]),
+    'ganlab_maxpool2x2_bits_bytes': (_c_sz, [_c_ll, _c_int, _c_int]),
+    'ganlab_maxpool2x2_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_p]),
+    'ganlab_maxpool2x2_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_p]),
+    'ganlab_gated_residual_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_p]),
+    'ganlab_dot_workspace': (_c_sz, [_c_ll]),
+    'ganlab_dot_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_p, _c_sz, _c_p]),
     'ganlab_step_scalars_size': (_c_int, []),
     'ganlab_set_step_scalars': (_c_int, [_c_p, _c_u64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
 }

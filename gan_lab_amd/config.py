@@ -29,7 +29,12 @@ the image as it is (right for periodic textures, and the setting under which a c
 ``spectral_norm`` (ResNet GAN only; False = off): every Conv2dEx / LinearEx weight of the critic is divided by its largest
 singular value, estimated by one power iteration per critic update (spectral_norm.py; excludes ``use_equalized_lr``; validated
 when the learner is built), and ``loss='hinge'`` (ResNet GAN only) is the loss usually trained with it - with both on,
-``gradient_penalty=None`` is a sane setting.
+``gradient_penalty=None`` is a sane setting; ``self_attention`` (ResNet GAN only; None = off, ``'g'``, ``'d'`` or ``'gd'``;
+``--self_attention=none`` on the command line) adds a SAGAN self-attention block (attention.py: fused exact-fp32 kernels, the
+attention map is never stored) to the generator and / or the critic - on the 32x32 map of the 64-pixel networks, the 16x16 map
+of the 32-pixel ones.  The block is first order: ``'d'`` requires ``gradient_penalty=None`` (hinge loss + spectral normalisation
+is the recipe it belongs to), ``'g'`` works with every loss and penalty; on ProGAN / StyleGAN any value but None raises when the
+learner is built.
 """
 import argparse
 import os
@@ -50,6 +55,11 @@ _MODELS = {'resnetgan': 'ResNet GAN', 'resnet gan': 'ResNet GAN', 'progan': 'Pro
 def _float_or_none(v):
     """CLI type of an optional float: 'none' (any case) -> None."""
     return None if v is None or str(v).casefold() == 'none' else float(v)
+
+
+def _str_or_none(v):
+    """CLI type of an optional name: 'none' (any case) -> None, else casefolded."""
+    return None if v is None or str(v).casefold() == 'none' else str(v).casefold()
 
 
 def _spec(model_type):
@@ -76,6 +86,7 @@ def _spec(model_type):
         ('ada_kimg', float, 500.0),
         ('swd_nhoods', int, 128), ('swd_dir_repeats', int, 4), ('swd_dirs_per_repeat', int, 128), ('swd_seed', int, 0),
         ('msssim_range', float, 2.0), ('spectrum_window', str.casefold, 'hann'),
+        ('self_attention', _str_or_none, None),
     ]
     if model_type == 'ResNet GAN':
         rows += [('batch_size', int, BS), ('num_main_iters', int, 300000), ('num_disc_iters', int, 5),

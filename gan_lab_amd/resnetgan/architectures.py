@@ -1,6 +1,7 @@
 """ResNet GAN generators / discriminators on the HIP path (drop-in for
 gan_lab/resnetgan/architectures.py:29-224): same class names, constructor arguments, module tree and
-``state_dict`` keys; every tensor op runs in the hand-written kernels (gan_lab_amd.ops)."""
+``state_dict`` keys; every tensor op runs in the hand-written kernels (gan_lab_amd.ops).  ``self_attention=True`` (not in
+the reference; default off) adds a SAGAN block ``self_attn`` (attention.py) beside the unchanged module tree."""
 from torch import nn
 
 from .. import ops
@@ -16,10 +17,10 @@ FMAP_G_INIT_64_FCTR = 4
 RES_FEATURE_SPACE = 4
 
 
-def _run(seq, x):
-    """Children of a Sequential through the peephole executor, ResBlocks through their own forward."""
+def _run(seq, x, start=0, stop=None):
+    """Children [start, stop) of a Sequential through the peephole executor, ResBlocks through their own forward."""
     run = []
-    for m in seq:
+    for m in list(seq)[start:stop]:
         if isinstance(m, (ResBlock2d, FastResBlock2dDownsample)):
             if run:
                 x = fused_sequential(run, x)
@@ -30,16 +31,37 @@ def _run(seq, x):
     return fused_sequential(run, x) if run else x
 
 
+def _init_self_attention(net, self_attention, ni, equalized_lr):
+    """``self_attention=True``: the SAGAN block as the attribute ``self_attn`` - NOT a child of the Sequential, so the
+    module tree and ``state_dict`` keys without it are unchanged and only ``self_attn.*`` keys are added with it."""
+    if self_attention:
+        from ..attention import SelfAttention2d
+        net.self_attn = SelfAttention2d(ni, equalized_lr=equalized_lr)
+    else:
+        net.self_attn = None
+
+
+def _run_with_attention(net, seq, x, split):
+    """``_run`` over ``seq`` with the network's attention block between children ``split - 1`` and ``split``."""
+    if net.self_attn is None:
+        return _run(seq, x)
+    return _run(seq, net.self_attn(_run(seq, x, 0, split)), split)
+
+
 class _ResnetGenerator(GAN):
+    ATTN_AFTER = None       # index of the first child of generator_model behind the attention block
+
     def forward(self, x):
-        return _run(self.generator_model, x)
+        return _run_with_attention(self, self.generator_model, x, self.ATTN_AFTER)
 
 
 class Generator32PixResnet(_ResnetGenerator):
-    """32-pixel ResNet generator with optional class conditioning (architectures.py:29-59)."""
+    """32-pixel ResNet generator with optional class conditioning (architectures.py:29-59).  ``self_attention``: a SAGAN
+    block on the 16x16 map, after the second block."""
+    ATTN_AFTER = 5
 
     def __init__(self, len_latent=128, fmap=FMAP_G * 2, upsampler=None, blur_type=None, nl=None, num_classes=0,
-                 equalized_lr=False):
+                 equalized_lr=False, self_attention=False):
         super().__init__(32)
         from ..utils.custom_layers import Upsample2x
         upsampler = _own_resampler(upsampler) if upsampler is not None else Upsample2x()
@@ -61,13 +83,16 @@ class Generator32PixResnet(_ResnetGenerator):
             Conv2dEx(ni=fmap, nf=FMAP_SAMPLES, ks=3, stride=1, padding=1, init='Xavier', equalized_lr=equalized_lr),
             Tanh(),
         )
+        _init_self_attention(self, self_attention, fmap, equalized_lr)
 
 
 class Generator64PixResnet(_ResnetGenerator):
-    """64-pixel ResNet generator with optional class conditioning (architectures.py:62-97)."""
+    """64-pixel ResNet generator with optional class conditioning (architectures.py:62-97).  ``self_attention``: a SAGAN
+    block on the 32x32 map (2 * fmap channels), after the third block."""
+    ATTN_AFTER = 6
 
     def __init__(self, len_latent=128, fmap=FMAP_G, upsampler=None, blur_type=None, nl=None, num_classes=0,
-                 equalized_lr=False):
+                 equalized_lr=False, self_attention=False):
         super().__init__(64)
         from ..utils.custom_layers import Upsample2x
         upsampler = _own_resampler(upsampler) if upsampler is not None else Upsample2x()
@@ -90,6 +115,7 @@ class Generator64PixResnet(_ResnetGenerator):
             Conv2dEx(ni=1 * fmap, nf=FMAP_SAMPLES, ks=3, stride=1, padding=1, init='He', equalized_lr=equalized_lr),
             Tanh(),
         )
+        _init_self_attention(self, self_attention, 2 * fmap, equalized_lr)
 
 
 def _init_spectral_norm(critic, spectral_norm):
@@ -108,10 +134,11 @@ def _check_spectral_norm(critic):
 
 
 class Discriminator32PixResnet(GAN):
-    """32-pixel ResNet discriminator / critic (architectures.py:103-133)."""
+    """32-pixel ResNet discriminator / critic (architectures.py:103-133).  ``self_attention``: a SAGAN block on the 16x16
+    map, after ``conv1``."""
 
     def __init__(self, fmap=FMAP_D * 2, pooler=None, blur_type=None, nl=None, num_classes=0, equalized_lr=False,
-                 spectral_norm=False):
+                 spectral_norm=False, self_attention=False):
         super().__init__(32)
         from ..utils.custom_layers import AvgPool2x
         pooler = _own_resampler(pooler) if pooler is not None else AvgPool2x()
@@ -130,10 +157,11 @@ class Discriminator32PixResnet(GAN):
             Lambda(lambda x: x.view(-1, fmap)),
         )
         self.linear1 = LinearEx(nin_feat=fmap, nout_feat=1, init='Xavier', equalized_lr=equalized_lr)
-        _init_spectral_norm(self, spectral_norm)
+        _init_self_attention(self, self_attention, fmap, equalized_lr)
+        _init_spectral_norm(self, spectral_norm)      # after the block exists: its convolutions get u, v too
 
     def features(self, x):
-        return _run(self.resblocks, self.conv1(self.view1(x)))
+        return _run_with_attention(self, self.resblocks, self.conv1(self.view1(x)), 0)
 
     def forward(self, x):
         _check_spectral_norm(self)
@@ -141,10 +169,11 @@ class Discriminator32PixResnet(GAN):
 
 
 class Discriminator64PixResnet(GAN):
-    """64-pixel ResNet discriminator / critic (architectures.py:157-187)."""
+    """64-pixel ResNet discriminator / critic (architectures.py:157-187).  ``self_attention``: a SAGAN block on the 32x32
+    map (2 * fmap channels), after the first block."""
 
     def __init__(self, fmap=FMAP_D, pooler=None, blur_type=None, nl=None, num_classes=0, equalized_lr=False,
-                 spectral_norm=False):
+                 spectral_norm=False, self_attention=False):
         super().__init__(64)
         from ..utils.custom_layers import AvgPool2x
         pooler = _own_resampler(pooler) if pooler is not None else AvgPool2x()
@@ -164,10 +193,11 @@ class Discriminator64PixResnet(GAN):
         )
         self.linear1 = LinearEx(nin_feat=RES_FEATURE_SPACE ** 2 * 8 * fmap, nout_feat=1, init='Xavier',
                                 equalized_lr=equalized_lr)
-        _init_spectral_norm(self, spectral_norm)
+        _init_self_attention(self, self_attention, 2 * fmap, equalized_lr)
+        _init_spectral_norm(self, spectral_norm)      # after the block exists: its convolutions get u, v too
 
     def features(self, x):
-        return _run(self.resblocks, self.conv1(self.view1(x)))
+        return _run_with_attention(self, self.resblocks, self.conv1(self.view1(x)), 1)
 
     def forward(self, x):
         _check_spectral_norm(self)

@@ -11,7 +11,8 @@ Every tensor op of the step runs in the hand-written kernels (gan_lab_amd.ops); 
 and Adam moments live in flat arenas (optim.py); with torch.distributed initialised the gradients are
 mean-all-reduced over RCCL (BatchNorm statistics stay per rank, like DDP without SyncBN).
 ``config.spectral_norm`` (ResNet GAN only) normalises every critic weight by its largest singular value
-(spectral_norm.py) and ``loss='hinge'`` is its usual partner; both are off by default.
+(spectral_norm.py) and ``loss='hinge'`` is its usual partner; ``config.self_attention`` ('g', 'd', 'gd'; ResNet GAN only) adds
+SAGAN's self-attention block to the generator / critic (attention.py); all three are off by default.
 Validation metrics, image grids and plotting (:249-461, :950-1046) are outside the hot path."""
 import os
 import warnings
@@ -64,6 +65,10 @@ class GANLearner(object):
         # ... and the radial power-spectrum distance's ('spectrum' in config.gen_metrics; spectrum.py)
         from .. import spectrum
         spectrum.validate_config(config)
+        # self-attention (config.self_attention; attention.py): a ResNet GAN option, and first order only - a critic with a
+        # block excludes the gradient penalties
+        from .. import attention
+        self._attn_g, self._attn_d = attention.validate_config(config)
 
         self.curr_dataset_batch_num = 0
         self.curr_epoch_num = 1
@@ -142,9 +147,11 @@ class GANLearner(object):
         fmap_d = getattr(config, 'fmap_d', fmap_d)
         self.gen_model = gen_cls(len_latent=c.len_latent, fmap=fmap_g, upsampler=self.gen_model_upsampler,
                                  blur_type=c.blur_type, nl=self.nl, num_classes=self.num_classes_gen,
-                                 equalized_lr=c.use_equalized_lr)
+                                 equalized_lr=c.use_equalized_lr, **({'self_attention': True} if self._attn_g else {}))
         from .. import spectral_norm
         sn_kw = {'spectral_norm': True} if spectral_norm.validate_config(config) else {}
+        if self._attn_d:
+            sn_kw['self_attention'] = True
         self.disc_model = disc_cls(fmap=fmap_d, pooler=self.disc_model_downsampler, blur_type=c.blur_type,
                                    nl=self.nl, num_classes=self.num_classes_disc, equalized_lr=c.use_equalized_lr, **sn_kw)
         self.gen_model.to(c.dev)
@@ -401,9 +408,12 @@ class GANLearner(object):
     def save_model(self, save_path, sync=True, reference_format=False):
         """Checkpoint as plain data (key names follow resnetgan/learner.py:1076-1140).  ``sync=False``: no barrier
         behind rank 0's write (the interrupt path).  ``reference_format``: this learner writes plain-data checkpoints only;
-        with spectral normalisation on the request is refused as a ValueError (the reference cannot hold u, v)."""
+        with spectral normalisation or self-attention on the request is refused as a ValueError (the reference cannot hold
+        u, v or the block)."""
         from .. import spectral_norm
         spectral_norm.check_save_format(bool(getattr(self.config, 'spectral_norm', False)), reference_format)
+        from .. import attention
+        attention.check_save_format(getattr(self.config, 'self_attention', None), reference_format)
         if reference_format:
             raise NotImplementedError('the ResNet GAN learner writes plain-data checkpoints only')
         if self.not_trained_yet:
@@ -413,7 +423,8 @@ class GANLearner(object):
         sched_steps = max(self.scheduler_gen._step_count - 1, 0) if (self.sched_bool and self.scheduler_gen) else 0
         ck = {
             'config': ckpt.saved_config_fields({k: v for k, v in vars(self.config).items() if not k.startswith('_') and
-                                                isinstance(v, (int, float, str, bool, dict, list, tuple, type(None)))}),
+                                                isinstance(v, (int, float, str, bool, dict, list, tuple, type(None))) and
+                                                not (k == 'self_attention' and v is None)}),
             'gen_model_state_dict': {k: v.detach().cpu() for k, v in self.gen_model.state_dict().items()},
             'disc_model_state_dict': {k: v.detach().cpu() for k, v in self.disc_model.state_dict().items()},
             'opt_gen_state_dict': self.opt_gen.export_moments(self.gen_model.named_parameters()),
@@ -490,6 +501,9 @@ class GANLearner(object):
 
     @gradient_penalty.setter
     def gradient_penalty(self, new_gradient_penalty):
+        if new_gradient_penalty is not None and getattr(self, '_attn_d', False):
+            raise ValueError('the critic has a self-attention block (config.self_attention): the double backward of a gradient '
+                             'penalty through attention is not provided; keep gradient_penalty=None (hinge + spectral norm)')
         self._gradient_penalty = new_gradient_penalty.casefold() if new_gradient_penalty is not None else None
 
     @property

@@ -798,6 +798,36 @@ int ganlab_sn_refresh(const ganlab_sn_job* jobs_device, int n_layers, long long 
                       long long blocks_e, int iterate, float eps, void* stream);
 int ganlab_sn_backward(const ganlab_sn_job* jobs_device, int n_layers, long long blocks_e, void* stream);
 
+/* ---- SAGAN self-attention (Zhang et al. 2019; csrc/attention.hip) ----------------------------------------------
+ * Channel-major operands as the 1x1 convolutions leave them: q (N, Dk, L), k (N, Dk, S), v (N, Dv, S); no 1/sqrt(d) scale.
+ *   P[n,l,:] = softmax_s(sum_d q[n,d,l] k[n,d,s]) ; o[n,c,l] = sum_s v[n,c,s] P[n,l,s] ; lse[n,l] = logsumexp_s
+ * fwd: one flash-style kernel on the exact-fp32 MFMA (online max / sum over key tiles) writes o (N, Dv, L) and lse (N, L);
+ * nothing of size L x S is written.  bwd (first order): from q, k, v, o, lse, d_o it recomputes P per tile and writes dq, dk, dv
+ * in three launches (D = rowsum(d_o * o) into the workspace; dq parallel over query tiles; dk, dv parallel over key tiles).
+ * No atomics, fixed summation order: bitwise reproducible.  Stream-ordered, nothing is read back by the host.
+ * Supported (ganlab_attn_supported): Dk % 4 == 0 in [4, 64], Dv % 16 == 0 in [16, 256], any N, L, S >= 1 (tails masked);
+ * anything else returns GANLAB_EUNSUPPORTED. */
+int ganlab_attn_supported(int N, int Dk, int Dv, int L, int S);
+int ganlab_attn_fwd_f32(const float* q, const float* k, const float* v, float* o, float* lse, int N, int Dk, int Dv, int L,
+                        int S, void* stream);
+size_t ganlab_attn_bwd_workspace(int N, int L);
+int ganlab_attn_bwd_f32(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* d_o,
+                        float* dq, float* dk, float* dv, int N, int Dk, int Dv, int L, int S, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* 2x2 max pool of `planes` (H, W) planes, H and W even (else GANLAB_EINVAL): y (planes, H/2, W/2) and a 2-bit argmax per output
+ * (2 * dy + dx; on a tie the first of the four in row-major order, as in ATen), four outputs of the flat index per byte:
+ * ganlab_maxpool2x2_bits_bytes bytes.  bwd is a gather: every input element reads its output's code. */
+size_t ganlab_maxpool2x2_bits_bytes(long long planes, int H, int W);
+int ganlab_maxpool2x2_f32(const float* x, float* y, void* bits, long long planes, int H, int W, void* stream);
+int ganlab_maxpool2x2_bwd_f32(const float* gy, const void* bits, float* gx, long long planes, int H, int W, void* stream);
+/* out = x + gamma[0] * y, gamma a one-element device tensor (its backward: dx = g, dy = ganlab_scale_dev_f32, dgamma =
+ * ganlab_dot_f32(g, y)) */
+int ganlab_gated_residual_f32(const float* x, const float* y, const float* gamma, float* out, long long n, void* stream);
+/* out[0] = sum_i a[i] b[i]: fp64 products and partials, block partials added in index order */
+size_t ganlab_dot_workspace(long long n);
+int ganlab_dot_f32(const float* a, const float* b, float* out, long long n, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
