@@ -276,6 +276,13 @@ SIGNATURES = {
     'ganlab_gated_residual_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_p]),
     'ganlab_dot_workspace': (_c_sz, [_c_ll]),
     'ganlab_dot_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_p, _c_sz, _c_p]),
+    'ganlab_cbn_apply_f32': (_c_int, [_c_p] * 7 + [_c_int, _c_int, _c_ll, _c_int, _c_int, _c_f, _c_p]),
+    'ganlab_cbn_bwd_workspace': (_c_sz, [_c_int, _c_int]),
+    'ganlab_cbn_bwd_f32': (_c_int, [_c_p] * 12 + [_c_int, _c_int, _c_ll, _c_int, _c_int, _c_f, _c_p, _c_sz, _c_p]),
+    'ganlab_proj_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_p]),
+    'ganlab_proj_dfeat_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_p]),
+    'ganlab_proj_dweight_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_p]),
+    'ganlab_randint_i32': (_c_int, [_c_p, _c_ll, _c_int, _c_u64, _c_u64, _c_p]),
     'ganlab_step_scalars_size': (_c_int, []),
     'ganlab_set_step_scalars': (_c_int, [_c_p, _c_u64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
 }

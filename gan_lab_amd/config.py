@@ -34,7 +34,14 @@ when the learner is built), and ``loss='hinge'`` (ResNet GAN only) is the loss u
 attention map is never stored) to the generator and / or the critic - on the 32x32 map of the 64-pixel networks, the 16x16 map
 of the 32-pixel ones.  The block is first order: ``'d'`` requires ``gradient_penalty=None`` (hinge loss + spectral normalisation
 is the recipe it belongs to), ``'g'`` works with every loss and penalty; on ProGAN / StyleGAN any value but None raises when the
-learner is built.
+learner is built; ``cgan`` (ResNet GAN only; None = off, ``'projection'`` the only other value; ``--cgan=none`` on the command
+line) with ``num_classes`` >= 2 makes the pair class-conditional the SNGAN-projection / SAGAN / BigGAN way (conditional.py):
+class-conditional BatchNorm in the generator, a projection critic, on HIP kernels of their own; the inputs keep their widths and
+the learner's steps take the batch's labels (``DeviceImageLoader(labels=...)`` or any loader that yields ``(x, label)``).  It is
+independent of ``class_condition`` / ``use_auxiliary_classifier`` (the reference's own conditioning, which never ran and keeps
+raising), works with every loss, penalty and augmentation and with ``spectral_norm`` / ``self_attention``; any other value, a
+progressive model or ``num_classes`` < 2 raises when the learner is built.  ``--gradient_penalty=none`` on the command line
+means no penalty (None), as ``make_config(gradient_penalty=None)`` does.
 """
 import argparse
 import os
@@ -68,7 +75,7 @@ def _spec(model_type):
     rows = [
         ('dev', str.casefold, dev), ('n_gpu', int, 1), ('enable_cudnn_autotuner', bool, False),
         ('random_seed', int, -1), ('gen_bs_mult', int, 1), ('num_gen_iters', int, 1),
-        ('loss', str.casefold, 'wgan'), ('gradient_penalty', str.casefold, 'wgan-gp'), ('lda', float, 10.),
+        ('loss', str.casefold, 'wgan'), ('gradient_penalty', _str_or_none, 'wgan-gp'), ('lda', float, 10.),
         ('gamma', float, 1.), ('lr_sched_custom', str.casefold, None), ('optimizer', str.casefold, 'adam'),
         ('beta1', float, 0.), ('eps', float, 1.e-8), ('wd', float, 0.), ('align_corners', bool, False),
         ('model_upsample_type', str.casefold, 'nearest'), ('model_downsample_type', str.casefold, 'average'),
@@ -86,7 +93,7 @@ def _spec(model_type):
         ('ada_kimg', float, 500.0),
         ('swd_nhoods', int, 128), ('swd_dir_repeats', int, 4), ('swd_dirs_per_repeat', int, 128), ('swd_seed', int, 0),
         ('msssim_range', float, 2.0), ('spectrum_window', str.casefold, 'hann'),
-        ('self_attention', _str_or_none, None),
+        ('self_attention', _str_or_none, None), ('cgan', _str_or_none, None),
     ]
     if model_type == 'ResNet GAN':
         rows += [('batch_size', int, BS), ('num_main_iters', int, 300000), ('num_disc_iters', int, 5),

@@ -1,7 +1,11 @@
 """ResNet GAN generators / discriminators on the HIP path (drop-in for
 gan_lab/resnetgan/architectures.py:29-224): same class names, constructor arguments, module tree and
 ``state_dict`` keys; every tensor op runs in the hand-written kernels (gan_lab_amd.ops).  ``self_attention=True`` (not in
-the reference; default off) adds a SAGAN block ``self_attn`` (attention.py) beside the unchanged module tree."""
+the reference; default off) adds a SAGAN block ``self_attn`` (attention.py) beside the unchanged module tree; ``cgan=True``
+(not in the reference either; default off) with ``num_classes`` = K makes the networks class-conditional (conditional.py): every
+generator BatchNorm carries (K, C) tables and the generator is called as ``g(z, labels)``, the critic gains the projection layer
+``proj`` and is called as ``d(x, labels)``.  With ``cgan`` the reference's meaning of ``num_classes`` (a one-hot concatenated to
+the input) does not apply: the inputs keep their widths."""
 from torch import nn
 
 from .. import ops
@@ -48,11 +52,39 @@ def _run_with_attention(net, seq, x, split):
     return _run(seq, net.self_attn(_run(seq, x, 0, split)), split)
 
 
+def _need_labels(net, labels):
+    if labels is None:
+        raise TypeError(f'{type(net).__name__} was built with cgan=True: call it as net(input, labels) with one class label '
+                        f'per sample')
+    return labels
+
+
 class _ResnetGenerator(GAN):
     ATTN_AFTER = None       # index of the first child of generator_model behind the attention block
+    cgan = False
 
-    def forward(self, x):
-        return _run_with_attention(self, self.generator_model, x, self.ATTN_AFTER)
+    def _init_cgan(self, cgan, num_classes):
+        """``cgan=True``: the conditional norms were built by the blocks / NormalizeLayer; remember them for label routing."""
+        from ..utils.custom_layers import ConditionalBatchNorm2d
+        self.cgan = bool(cgan)
+        self._cond_norms = [m for m in self.modules() if isinstance(m, ConditionalBatchNorm2d)] if self.cgan else []
+        assert not self.cgan or len(self._cond_norms) == sum(isinstance(m, NormalizeLayer) for m in self.modules())
+
+    def forward(self, x, labels=None):
+        if not self.cgan:
+            if labels is not None:
+                raise TypeError(f'{type(self).__name__} is not class-conditional (cgan=False) and takes no labels')
+            return _run_with_attention(self, self.generator_model, x, self.ATTN_AFTER)
+        # the batch's labels reach the conditional norms as an attribute for the length of this forward: the Sequential, the
+        # peephole executor and the blocks stay label-free (the backward has its own copy, saved by the op)
+        _need_labels(self, labels)
+        for m in self._cond_norms:
+            m.labels = labels
+        try:
+            return _run_with_attention(self, self.generator_model, x, self.ATTN_AFTER)
+        finally:
+            for m in self._cond_norms:
+                m.labels = None
 
 
 class Generator32PixResnet(_ResnetGenerator):
@@ -61,15 +93,16 @@ class Generator32PixResnet(_ResnetGenerator):
     ATTN_AFTER = 5
 
     def __init__(self, len_latent=128, fmap=FMAP_G * 2, upsampler=None, blur_type=None, nl=None, num_classes=0,
-                 equalized_lr=False, self_attention=False):
+                 equalized_lr=False, self_attention=False, cgan=False):
         super().__init__(32)
+        cond_classes, num_classes = _cgan_classes(cgan, num_classes)
         from ..utils.custom_layers import Upsample2x
         upsampler = _own_resampler(upsampler) if upsampler is not None else Upsample2x()
         nl = _own_nl(nl)
         self.len_latent, self.num_classes, self.equalized_lr = len_latent, num_classes, equalized_lr
         f0 = len_latent * FMAP_G_INIT_32_FCTR
         kw = dict(ks=3, norm_type='BatchNorm', upsampler=upsampler, init='He', nl=nl, equalized_lr=equalized_lr,
-                  blur_type=blur_type)
+                  blur_type=blur_type, **({'num_classes': cond_classes} if cgan else {}))
         self.generator_model = nn.Sequential(
             Lambda(lambda x: x.view(-1, len_latent + num_classes)),
             LinearEx(nin_feat=len_latent + num_classes, nout_feat=f0 * RES_INIT ** 2, init='Xavier',
@@ -78,12 +111,13 @@ class Generator32PixResnet(_ResnetGenerator):
             ResBlock2d32Pix(ni=f0, nf=fmap, **kw),
             ResBlock2d32Pix(ni=fmap, nf=fmap, **kw),
             ResBlock2d32Pix(ni=fmap, nf=fmap, **kw),
-            NormalizeLayer('BatchNorm', ni=fmap),
+            NormalizeLayer('BatchNorm', ni=fmap, num_classes=cond_classes),
             nl,
             Conv2dEx(ni=fmap, nf=FMAP_SAMPLES, ks=3, stride=1, padding=1, init='Xavier', equalized_lr=equalized_lr),
             Tanh(),
         )
         _init_self_attention(self, self_attention, fmap, equalized_lr)
+        self._init_cgan(cgan, cond_classes)
 
 
 class Generator64PixResnet(_ResnetGenerator):
@@ -92,15 +126,16 @@ class Generator64PixResnet(_ResnetGenerator):
     ATTN_AFTER = 6
 
     def __init__(self, len_latent=128, fmap=FMAP_G, upsampler=None, blur_type=None, nl=None, num_classes=0,
-                 equalized_lr=False, self_attention=False):
+                 equalized_lr=False, self_attention=False, cgan=False):
         super().__init__(64)
+        cond_classes, num_classes = _cgan_classes(cgan, num_classes)
         from ..utils.custom_layers import Upsample2x
         upsampler = _own_resampler(upsampler) if upsampler is not None else Upsample2x()
         nl = _own_nl(nl)
         self.len_latent, self.num_classes, self.equalized_lr = len_latent, num_classes, equalized_lr
         f0 = len_latent * FMAP_G_INIT_64_FCTR
         kw = dict(ks=3, norm_type='BatchNorm', upsampler=upsampler, init='He', nl=nl, equalized_lr=equalized_lr,
-                  blur_type=blur_type)
+                  blur_type=blur_type, **({'num_classes': cond_classes} if cgan else {}))
         self.generator_model = nn.Sequential(
             Lambda(lambda x: x.view(-1, len_latent + num_classes)),
             LinearEx(nin_feat=len_latent + num_classes, nout_feat=f0 * RES_INIT ** 2, init='Xavier',
@@ -110,12 +145,47 @@ class Generator64PixResnet(_ResnetGenerator):
             ResBlock2d(ni=8 * fmap, nf=4 * fmap, **kw),
             ResBlock2d(ni=4 * fmap, nf=2 * fmap, **kw),
             ResBlock2d(ni=2 * fmap, nf=1 * fmap, **kw),
-            NormalizeLayer('BatchNorm', ni=1 * fmap),
+            NormalizeLayer('BatchNorm', ni=1 * fmap, num_classes=cond_classes),
             nl,
             Conv2dEx(ni=1 * fmap, nf=FMAP_SAMPLES, ks=3, stride=1, padding=1, init='He', equalized_lr=equalized_lr),
             Tanh(),
         )
         _init_self_attention(self, self_attention, 2 * fmap, equalized_lr)
+        self._init_cgan(cgan, cond_classes)
+
+
+def _cgan_classes(cgan, num_classes):
+    """-> (classes of the conditional layers, one-hot width concatenated to the input).  ``cgan=True``: ``num_classes`` counts
+    the classes of the tables / the projection and nothing is concatenated."""
+    if not cgan:
+        return 0, num_classes
+    if not isinstance(num_classes, int) or num_classes < 2:
+        raise ValueError(f'cgan=True needs num_classes >= 2 (got {num_classes!r})')
+    return num_classes, 0
+
+
+def _init_projection(critic, cgan, num_classes, nin_feat, equalized_lr):
+    """``cgan=True``: the class embedding ``proj`` of the projection critic - a bias-free LinearEx beside ``linear1``, reading the
+    same feature; built before ``_init_spectral_norm`` so that it gets its u, v like every other layer."""
+    critic.proj = LinearEx(nin_feat=nin_feat, nout_feat=num_classes, include_bias=False, init='Xavier',
+                           equalized_lr=equalized_lr) if cgan else None
+
+
+def _critic_forward(critic, x, labels):
+    _check_spectral_norm(critic)
+    if critic.proj is None and labels is not None:
+        raise TypeError(f'{type(critic).__name__} is not class-conditional (cgan=False) and takes no labels')
+    if critic.proj is not None:
+        _need_labels(critic, labels)
+    f = critic.features(x)
+    base = critic.linear1(f).view(-1)
+    if critic.proj is None:
+        return base
+    proj = critic.proj
+    weight = proj.linear.weight if proj.weight_override is None else proj.weight_override
+    if proj.scale != 1.0:
+        weight = ops.scale(weight, proj.scale)
+    return ops.class_projection(f, weight, labels, base)
 
 
 def _init_spectral_norm(critic, spectral_norm):
@@ -138,8 +208,9 @@ class Discriminator32PixResnet(GAN):
     map, after ``conv1``."""
 
     def __init__(self, fmap=FMAP_D * 2, pooler=None, blur_type=None, nl=None, num_classes=0, equalized_lr=False,
-                 spectral_norm=False, self_attention=False):
+                 spectral_norm=False, self_attention=False, cgan=False):
         super().__init__(32)
+        cond_classes, num_classes = _cgan_classes(cgan, num_classes)
         from ..utils.custom_layers import AvgPool2x
         pooler = _own_resampler(pooler) if pooler is not None else AvgPool2x()
         nl = _own_nl(nl)
@@ -158,14 +229,14 @@ class Discriminator32PixResnet(GAN):
         )
         self.linear1 = LinearEx(nin_feat=fmap, nout_feat=1, init='Xavier', equalized_lr=equalized_lr)
         _init_self_attention(self, self_attention, fmap, equalized_lr)
+        _init_projection(self, cgan, cond_classes, fmap, equalized_lr)
         _init_spectral_norm(self, spectral_norm)      # after the block exists: its convolutions get u, v too
 
     def features(self, x):
         return _run_with_attention(self, self.resblocks, self.conv1(self.view1(x)), 0)
 
-    def forward(self, x):
-        _check_spectral_norm(self)
-        return self.linear1(self.features(x)).view(-1)
+    def forward(self, x, labels=None):
+        return _critic_forward(self, x, labels)
 
 
 class Discriminator64PixResnet(GAN):
@@ -173,8 +244,9 @@ class Discriminator64PixResnet(GAN):
     map (2 * fmap channels), after the first block."""
 
     def __init__(self, fmap=FMAP_D, pooler=None, blur_type=None, nl=None, num_classes=0, equalized_lr=False,
-                 spectral_norm=False, self_attention=False):
+                 spectral_norm=False, self_attention=False, cgan=False):
         super().__init__(64)
+        cond_classes, num_classes = _cgan_classes(cgan, num_classes)
         from ..utils.custom_layers import AvgPool2x
         pooler = _own_resampler(pooler) if pooler is not None else AvgPool2x()
         nl = _own_nl(nl)
@@ -194,14 +266,14 @@ class Discriminator64PixResnet(GAN):
         self.linear1 = LinearEx(nin_feat=RES_FEATURE_SPACE ** 2 * 8 * fmap, nout_feat=1, init='Xavier',
                                 equalized_lr=equalized_lr)
         _init_self_attention(self, self_attention, 2 * fmap, equalized_lr)
+        _init_projection(self, cgan, cond_classes, RES_FEATURE_SPACE ** 2 * 8 * fmap, equalized_lr)
         _init_spectral_norm(self, spectral_norm)      # after the block exists: its convolutions get u, v too
 
     def features(self, x):
         return _run_with_attention(self, self.resblocks, self.conv1(self.view1(x)), 1)
 
-    def forward(self, x):
-        _check_spectral_norm(self)
-        return self.linear1(self.features(x)).view(-1)
+    def forward(self, x, labels=None):
+        return _critic_forward(self, x, labels)
 
 
 class DiscriminatorAC32PixResnet(Discriminator32PixResnet):

@@ -12,7 +12,9 @@ and Adam moments live in flat arenas (optim.py); with torch.distributed initiali
 mean-all-reduced over RCCL (BatchNorm statistics stay per rank, like DDP without SyncBN).
 ``config.spectral_norm`` (ResNet GAN only) normalises every critic weight by its largest singular value
 (spectral_norm.py) and ``loss='hinge'`` is its usual partner; ``config.self_attention`` ('g', 'd', 'gd'; ResNet GAN only) adds
-SAGAN's self-attention block to the generator / critic (attention.py); all three are off by default.
+SAGAN's self-attention block to the generator / critic (attention.py); ``config.cgan='projection'`` (ResNet GAN only, with
+``config.num_classes`` >= 2) makes the pair class-conditional - conditional BatchNorm in the generator, a projection critic
+(conditional.py) - and ``g_step`` / ``d_step`` then take the batch's labels; all four are off by default.
 Validation metrics, image grids and plotting (:249-461, :950-1046) are outside the hot path."""
 import os
 import warnings
@@ -82,6 +84,9 @@ class GANLearner(object):
             # so there is no behaviour to be in parity with.
             raise NotImplementedError('class_condition / use_auxiliary_classifier: no variant of these options runs in '
                                       'the reference (tests/golden/conditional_probe.json); not provided')
+        # class conditioning of our own (config.cgan; conditional.py): conditional BatchNorm + projection critic, ResNet GAN only
+        from .. import conditional
+        self.cgan = conditional.validate_config(config)
         if not (config.res_samples <= config.res_dataset):
             raise ValueError(f'Resolution of generated images (config.res_samples = {config.res_samples}) must be '
                              f'less than\nor equal to resolution of dataset (config.res_dataset = '
@@ -145,15 +150,17 @@ class GANLearner(object):
                              'ProGAN or StyleGAN models featured in this package instead.')
         fmap_g = getattr(config, 'fmap_g', fmap_g)      # width override (tests / small runs)
         fmap_d = getattr(config, 'fmap_d', fmap_d)
+        cgan_kw = {'cgan': True, 'num_classes': c.num_classes} if self.cgan else {'num_classes': 0}
         self.gen_model = gen_cls(len_latent=c.len_latent, fmap=fmap_g, upsampler=self.gen_model_upsampler,
-                                 blur_type=c.blur_type, nl=self.nl, num_classes=self.num_classes_gen,
-                                 equalized_lr=c.use_equalized_lr, **({'self_attention': True} if self._attn_g else {}))
+                                 blur_type=c.blur_type, nl=self.nl,
+                                 equalized_lr=c.use_equalized_lr, **({'self_attention': True} if self._attn_g else {}),
+                                 **cgan_kw)
         from .. import spectral_norm
         sn_kw = {'spectral_norm': True} if spectral_norm.validate_config(config) else {}
         if self._attn_d:
             sn_kw['self_attention'] = True
         self.disc_model = disc_cls(fmap=fmap_d, pooler=self.disc_model_downsampler, blur_type=c.blur_type,
-                                   nl=self.nl, num_classes=self.num_classes_disc, equalized_lr=c.use_equalized_lr, **sn_kw)
+                                   nl=self.nl, equalized_lr=c.use_equalized_lr, **sn_kw, **cgan_kw)
         self.gen_model.to(c.dev)
         self.disc_model.to(c.dev)
         from .. import rng
@@ -254,9 +261,38 @@ class GANLearner(object):
         if self.ada is not None and ck.get('ada_state') is not None:
             self.ada.load_state_dict(ck['ada_state'])
 
-    def g_step(self, zb=None, aug_params=None):
+    def _device_labels(self, labels, n, draw):
+        """The labels of a step as ops take them (``config.cgan``; None without it): an (n,) int32 device tensor.  A CPU tensor
+        (what the loaders yield) is range-checked on the host and uploaded; a device tensor is taken as it is - the kernels clamp,
+        nothing is read back.  None: ``draw`` them uniformly from the project's Philox stream (the generator step), else raise."""
+        if not self.cgan:
+            if labels is not None:
+                raise ValueError("labels were passed but config.cgan is None: this learner is not class-conditional")
+            return None
+        k = self.config.num_classes
+        if labels is None:
+            if not draw:
+                raise ValueError("config.cgan='projection': d_step needs the labels of the real batch (labels=...)")
+            from .. import rng
+            return rng.randint(n, k, self.config.dev)
+        if isinstance(labels, torch.Tensor) and labels.is_cuda:
+            if tuple(labels.shape) != (n,) or labels.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f'labels must be an int32 / int64 tensor of shape ({n},) (got {labels.dtype}, '
+                                 f'{tuple(labels.shape)})')
+            return labels.to(torch.int32)
+        from .. import conditional
+        return conditional.check_host_labels(labels, k, n).to(self.config.dev, non_blocking=True)
+
+    def _gen(self, zb, labels):
+        return self.gen_model(zb, labels) if self.cgan else self.gen_model(zb)
+
+    def _disc(self, x, labels):
+        return self.disc_model(x, labels) if self.cgan else self.disc_model(x)
+
+    def g_step(self, zb=None, aug_params=None, labels=None):
         """resnetgan/learner.py:545-597 (critic parameters frozen by the caller).  ``aug_params``: the DiffAugment rows
-        of the generated batch (tests; drawn when None)."""
+        of the generated batch (tests; drawn when None).  ``labels`` (``config.cgan``): the classes to generate, drawn
+        uniformly on the device when None."""
         c = self.config
         self.arena_g.zero_grad()
         if self.sn is not None:
@@ -264,10 +300,11 @@ class GANLearner(object):
         if zb is None:
             zb = gen_rand_latent_vars(num_samples=self.batch_size * c.gen_bs_mult, length=c.len_latent,
                                       distribution=self.latent_distribution, device=c.dev)
-        fake = self.gen_model(zb)
+        labels = self._device_labels(labels, zb.shape[0], draw=True)
+        fake = self._gen(zb, labels)
         if self.critic_aug is not None:
             fake = self._augment(fake, aug_params)
-        out = self.disc_model(fake)
+        out = self._disc(fake, labels)
         # :573-578 - the minimax generator loss here is -BCE(D(G(z)), 0), like backprop_utils
         loss = self.loss_func_gen(out)
         self.reducer.arm(self.arena_g)
@@ -289,19 +326,24 @@ class GANLearner(object):
             self._pairable = (id(self.disc_model), ok)
         return ok
 
-    def d_step(self, xb, zb=None, eps_interp=None, aug_params=None):
+    def d_step(self, xb, zb=None, eps_interp=None, aug_params=None, labels=None):
         """resnetgan/learner.py:606-672: generator frozen but in train mode (its BatchNorm running
         statistics keep moving, :621-622); no drift term on this path.  ``aug_params``: the DiffAugment rows, [0, B) for
-        the generated batch and [B, 2B) for the real one (tests; drawn when None)."""
+        the generated batch and [B, 2B) for the real one (tests; drawn when None).  ``labels`` (``config.cgan``; required
+        then): the real batch's classes; the generated batch is produced with the SAME labels, so that row i of a WGAN-GP
+        interpolate lies between two images of one class."""
         c = self.config
+        labels = self._device_labels(labels, xb.shape[0], draw=False)
         self.arena_d.zero_grad()
         if self.sn is not None:
             self.sn.refresh(iterate=True)       # ONE power iteration per critic update (spectral_norm.py)
         if zb is None:
             zb = gen_rand_latent_vars(num_samples=self.batch_size, length=c.len_latent,
                                       distribution=self.latent_distribution, device=c.dev)
+        if labels is not None and zb.shape[0] != labels.shape[0]:
+            raise ValueError(f'd_step: {zb.shape[0]} latents for {labels.shape[0]} labelled real images')
         with torch.no_grad():
-            xgenb = self.gen_model(zb)
+            xgenb = self._gen(zb, labels)
         n, aug = xgenb.shape[0], self.critic_aug
         if aug is not None and aug_params is None:
             aug_params = aug.draw(n + xb.shape[0], xb.shape[2], xb.shape[3], xb.device)
@@ -313,16 +355,16 @@ class GANLearner(object):
             if aug is not None:        # one launch over the pair: per sample, the same as two
                 both = aug(both, aug_params)
                 xgenb, xb = both[:n], both[n:]
-            out = self.disc_model(both)
+            out = self._disc(both, torch.cat((labels, labels)) if labels is not None else None)
             d_gen, d_real = out[:n], out[n:]
         else:
             if aug is not None:
                 xgenb, xb = aug(xgenb, aug_params[:n]), aug(xb, aug_params[n:])
-            d_gen, d_real = self.disc_model(xgenb), self.disc_model(xb)
+            d_gen, d_real = self._disc(xgenb, labels), self._disc(xb, labels)
         loss = self.loss_func_disc(d_gen, d_real)
         self._ada_update(d_real)
         if self.gradient_penalty is not None:
-            loss = loss + self.calc_gp(xgenb, xb, eps_interp=eps_interp)
+            loss = loss + self.calc_gp(xgenb, xb, eps_interp=eps_interp, labels=labels)
         # With spectral normalisation the normalised layers' gradients reach the arena only in ``sn.backward()``, after the
         # sweep: no bucket of the critic arena may leave from inside the backward, so the reducer is not armed and
         # ``allreduce`` sends the whole arena afterwards.
@@ -375,7 +417,8 @@ class GANLearner(object):
                         self.train_dataiter = iter(train_dl)
                         batch = next(self.train_dataiter)
                     xb = batch[0].to(c.dev, non_blocking=True).float()
-                    loss_d = self.d_step(xb)
+                    # config.cgan: the batch's labels, range-checked while they are still on the host (_device_labels)
+                    loss_d = self.d_step(xb, labels=batch[1] if self.cgan else None)
                     self.curr_dataset_batch_num += 1
                     self.curr_img_num += self.batch_size
                 if self.sched_bool:
@@ -414,6 +457,8 @@ class GANLearner(object):
         spectral_norm.check_save_format(bool(getattr(self.config, 'spectral_norm', False)), reference_format)
         from .. import attention
         attention.check_save_format(getattr(self.config, 'self_attention', None), reference_format)
+        from .. import conditional
+        conditional.check_save_format(getattr(self.config, 'cgan', None), reference_format)
         if reference_format:
             raise NotImplementedError('the ResNet GAN learner writes plain-data checkpoints only')
         if self.not_trained_yet:
@@ -424,7 +469,7 @@ class GANLearner(object):
         ck = {
             'config': ckpt.saved_config_fields({k: v for k, v in vars(self.config).items() if not k.startswith('_') and
                                                 isinstance(v, (int, float, str, bool, dict, list, tuple, type(None))) and
-                                                not (k == 'self_attention' and v is None)}),
+                                                not (k in ('self_attention', 'cgan') and v is None)}),
             'gen_model_state_dict': {k: v.detach().cpu() for k, v in self.gen_model.state_dict().items()},
             'disc_model_state_dict': {k: v.detach().cpu() for k, v in self.disc_model.state_dict().items()},
             'opt_gen_state_dict': self.opt_gen.export_moments(self.gen_model.named_parameters()),
@@ -465,9 +510,11 @@ class GANLearner(object):
         self.pretrained_model = True
 
     # -- gradient penalty (resnetgan/learner.py:780-827) ------------------------------------------------
-    def calc_gp(self, gen_data, real_data, eps_interp=None):
-        """Method that takes care of all gradient regularizers (double backward through HIP kernels)."""
-        return bp.calc_gp(self.disc_model, self.gradient_penalty, gen_data, real_data, lda=self.config.lda,
+    def calc_gp(self, gen_data, real_data, eps_interp=None, labels=None):
+        """Method that takes care of all gradient regularizers (double backward through HIP kernels).  ``labels``
+        (``config.cgan``): the critic is evaluated as a closure over the batch's labels."""
+        disc = self.disc_model if labels is None else (lambda x: self.disc_model(x, labels))
+        return bp.calc_gp(disc, self.gradient_penalty, gen_data, real_data, lda=self.config.lda,
                           gamma=self.config.gamma, eps_interp=eps_interp)
 
     # -- redefinable-from-learner properties (:831-946) -------------------------------------------------

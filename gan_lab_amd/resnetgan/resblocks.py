@@ -24,7 +24,8 @@ class ResBlock2d(nn.Module):
     """norm -> nl -> [up] conv [blur] -> norm -> nl -> conv [pool], plus a 1x1-conv skip (resblocks.py:15-64)."""
 
     def __init__(self, ni, nf, ks, norm_type, upsampler=None, pooler=None, init='He', nl=None, res=None,
-                 flip_sampling=False, equalized_lr=False, blur_type=None):
+                 flip_sampling=False, equalized_lr=False, blur_type=None, num_classes=0):
+        """``num_classes`` > 0 (not in the reference): both norms are class-conditional (NormalizeLayer)."""
         super().__init__()
         assert not (upsampler is not None and pooler is not None)
         upsampler, pooler, nl = _own_resampler(upsampler), _own_resampler(pooler), _own_nl(nl)
@@ -39,8 +40,8 @@ class ResBlock2d(nn.Module):
             Conv2dEx(ni, nf, ks=1, stride=1, padding=0, init='Xavier', equalized_lr=equalized_lr),
         )
         blur_op = get_blur_op(blur_type=blur_type, num_channels=self.convs[0].nf) if blur_type is not None else None
-        norm_nls = ([NormalizeLayer(norm_type, ni=ni, res=res), nl],
-                    [NormalizeLayer(norm_type, ni=self.convs[0].nf, res=res), nl])
+        norm_nls = ([NormalizeLayer(norm_type, ni=ni, res=res, num_classes=num_classes), nl],
+                    [NormalizeLayer(norm_type, ni=self.convs[0].nf, res=res, num_classes=num_classes), nl])
         if upsampler is not None:
             op1 = [upsampler, self.convs[0], blur_op] if blur_type is not None else [upsampler, self.convs[0]]
             op2 = [upsampler, self.convs[2], blur_op] if blur_type is not None else [upsampler, self.convs[2]]
@@ -67,9 +68,9 @@ class ResBlock2d32Pix(ResBlock2d):
     """resblocks.py:67-80: flip_sampling default True; the pooling skip is conv1x1 -> pool."""
 
     def __init__(self, ni, nf, ks, norm_type, upsampler=None, pooler=None, init='He', nl=None, res=None,
-                 flip_sampling=True, equalized_lr=False, blur_type=None):
+                 flip_sampling=True, equalized_lr=False, blur_type=None, num_classes=0):
         super().__init__(ni, nf, ks, norm_type, upsampler, pooler, init, nl, res, flip_sampling, equalized_lr,
-                         blur_type)
+                         blur_type, num_classes)
         pooler = _own_resampler(pooler)
         if upsampler is None and pooler is not None:
             self.skip_connection = nn.Sequential(self.convs[2], pooler)

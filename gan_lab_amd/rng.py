@@ -59,6 +59,17 @@ def randn(shape, device='cuda'):
     return out
 
 
+def randint(n, high, device='cuda'):
+    """(n,) int32 uniform in [0, high): the class labels a conditional generator step draws (conditional.py); advances the stream
+    by ceil(n / 4) counters.  Not available while a step graph is being captured (the ResNet GAN steps eagerly)."""
+    n = int(n)
+    if _DEVICE_BASE['block'] is not None:
+        raise RuntimeError('rng.randint: not available while a step graph is being captured')
+    out = ops.randint(n, high, _STATE['seed'], _STATE['offset'], device)
+    _STATE['offset'] += (n + 3) // 4
+    return out
+
+
 def augment_params(n, h, w, device='cuda'):
     """(n, 8) DiffAugment parameter rows for (h, w) images (augment.py); advances the stream by 2 counters per row."""
     n = int(n)

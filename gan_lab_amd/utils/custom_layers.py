@@ -218,6 +218,35 @@ class BatchNorm2d(nn.BatchNorm2d):
                               act_slope=act_slope)
 
 
+class ConditionalBatchNorm2d(nn.Module):
+    """Class-conditional BatchNorm (de Vries et al. 2017; the generator norm of SNGAN-projection / SAGAN / BigGAN): the
+    buffers of ``BatchNorm2d`` and its parameter names, but ``weight`` / ``bias`` are (num_classes, ni) tables, one affine row
+    per class (initialised to 1 / 0), and sample n is scaled and shifted by row ``labels[n]`` (ops.cond_batch_norm).  The owning
+    network sets ``labels`` (int32, on the device) before it runs its Sequential and clears it afterwards."""
+
+    def __init__(self, ni, num_classes, eps=1e-5, momentum=0.1):
+        super().__init__()
+        if not isinstance(num_classes, int) or num_classes < 1:
+            raise ValueError(f'ConditionalBatchNorm2d: num_classes must be a positive int (got {num_classes!r})')
+        self.num_features, self.num_classes, self.eps, self.momentum = ni, num_classes, eps, momentum
+        self.weight = nn.Parameter(torch.ones(num_classes, ni))
+        self.bias = nn.Parameter(torch.zeros(num_classes, ni))
+        self.register_buffer('running_mean', torch.zeros(ni))
+        self.register_buffer('running_var', torch.ones(ni))
+        self.register_buffer('num_batches_tracked', torch.tensor(0, dtype=torch.long))
+        self.labels = None
+
+    def forward(self, x, act_slope=None):
+        if self.labels is None:
+            raise ValueError('ConditionalBatchNorm2d: no labels - a class-conditional network is called as net(input, labels)')
+        return ops.cond_batch_norm(x, self.weight, self.bias, self.labels, self.running_mean, self.running_var, self.training,
+                                   momentum=self.momentum, eps=self.eps,
+                                   batches=self.num_batches_tracked if self.training else None, act_slope=act_slope)
+
+    def extra_repr(self):
+        return f'{self.num_features}, num_classes={self.num_classes}, eps={self.eps}, momentum={self.momentum}'
+
+
 class LayerNorm(nn.LayerNorm):
     """nn.LayerNorm([C, R, R]) parameter container whose forward (and first / second derivatives, for
     WGAN-GP) runs on the HIP kernels (ops.layer_norm)."""
@@ -230,7 +259,8 @@ class LayerNorm(nn.LayerNorm):
 class NormalizeLayer(nn.Module):
     """All normalisation methods in one place (custom_layers.py:88-111)."""
 
-    def __init__(self, norm_type, ni=None, res=None):
+    def __init__(self, norm_type, ni=None, res=None, num_classes=0):
+        """``num_classes`` > 0: 'BatchNorm' is the class-conditional one (the other types have no conditional form)."""
         super().__init__()
         norm_type = norm_type.lower()
         if norm_type in ('pixelnorm', 'pixel norm',):
@@ -239,7 +269,7 @@ class NormalizeLayer(nn.Module):
             self.norm = InstanceNorm2d(eps=1.e-8)
         elif norm_type in ('batchnorm', 'batch norm',):
             assert isinstance(ni, int)
-            self.norm = BatchNorm2d(ni)
+            self.norm = ConditionalBatchNorm2d(ni, num_classes) if num_classes else BatchNorm2d(ni)
         elif norm_type in ('layernorm', 'layer norm',):
             assert isinstance(ni, int)
             assert isinstance(res, int)
@@ -251,7 +281,7 @@ class NormalizeLayer(nn.Module):
         """``act_slope``: the LeakyReLU that follows (fused_sequential) - Batch / LayerNorm apply it in their own passes."""
         if act_slope is None:
             return self.norm(x)
-        if isinstance(self.norm, (BatchNorm2d, LayerNorm)):
+        if isinstance(self.norm, (BatchNorm2d, ConditionalBatchNorm2d, LayerNorm)):
             return self.norm(x, act_slope=act_slope)
         return ops.bias_act(self.norm(x), act='lrelu', slope=act_slope)
 

@@ -828,6 +828,37 @@ size_t ganlab_dot_workspace(long long n);
 int ganlab_dot_f32(const float* a, const float* b, float* out, long long n, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* ---- class conditioning of the ResNet GAN (config.cgan = 'projection'; csrc/cond.hip) --------------------------
+ * labels: int32 (N,) on the device; every kernel clamps them into [0, K) before indexing a (K, .) table.  No atomics, fixed
+ * summation order (n ascending): bitwise reproducible.  Stream-ordered, nothing is read back by the host.
+ * Conditional BatchNorm, weight / bias (K, C); mean / rstd (C): the batch statistics of ganlab_bn_stats_f32 +
+ * ganlab_bn_finalize_f32(weight = NULL), or the running ones (eval mode).
+ *   cbn_apply: y[n,c,:] = act((x - mean[c]) * (rstd[c] * weight[l_n,c]) + bias[l_n,c])   (bn_apply's centred form: a table of
+ *              equal rows gives ganlab_bn_apply_f32's bits)
+ *   cbn_bwd:   gz = gy * lrelu'(yact) (yact / gz both NULL: gz = gy); sums[c] = {sum ghat, sum ghat * xhat}, ghat = gz *
+ *              weight[l_n,c]; gb[k,c] = sum_{n: l_n = k} sum_hw gz, gw[k,c] likewise of gz * xhat (every row written, zeros for
+ *              an absent class); gx (may be NULL) = rstd[c] * (ghat - s0/L - xhat * s1/L), L = N*HW - with batch_stats = 0
+ *              (eval mode) gx = rstd[c] * ghat.  Three launches; workspace ganlab_cbn_bwd_workspace(N, C) bytes (fp64 plane sums) */
+int ganlab_cbn_apply_f32(const float* x, const float* mean, const float* rstd, const float* weight, const float* bias,
+                         const int* labels, float* y, int N, int C, long long HW, int K, int act, float slope, void* stream);
+size_t ganlab_cbn_bwd_workspace(int N, int C);
+int ganlab_cbn_bwd_f32(const float* gy, const float* x, const float* mean, const float* rstd, const float* weight,
+                       const int* labels, const float* yact, float* gz, float* gx, float* gw, float* gb, float* sums, int N,
+                       int C, long long HW, int K, int batch_stats, float slope, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* The projection critic's class term, weight (K, F), f (N, F); three kernels that are each other's derivatives:
+ *   proj_fwd:     out[n] = base[n] + sum_j weight[l_n,j] f[n,j]       (base may be NULL: 0)
+ *   proj_dfeat:   out[n,j] = g[n] weight[l_n,j]
+ *   proj_dweight: out[k,j] = sum_{n: l_n = k} g[n] f[n,j]             (every row written) */
+int ganlab_proj_fwd_f32(const float* f, const float* weight, const int* labels, const float* base, float* out, int N,
+                        long long F, int K, void* stream);
+int ganlab_proj_dfeat_f32(const float* g, const float* weight, const int* labels, float* out, int N, long long F, int K,
+                          void* stream);
+int ganlab_proj_dweight_f32(const float* g, const float* f, const int* labels, float* out, int N, long long F, int K,
+                            void* stream);
+/* n integers uniform in [0, high), high <= 2^24, from the Philox stream: element e is word e % 4 of counter offset + e / 4 */
+int ganlab_randint_i32(int* out, long long n, int high, uint64_t seed, uint64_t offset, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
