@@ -48,6 +48,15 @@ class SnJob(ctypes.Structure):
 
 SN_ROW_CHUNK, SN_COL_TILE, SN_ELEM_BLOCK = 16, 1024, 2048      # GANLAB_SN_* (include/ganlab_hip.h)
 
+
+class OrthoJob(ctypes.Structure):
+    """Mirror of `ganlab_ortho_job` (include/ganlab_hip.h): one layer of the orthogonal-regularisation job table."""
+    _fields_ = [('w', _c_p), ('gw', _c_p), ('s', _c_p), ('q', _c_p), ('part', _c_p), ('penalty', _c_p), ('R', _c_int),
+                ('K', _c_int), ('form', _c_int), ('n_part', _c_int), ('blk_g0', _c_ll), ('blk_a0', _c_ll)]
+
+
+ORTHO_TILE, ORTHO_QROWS, ORTHO_ROW, ORTHO_COL = 64, 4, 0, 1      # GANLAB_ORTHO_* (include/ganlab_hip.h)
+
 # name -> (restype, argtypes): must list every function declared in include/ganlab_hip.h
 SIGNATURES = {
     'ganlab_abi_version': (_c_int, []),
@@ -266,6 +275,8 @@ SIGNATURES = {
     'ganlab_sn_job_size': (_c_int, []),
     'ganlab_sn_refresh': (_c_int, [_c_p, _c_int, _c_ll, _c_ll, _c_ll, _c_int, _c_f, _c_p]),
     'ganlab_sn_backward': (_c_int, [_c_p, _c_int, _c_ll, _c_p]),
+    'ganlab_ortho_job_size': (_c_int, []),
+    'ganlab_ortho_apply': (_c_int, [_c_p, _c_int, _c_ll, _c_ll, _c_f, _c_p, _c_p]),
     'ganlab_attn_supported': (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     'ganlab_attn_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p]),
     'ganlab_attn_bwd_workspace': (_c_sz, [_c_int, _c_int]),
@@ -328,6 +339,9 @@ def lib():
         if handle.ganlab_sn_job_size() != ctypes.sizeof(SnJob):
             raise GanlabLibraryError(f'SnJob mirror is {ctypes.sizeof(SnJob)} bytes, the library\'s '
                                      f'ganlab_sn_job {handle.ganlab_sn_job_size()}: header and binding disagree')
+        if handle.ganlab_ortho_job_size() != ctypes.sizeof(OrthoJob):
+            raise GanlabLibraryError(f'OrthoJob mirror is {ctypes.sizeof(OrthoJob)} bytes, the library\'s '
+                                     f'ganlab_ortho_job {handle.ganlab_ortho_job_size()}: header and binding disagree')
         _LIB = handle
     return _LIB
 

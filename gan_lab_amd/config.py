@@ -40,8 +40,14 @@ class-conditional BatchNorm in the generator, a projection critic, on HIP kernel
 the learner's steps take the batch's labels (``DeviceImageLoader(labels=...)`` or any loader that yields ``(x, label)``).  It is
 independent of ``class_condition`` / ``use_auxiliary_classifier`` (the reference's own conditioning, which never ran and keeps
 raising), works with every loss, penalty and augmentation and with ``spectral_norm`` / ``self_attention``; any other value, a
-progressive model or ``num_classes`` < 2 raises when the learner is built.  ``--gradient_penalty=none`` on the command line
-means no penalty (None), as ``make_config(gradient_penalty=None)`` does.
+progressive model or ``num_classes`` < 2 raises when the learner is built; ``ortho_reg`` / ``ortho_reg_d`` (ResNet GAN only; 0 =
+off) are the strengths beta of BigGAN's orthogonal regulariser (Brock et al. 2019, eq. 3; ortho_reg.py) on the generator's / the
+critic's Conv2dEx and LinearEx weights: at every generator (critic) update the gradient ``4 beta ((Wm Wm^T) o (1 - I)) Wm`` of
+``beta |(Wm Wm^T) o (1 - I)|_F^2`` is added to the parameter gradients by batched fp32 matrix-core kernels, after the all-reduce
+and before the optimiser step; normalisation affines, the class tables, biases and attention's ``gamma`` are exempt.  BigGAN
+trains with 1e-4 on the generator and 0 on the critic (BigGAN-PyTorch's ``ortho()`` applies half this gradient for the same
+number); a negative or non-finite value raises when the learner is built, and ProGAN / StyleGAN have no such field.
+``--gradient_penalty=none`` on the command line means no penalty (None), as ``make_config(gradient_penalty=None)`` does.
 """
 import argparse
 import os
@@ -100,7 +106,8 @@ def _spec(model_type):
                  ('lr_base', float, .0001), ('lr_sched', str.casefold, None), ('beta2', float, .9),
                  ('res_samples', int, 64), ('res_dataset', int, 64), ('blur_type', str.casefold, None),
                  ('eps_drift', float, 0.), ('len_latent', int, 128), ('nonlinearity', str.casefold, 'relu'),
-                 ('leakiness', float, .01), ('use_equalized_lr', bool, False), ('spectral_norm', bool, False)]
+                 ('leakiness', float, .01), ('use_equalized_lr', bool, False), ('spectral_norm', bool, False),
+                 ('ortho_reg', float, 0.), ('ortho_reg_d', float, 0.)]
     else:
         rows += [('batch_size', int, BS),
                  ('bs_dict', dict, {4: BS, 8: BS, 16: BS, 32: BS, 64: BS, 128: BS, 256: BS, 512: BS // 2,

@@ -1789,6 +1789,93 @@ def sn_backward(table):
     check(_lib.lib().ganlab_sn_backward(table.table.data_ptr(), table.n, table.blocks[2], _st()), 'sn_backward')
 
 
+# ---- orthogonal regularisation: every weight of a network per launch (csrc/ortho.hip) ----------------------------------
+def ortho_plan(shapes):
+    """Host-side layout of the job table of ``ganlab_ortho_apply`` for weights of the given (R, K) shapes.  -> (entries,
+    scratch floats, (Gram blocks, apply blocks)); ``entries[i]`` is None for a layer with R == 1 (no off-diagonal element: its
+    penalty and gradient are exactly 0, it is left out) and else a dict with ``form`` (row form when R <= K, else column form:
+    the m x m Gram matrix has m = min(R, K)), ``m``, the float offsets ``s``, ``q`` (None in row form) and ``part`` into the
+    scratch, ``n_part`` and the first block ``blk_g0`` / ``blk_a0`` of either pass.  Pure arithmetic: no GPU, no library."""
+    T, QR = _lib.ORTHO_TILE, _lib.ORTHO_QROWS
+    entries, need, bg, ba = [], 0, 0, 0
+
+    def take(n):
+        nonlocal need
+        o = need
+        need += (n + 3) // 4 * 4
+        return o
+
+    for R, K in shapes:
+        R, K = int(R), int(K)
+        if R < 1 or K < 1:
+            raise ValueError(f'ortho_plan: bad weight shape ({R}, {K})')
+        if R == 1:
+            entries.append(None)
+            continue
+        row = R <= K
+        m = R if row else K
+        tm = (m + T - 1) // T
+        n_part = tm * tm + (0 if row else (R + QR - 1) // QR)
+        e = dict(R=R, K=K, form=_lib.ORTHO_ROW if row else _lib.ORTHO_COL, m=m, s=take(m * m), q=None if row else take(R),
+                 part=take(n_part), n_part=n_part, blk_g0=bg, blk_a0=ba)
+        bg += n_part
+        ba += ((R + T - 1) // T) * ((K + T - 1) // T)
+        entries.append(e)
+    return entries, need, (bg, ba)
+
+
+class OrthoTable(object):
+    """Device-resident job table of ``ganlab_ortho_apply``.  ``layers``: one dict per weight with the float32 GPU tensors ``w``
+    (the parameter, viewed as (shape[0], -1)) and ``gw`` (its gradient slot, same numel), both contiguous and 16-byte aligned.
+    Built and uploaded once (outside any capture), together with the scratch (the m x m Gram matrices, q, the partial sums) and
+    the results: ``penalties`` holds one float per layer (0 for a skipped one) and then the total.  Keeps the tensors it points
+    at alive."""
+
+    def __init__(self, layers):
+        if not layers:
+            raise ValueError('OrthoTable: no layers')
+        self.layers = [dict(d) for d in layers]
+        dev = self.layers[0]['w'].device
+        shapes = []
+        for d in self.layers:
+            w = d['w']
+            R = int(w.shape[0])
+            K = w.numel() // R
+            for name in ('w', 'gw'):
+                t = d[name]
+                _c(t, f'OrthoTable {name}')
+                if not t.is_contiguous() or t.numel() != R * K or t.data_ptr() % 16 or t.device != dev:
+                    raise ValueError(f'OrthoTable: {name} must be contiguous, 16-byte aligned, on {dev}, with {R * K} elements '
+                                     f'(got {tuple(t.shape)} at {t.data_ptr():#x} on {t.device})')
+            shapes.append((R, K))
+        self.plan, need, self.blocks = ortho_plan(shapes)
+        self.scratch = torch.zeros(max(need, 4), dtype=torch.float32, device=dev)
+        self.penalties = torch.zeros(len(self.layers) + 1, dtype=torch.float32, device=dev)
+        live = [(i, d, e) for i, (d, e) in enumerate(zip(self.layers, self.plan)) if e is not None]
+        self.n = len(live)
+        arr = (_lib.OrthoJob * max(self.n, 1))()
+        base, pen = self.scratch.data_ptr(), self.penalties.data_ptr()
+        for j, (i, d, e) in zip(arr, live):
+            j.w, j.gw = d['w'].data_ptr(), d['gw'].data_ptr()
+            j.s, j.part, j.penalty = base + 4 * e['s'], base + 4 * e['part'], pen + 4 * i
+            j.q = base + 4 * e['q'] if e['q'] is not None else None
+            j.R, j.K, j.form, j.n_part, j.blk_g0, j.blk_a0 = e['R'], e['K'], e['form'], e['n_part'], e['blk_g0'], e['blk_a0']
+        self.total = self.penalties[len(self.layers):]      # 1 element: beta * sum over all layers
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+
+
+def ortho_apply(table, beta):
+    """gw += 4 beta ((Wm Wm^T) o (1 - I)) Wm for every layer of ``table``, and ``table.penalties`` = beta * sum(M^2) per layer
+    and in total: 3 launches whatever the number of layers (none when every layer was skipped)."""
+    beta = float(beta)
+    if not (0.0 <= beta < float('inf')):
+        raise ValueError(f'ortho_apply: beta must be a finite number >= 0 (got {beta!r})')
+    if table.n == 0:
+        return
+    bg, ba = table.blocks
+    check(_lib.lib().ganlab_ortho_apply(table.table.data_ptr(), table.n, bg, ba, beta, _p(table.total), _st()), 'ortho_apply')
+
+
 def lerp_rows(a, b, t):
     a, b, t = _c(a), _c(b), _c(t)
     out = torch.empty_like(a)

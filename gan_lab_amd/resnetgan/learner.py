@@ -14,7 +14,9 @@ mean-all-reduced over RCCL (BatchNorm statistics stay per rank, like DDP without
 (spectral_norm.py) and ``loss='hinge'`` is its usual partner; ``config.self_attention`` ('g', 'd', 'gd'; ResNet GAN only) adds
 SAGAN's self-attention block to the generator / critic (attention.py); ``config.cgan='projection'`` (ResNet GAN only, with
 ``config.num_classes`` >= 2) makes the pair class-conditional - conditional BatchNorm in the generator, a projection critic
-(conditional.py) - and ``g_step`` / ``d_step`` then take the batch's labels; all four are off by default.
+(conditional.py) - and ``g_step`` / ``d_step`` then take the batch's labels; ``config.ortho_reg`` / ``config.ortho_reg_d``
+(ResNet GAN only) add the gradient of BigGAN's orthogonal regulariser to the generator's / critic's weight gradients before
+the optimiser step (ortho_reg.py); all of them are off by default.
 Validation metrics, image grids and plotting (:249-461, :950-1046) are outside the hot path."""
 import os
 import warnings
@@ -110,6 +112,10 @@ class GANLearner(object):
         self.gen_model = None
         self.disc_model = None
         self.sn = None          # spectral_norm.SpectralNorm of the ResNet GAN critic (config.spectral_norm)
+        # BigGAN's orthogonal regulariser (config.ortho_reg / config.ortho_reg_d; ortho_reg.py): managers over the arenas
+        from .. import ortho_reg
+        self._ortho_beta = ortho_reg.validate_config(config)
+        self.ortho_g = self.ortho_d = None
         self._gradient_penalty = config.gradient_penalty
         self._optimizer = config.optimizer.casefold()
         self.opt_gen = self.opt_disc = None
@@ -195,6 +201,11 @@ class GANLearner(object):
             if parallel.is_dist():
                 parallel.broadcast_params(self.sn.uv)       # u, v travel with the parameters
                 self.sn.refresh(iterate=False)
+        # the orthogonal regulariser's job tables point into the arenas: rebuilt with them (no state of their own)
+        from ..ortho_reg import OrthoReg
+        beta_g, beta_d = self._ortho_beta
+        self.ortho_g = OrthoReg(self.gen_model, self.arena_g, beta_g) if beta_g > 0 else None
+        self.ortho_d = OrthoReg(self.disc_model, self.arena_d, beta_d) if beta_d > 0 else None
 
     def _set_optimizer(self):
         """resnetgan/learner.py:884-908: Adam through configure_adam_for_gan; the others are not implemented
@@ -311,6 +322,9 @@ class GANLearner(object):
         with ops.direct_param_grads(ops.direct_grads_enabled()):      # first-use gradients land in the arena directly
             loss.backward()
         self.reducer.allreduce(self.arena_g.gflat)
+        if self.ortho_g is not None:            # rank-independent, so added after the reduction: every rank adds the same term
+            self.ortho_g.apply()
+            self.last_losses['ortho_g'] = self.ortho_g.penalty      # a device tensor: no host synchronisation
         self.opt_gen.step()
         return loss.detach()
 
@@ -375,6 +389,9 @@ class GANLearner(object):
         if self.sn is not None:
             self.sn.backward()
         self.reducer.allreduce(self.arena_d.gflat)
+        if self.ortho_d is not None:
+            self.ortho_d.apply()
+            self.last_losses['ortho_d'] = self.ortho_d.penalty
         self.opt_disc.step()
         return loss.detach()
 
@@ -430,7 +447,8 @@ class GANLearner(object):
                 if self.log_every and (itr % self.log_every == 0 or itr == num_main_iters - 1):
                     self.last_losses = dict(itr=itr, loss_d=float(loss_d) if loss_d is not None else None,
                                             loss_g=float(loss_g) if loss_g is not None else None,
-                                            res=c.res_samples, batch=self.batch_size)
+                                            res=c.res_samples, batch=self.batch_size,
+                                            **{k: v for k, v in self.last_losses.items() if k.startswith('ortho_')})
                     if parallel.rank() == 0:
                         print(('%9s' * 5) % (f'{self.curr_epoch_num}/{self.tot_num_epochs}',
                                              f'{c.res_samples}X{c.res_samples}',

@@ -798,6 +798,38 @@ int ganlab_sn_refresh(const ganlab_sn_job* jobs_device, int n_layers, long long 
                       long long blocks_e, int iterate, float eps, void* stream);
 int ganlab_sn_backward(const ganlab_sn_job* jobs_device, int n_layers, long long blocks_e, void* stream);
 
+/* ---- BigGAN orthogonal regularisation of every weight of a network, batched over the layers (csrc/ortho.hip)
+ * Brock et al. 2019, eq. 3, for a parameter W viewed as Wm = (R, K) row-major, M = (Wm Wm^T) o (1 - I):
+ *   penalty = beta * sum(M^2) ;  gW += 4 * beta * M Wm            (the true derivative of the penalty; accumulates)
+ * computed through the association with the smaller middle dimension m = min(R, K):
+ *   GANLAB_ORTHO_ROW (R <= K): S = Wm Wm^T (R, R), diagonal zeroed at the store ; G = S Wm ; sum(M^2) = sum(S^2)
+ *   GANLAB_ORTHO_COL (K <  R): S = Wm^T Wm (K, K), q[r] = |Wm[r,:]|^2 ; G = Wm S - q o Wm ; sum(M^2) = sum(S^2) - sum(q^2)
+ * Both products run on the exact-fp32 MFMA over GANLAB_ORTHO_TILE^2 output tiles, operands staged through LDS and zero-padded at
+ * the tails.  A layer with R == 1 has no off-diagonal element: the caller leaves it out of the table.
+ * `jobs_device`: device copy of n_layers jobs.  Every pointer is 16-byte aligned; w and gw hold R*K floats, s m*m, q R (column
+ * form; unused in row form), penalty 1, part n_part = T*T (+ ceil(R / GANLAB_ORTHO_QROWS) in column form) with
+ * T = ceil(m / GANLAB_ORTHO_TILE).  Job i owns blocks [blk_g0, +n_part) of the Gram pass and [blk_a0, +ceil(R / TILE) * ceil(K / TILE))
+ * of the apply pass; jobs are sorted by both and blocks_gram / blocks_apply are the totals.  3 launches whatever n_layers is
+ * (Gram, apply, a one-block tail that adds the partials in index order into every job's `penalty` and into `total_out`, both
+ * already times beta).  Fixed-order sums, no atomics: bitwise reproducible.  Nothing is read back by the host (graph-capturable). */
+#define GANLAB_ORTHO_TILE 64
+#define GANLAB_ORTHO_QROWS 4
+#define GANLAB_ORTHO_ROW 0
+#define GANLAB_ORTHO_COL 1
+typedef struct ganlab_ortho_job {
+  const float* w;        /* the parameter (R*K floats): read only */
+  float* gw;             /* the parameter's gradient slot: accumulated into */
+  float* s;              /* scratch: the m x m Gram matrix */
+  float* q;              /* scratch, column form: squared row norms (R) */
+  float* part;           /* scratch: n_part partial sums of the Gram pass */
+  float* penalty;        /* out: beta * sum(M^2) of this layer */
+  int R, K, form, n_part;
+  long long blk_g0, blk_a0;
+} ganlab_ortho_job;
+int ganlab_ortho_job_size(void);
+int ganlab_ortho_apply(const ganlab_ortho_job* jobs_device, int n_layers, long long blocks_gram, long long blocks_apply,
+                       float beta, float* total_out, void* stream);
+
 /* ---- SAGAN self-attention (Zhang et al. 2019; csrc/attention.hip) ----------------------------------------------
  * Channel-major operands as the 1x1 convolutions leave them: q (N, Dk, L), k (N, Dk, S), v (N, Dv, S); no 1/sqrt(d) scale.
  *   P[n,l,:] = softmax_s(sum_d q[n,d,l] k[n,d,s]) ; o[n,c,l] = sum_s v[n,c,s] P[n,l,s] ; lse[n,l] = logsumexp_s
