@@ -57,6 +57,13 @@ class OrthoJob(ctypes.Structure):
 
 ORTHO_TILE, ORTHO_QROWS, ORTHO_ROW, ORTHO_COL = 64, 4, 0, 1      # GANLAB_ORTHO_* (include/ganlab_hip.h)
 
+
+class HierJob(ctypes.Structure):
+    """Mirror of `ganlab_hier_job` (include/ganlab_hip.h): one modulation linear of the hierarchical-latent job table."""
+    _fields_ = [('w', _c_p), ('gw', _c_p), ('gw_own', _c_p), ('C', _c_int), ('z_off', _c_int), ('z_len', _c_int),
+                ('col', _c_int), ('scale', _c_f), ('one', _c_f), ('blk_f0', _c_ll), ('blk_w0', _c_ll)]
+
+
 # name -> (restype, argtypes): must list every function declared in include/ganlab_hip.h
 SIGNATURES = {
     'ganlab_abi_version': (_c_int, []),
@@ -290,6 +297,14 @@ SIGNATURES = {
     'ganlab_cbn_apply_f32': (_c_int, [_c_p] * 7 + [_c_int, _c_int, _c_ll, _c_int, _c_int, _c_f, _c_p]),
     'ganlab_cbn_bwd_workspace': (_c_sz, [_c_int, _c_int]),
     'ganlab_cbn_bwd_f32': (_c_int, [_c_p] * 12 + [_c_int, _c_int, _c_ll, _c_int, _c_int, _c_f, _c_p, _c_sz, _c_p]),
+    'ganlab_hier_job_size': (_c_int, []),
+    'ganlab_hier_fwd_f32': (_c_int, [_c_p, _c_int, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_int, _c_int, _c_p]),
+    'ganlab_hier_bwd_f32': (_c_int, [_c_p, _c_int, _c_ll] + [_c_p] * 7 + [_c_int, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    'ganlab_mbn_apply_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_ll, _c_p, _c_int, _c_int, _c_ll, _c_int, _c_f,
+                                      _c_p]),
+    'ganlab_mbn_bwd_workspace': (_c_sz, [_c_int, _c_int]),
+    'ganlab_mbn_bwd_f32': (_c_int, [_c_p] * 5 + [_c_ll] + [_c_p] * 5 + [_c_ll, _c_p, _c_int, _c_int, _c_ll, _c_int, _c_f, _c_p,
+                                    _c_sz, _c_p]),
     'ganlab_proj_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_p]),
     'ganlab_proj_dfeat_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_p]),
     'ganlab_proj_dweight_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_p]),
@@ -342,6 +357,9 @@ def lib():
         if handle.ganlab_ortho_job_size() != ctypes.sizeof(OrthoJob):
             raise GanlabLibraryError(f'OrthoJob mirror is {ctypes.sizeof(OrthoJob)} bytes, the library\'s '
                                      f'ganlab_ortho_job {handle.ganlab_ortho_job_size()}: header and binding disagree')
+        if handle.ganlab_hier_job_size() != ctypes.sizeof(HierJob):
+            raise GanlabLibraryError(f'HierJob mirror is {ctypes.sizeof(HierJob)} bytes, the library\'s '
+                                     f'ganlab_hier_job {handle.ganlab_hier_job_size()}: header and binding disagree')
         _LIB = handle
     return _LIB
 

@@ -46,7 +46,15 @@ critic's Conv2dEx and LinearEx weights: at every generator (critic) update the g
 ``beta |(Wm Wm^T) o (1 - I)|_F^2`` is added to the parameter gradients by batched fp32 matrix-core kernels, after the all-reduce
 and before the optimiser step; normalisation affines, the class tables, biases and attention's ``gamma`` are exempt.  BigGAN
 trains with 1e-4 on the generator and 0 on the critic (BigGAN-PyTorch's ``ortho()`` applies half this gradient for the same
-number); a negative or non-finite value raises when the learner is built, and ProGAN / StyleGAN have no such field.
+number); a negative or non-finite value raises when the learner is built, and ProGAN / StyleGAN have no such field;
+``hier_latent`` (bool) / ``shared_embed`` (int E; ResNet GAN only, both off by default) are BigGAN's generator conditioning
+(Brock et al. 2019; hier_latent.py): with ``hier_latent`` the latent is split over the first linear and the residual blocks
+(``chunk = len_latent // (B + 1)``, B = 3 at 32 pixels, 4 at 64; the first linear reads the first ``len_latent - B * chunk``
+entries, so 128 is 28 + 4 x 25 at 64 pixels), with ``shared_embed`` = E > 0 (needs ``cgan='projection'``; BigGAN uses 128) the
+class is embedded once into ``shared.weight`` (num_classes, E); both norms of every block then take their gain and bias from
+bias-free linears of ``[z_b, e(y)]`` (without labels: self-modulation, Chen et al. 2019), computed for the whole network in one
+launch, and the (num_classes, C) tables are gone.  ``len_latent < B + 1``, a negative value, ``shared_embed`` without ``cgan`` or
+a progressive model raises when the learner is built, and ProGAN / StyleGAN have no such field.
 ``--gradient_penalty=none`` on the command line means no penalty (None), as ``make_config(gradient_penalty=None)`` does.
 """
 import argparse
@@ -107,7 +115,7 @@ def _spec(model_type):
                  ('res_samples', int, 64), ('res_dataset', int, 64), ('blur_type', str.casefold, None),
                  ('eps_drift', float, 0.), ('len_latent', int, 128), ('nonlinearity', str.casefold, 'relu'),
                  ('leakiness', float, .01), ('use_equalized_lr', bool, False), ('spectral_norm', bool, False),
-                 ('ortho_reg', float, 0.), ('ortho_reg_d', float, 0.)]
+                 ('ortho_reg', float, 0.), ('ortho_reg_d', float, 0.), ('hier_latent', bool, False), ('shared_embed', int, 0)]
     else:
         rows += [('batch_size', int, BS),
                  ('bs_dict', dict, {4: BS, 8: BS, 16: BS, 32: BS, 64: BS, 128: BS, 256: BS, 512: BS // 2,

@@ -5,7 +5,11 @@ the reference; default off) adds a SAGAN block ``self_attn`` (attention.py) besi
 (not in the reference either; default off) with ``num_classes`` = K makes the networks class-conditional (conditional.py): every
 generator BatchNorm carries (K, C) tables and the generator is called as ``g(z, labels)``, the critic gains the projection layer
 ``proj`` and is called as ``d(x, labels)``.  With ``cgan`` the reference's meaning of ``num_classes`` (a one-hot concatenated to
-the input) does not apply: the inputs keep their widths."""
+the input) does not apply: the inputs keep their widths.  ``hier_latent=True`` / ``shared_embed=E`` (not in the reference; default
+off; generators only) are BigGAN's conditioning (hier_latent.py): both norms of every block become ``ModulatedBatchNorm2d`` whose
+``gain`` / ``shift`` linears read the block's chunk of ``z`` and / or the row ``shared.weight[label]`` of one (K, E) embedding, the
+first linear reads only the first chunk, the norm behind the last block is a plain ``BatchNorm2d`` and - with ``shared_embed`` -
+no (K, C) table is left; all gains and shifts of a forward come from one launch of the generator's ``hier`` manager."""
 from torch import nn
 
 from .. import ops
@@ -62,15 +66,61 @@ def _need_labels(net, labels):
 class _ResnetGenerator(GAN):
     ATTN_AFTER = None       # index of the first child of generator_model behind the attention block
     cgan = False
+    hier = None             # hier_latent.HierModulation with hier_latent / shared_embed
 
     def _init_cgan(self, cgan, num_classes):
         """``cgan=True``: the conditional norms were built by the blocks / NormalizeLayer; remember them for label routing."""
         from ..utils.custom_layers import ConditionalBatchNorm2d
         self.cgan = bool(cgan)
         self._cond_norms = [m for m in self.modules() if isinstance(m, ConditionalBatchNorm2d)] if self.cgan else []
-        assert not self.cgan or len(self._cond_norms) == sum(isinstance(m, NormalizeLayer) for m in self.modules())
+        assert not self.cgan or self.hier is not None or \
+            len(self._cond_norms) == sum(isinstance(m, NormalizeLayer) for m in self.modules())
+
+    def _init_hier(self, hier_latent, shared_embed, cgan, cond_classes, len_latent, num_classes, kw, blocks):
+        """``hier_latent`` / ``shared_embed``, before the Sequential is built.  -> (its first child, the input width of the first
+        linear, the keyword arguments of each of the ``blocks`` blocks, the classes of the last norm).  Both off: what the
+        generator has always had.  Else the first linear reads the first chunk of z only, the blocks' norms are modulated and
+        the last one is plain; ``_init_hier_manager`` finishes the job behind the Sequential."""
+        from .. import hier_latent as hl
+        if not isinstance(shared_embed, int) or isinstance(shared_embed, bool) or shared_embed < 0:
+            raise ValueError(f'shared_embed must be an int >= 0 (got {shared_embed!r})')
+        if shared_embed and not cgan:
+            raise ValueError('shared_embed > 0 needs cgan=True (and num_classes >= 2): it embeds the class')
+        self.hier_latent, self.shared_embed, self.hier = bool(hier_latent), shared_embed, None
+        if not self.hier_latent and not shared_embed:
+            return Lambda(lambda x: x.view(-1, len_latent + num_classes)), len_latent + num_classes, [kw] * blocks, cond_classes
+        first, self._chunks = hl.chunk_layout(len_latent, blocks) if self.hier_latent else (len_latent, [(0, 0)] * blocks)
+        if shared_embed:
+            self.shared = nn.Embedding(cond_classes, shared_embed)      # parameter container only (key `shared.weight`)
+        view = Lambda(lambda x: x.view(-1, len_latent)[:, :first]) if self.hier_latent else \
+            Lambda(lambda x: x.view(-1, len_latent))
+        return view, first, [dict(kw, num_classes=0, cond_dim=w + shared_embed) for _, w in self._chunks], 0
+
+    def _init_hier_manager(self):
+        if self.hier_latent or self.shared_embed:
+            from .. import hier_latent as hl
+            from ..utils.custom_layers import ModulatedBatchNorm2d
+            blocks = [m for m in self.generator_model if isinstance(m, ResBlock2d)]
+            norms = [(m, z_off, z_len) for blk, (z_off, z_len) in zip(blocks, self._chunks) for m in blk.modules()
+                     if isinstance(m, ModulatedBatchNorm2d)]
+            assert len(norms) == 2 * len(self._chunks)
+            self.hier = hl.HierModulation(self, norms, self.len_latent, self.shared if self.shared_embed else None)
+
+    def _forward_modulated(self, x, labels):
+        if self.shared_embed:
+            _need_labels(self, labels)
+        elif labels is not None and not self.cgan:
+            raise TypeError(f'{type(self).__name__} is not class-conditional (cgan=False) and takes no labels')
+        z = x.view(-1, self.len_latent)
+        self.hier(z, labels if self.shared_embed else None)
+        try:
+            return _run_with_attention(self, self.generator_model, z, self.ATTN_AFTER)
+        finally:
+            self.hier.clear()
 
     def forward(self, x, labels=None):
+        if self.hier is not None:
+            return self._forward_modulated(x, labels)
         if not self.cgan:
             if labels is not None:
                 raise TypeError(f'{type(self).__name__} is not class-conditional (cgan=False) and takes no labels')
@@ -93,7 +143,7 @@ class Generator32PixResnet(_ResnetGenerator):
     ATTN_AFTER = 5
 
     def __init__(self, len_latent=128, fmap=FMAP_G * 2, upsampler=None, blur_type=None, nl=None, num_classes=0,
-                 equalized_lr=False, self_attention=False, cgan=False):
+                 equalized_lr=False, self_attention=False, cgan=False, hier_latent=False, shared_embed=0):
         super().__init__(32)
         cond_classes, num_classes = _cgan_classes(cgan, num_classes)
         from ..utils.custom_layers import Upsample2x
@@ -103,20 +153,22 @@ class Generator32PixResnet(_ResnetGenerator):
         f0 = len_latent * FMAP_G_INIT_32_FCTR
         kw = dict(ks=3, norm_type='BatchNorm', upsampler=upsampler, init='He', nl=nl, equalized_lr=equalized_lr,
                   blur_type=blur_type, **({'num_classes': cond_classes} if cgan else {}))
+        view, nin, kws, last_classes = self._init_hier(hier_latent, shared_embed, cgan, cond_classes, len_latent, num_classes,
+                                                       kw, 3)
         self.generator_model = nn.Sequential(
-            Lambda(lambda x: x.view(-1, len_latent + num_classes)),
-            LinearEx(nin_feat=len_latent + num_classes, nout_feat=f0 * RES_INIT ** 2, init='Xavier',
-                     equalized_lr=equalized_lr),
+            view,
+            LinearEx(nin_feat=nin, nout_feat=f0 * RES_INIT ** 2, init='Xavier', equalized_lr=equalized_lr),
             Lambda(lambda x: x.view(-1, f0, RES_INIT, RES_INIT)),
-            ResBlock2d32Pix(ni=f0, nf=fmap, **kw),
-            ResBlock2d32Pix(ni=fmap, nf=fmap, **kw),
-            ResBlock2d32Pix(ni=fmap, nf=fmap, **kw),
-            NormalizeLayer('BatchNorm', ni=fmap, num_classes=cond_classes),
+            ResBlock2d32Pix(ni=f0, nf=fmap, **kws[0]),
+            ResBlock2d32Pix(ni=fmap, nf=fmap, **kws[1]),
+            ResBlock2d32Pix(ni=fmap, nf=fmap, **kws[2]),
+            NormalizeLayer('BatchNorm', ni=fmap, num_classes=last_classes),
             nl,
             Conv2dEx(ni=fmap, nf=FMAP_SAMPLES, ks=3, stride=1, padding=1, init='Xavier', equalized_lr=equalized_lr),
             Tanh(),
         )
         _init_self_attention(self, self_attention, fmap, equalized_lr)
+        self._init_hier_manager()
         self._init_cgan(cgan, cond_classes)
 
 
@@ -126,7 +178,7 @@ class Generator64PixResnet(_ResnetGenerator):
     ATTN_AFTER = 6
 
     def __init__(self, len_latent=128, fmap=FMAP_G, upsampler=None, blur_type=None, nl=None, num_classes=0,
-                 equalized_lr=False, self_attention=False, cgan=False):
+                 equalized_lr=False, self_attention=False, cgan=False, hier_latent=False, shared_embed=0):
         super().__init__(64)
         cond_classes, num_classes = _cgan_classes(cgan, num_classes)
         from ..utils.custom_layers import Upsample2x
@@ -136,21 +188,23 @@ class Generator64PixResnet(_ResnetGenerator):
         f0 = len_latent * FMAP_G_INIT_64_FCTR
         kw = dict(ks=3, norm_type='BatchNorm', upsampler=upsampler, init='He', nl=nl, equalized_lr=equalized_lr,
                   blur_type=blur_type, **({'num_classes': cond_classes} if cgan else {}))
+        view, nin, kws, last_classes = self._init_hier(hier_latent, shared_embed, cgan, cond_classes, len_latent, num_classes,
+                                                       kw, 4)
         self.generator_model = nn.Sequential(
-            Lambda(lambda x: x.view(-1, len_latent + num_classes)),
-            LinearEx(nin_feat=len_latent + num_classes, nout_feat=f0 * RES_INIT ** 2, init='Xavier',
-                     equalized_lr=equalized_lr),
+            view,
+            LinearEx(nin_feat=nin, nout_feat=f0 * RES_INIT ** 2, init='Xavier', equalized_lr=equalized_lr),
             Lambda(lambda x: x.view(-1, f0, RES_INIT, RES_INIT)),
-            ResBlock2d(ni=f0, nf=8 * fmap, **kw),
-            ResBlock2d(ni=8 * fmap, nf=4 * fmap, **kw),
-            ResBlock2d(ni=4 * fmap, nf=2 * fmap, **kw),
-            ResBlock2d(ni=2 * fmap, nf=1 * fmap, **kw),
-            NormalizeLayer('BatchNorm', ni=1 * fmap, num_classes=cond_classes),
+            ResBlock2d(ni=f0, nf=8 * fmap, **kws[0]),
+            ResBlock2d(ni=8 * fmap, nf=4 * fmap, **kws[1]),
+            ResBlock2d(ni=4 * fmap, nf=2 * fmap, **kws[2]),
+            ResBlock2d(ni=2 * fmap, nf=1 * fmap, **kws[3]),
+            NormalizeLayer('BatchNorm', ni=1 * fmap, num_classes=last_classes),
             nl,
             Conv2dEx(ni=1 * fmap, nf=FMAP_SAMPLES, ks=3, stride=1, padding=1, init='He', equalized_lr=equalized_lr),
             Tanh(),
         )
         _init_self_attention(self, self_attention, 2 * fmap, equalized_lr)
+        self._init_hier_manager()
         self._init_cgan(cgan, cond_classes)
 
 

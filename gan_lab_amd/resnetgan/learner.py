@@ -16,7 +16,9 @@ SAGAN's self-attention block to the generator / critic (attention.py); ``config.
 ``config.num_classes`` >= 2) makes the pair class-conditional - conditional BatchNorm in the generator, a projection critic
 (conditional.py) - and ``g_step`` / ``d_step`` then take the batch's labels; ``config.ortho_reg`` / ``config.ortho_reg_d``
 (ResNet GAN only) add the gradient of BigGAN's orthogonal regulariser to the generator's / critic's weight gradients before
-the optimiser step (ortho_reg.py); all of them are off by default.
+the optimiser step (ortho_reg.py); ``config.hier_latent`` / ``config.shared_embed`` (ResNet GAN only) give the generator BigGAN's
+conditioning - hierarchical latents and a shared class embedding modulating every block norm (hier_latent.py) - without touching
+the critic or the label routing; all of them are off by default.
 Validation metrics, image grids and plotting (:249-461, :950-1046) are outside the hot path."""
 import os
 import warnings
@@ -89,6 +91,9 @@ class GANLearner(object):
         # class conditioning of our own (config.cgan; conditional.py): conditional BatchNorm + projection critic, ResNet GAN only
         from .. import conditional
         self.cgan = conditional.validate_config(config)
+        # BigGAN's generator conditioning (config.hier_latent / config.shared_embed; hier_latent.py): ResNet GAN only
+        from .. import hier_latent
+        self._hier_latent, self._shared_embed = hier_latent.validate_config(config)
         if not (config.res_samples <= config.res_dataset):
             raise ValueError(f'Resolution of generated images (config.res_samples = {config.res_samples}) must be '
                              f'less than\nor equal to resolution of dataset (config.res_dataset = '
@@ -157,10 +162,11 @@ class GANLearner(object):
         fmap_g = getattr(config, 'fmap_g', fmap_g)      # width override (tests / small runs)
         fmap_d = getattr(config, 'fmap_d', fmap_d)
         cgan_kw = {'cgan': True, 'num_classes': c.num_classes} if self.cgan else {'num_classes': 0}
+        hier_kw = {k: v for k, v in (('hier_latent', self._hier_latent), ('shared_embed', self._shared_embed)) if v}
         self.gen_model = gen_cls(len_latent=c.len_latent, fmap=fmap_g, upsampler=self.gen_model_upsampler,
                                  blur_type=c.blur_type, nl=self.nl,
                                  equalized_lr=c.use_equalized_lr, **({'self_attention': True} if self._attn_g else {}),
-                                 **cgan_kw)
+                                 **cgan_kw, **hier_kw)
         from .. import spectral_norm
         sn_kw = {'spectral_norm': True} if spectral_norm.validate_config(config) else {}
         if self._attn_d:
@@ -201,6 +207,9 @@ class GANLearner(object):
             if parallel.is_dist():
                 parallel.broadcast_params(self.sn.uv)       # u, v travel with the parameters
                 self.sn.refresh(iterate=False)
+        # the generator's modulation job table (hier_latent.py) points into its arena too: uploaded now, not inside a step
+        if getattr(self.gen_model, 'hier', None) is not None and self.arena_g.flat.is_cuda:
+            self.gen_model.hier.attach()
         # the orthogonal regulariser's job tables point into the arenas: rebuilt with them (no state of their own)
         from ..ortho_reg import OrthoReg
         beta_g, beta_d = self._ortho_beta
@@ -469,14 +478,17 @@ class GANLearner(object):
     def save_model(self, save_path, sync=True, reference_format=False):
         """Checkpoint as plain data (key names follow resnetgan/learner.py:1076-1140).  ``sync=False``: no barrier
         behind rank 0's write (the interrupt path).  ``reference_format``: this learner writes plain-data checkpoints only;
-        with spectral normalisation or self-attention on the request is refused as a ValueError (the reference cannot hold
-        u, v or the block)."""
+        with spectral normalisation, self-attention, class conditioning or the hierarchical latent / shared embedding on the
+        request is refused as a ValueError (the reference cannot hold u, v, the block, the tables or the modulation)."""
         from .. import spectral_norm
         spectral_norm.check_save_format(bool(getattr(self.config, 'spectral_norm', False)), reference_format)
         from .. import attention
         attention.check_save_format(getattr(self.config, 'self_attention', None), reference_format)
         from .. import conditional
         conditional.check_save_format(getattr(self.config, 'cgan', None), reference_format)
+        from .. import hier_latent
+        hier_latent.check_save_format(getattr(self.config, 'hier_latent', False), getattr(self.config, 'shared_embed', 0),
+                                      reference_format)
         if reference_format:
             raise NotImplementedError('the ResNet GAN learner writes plain-data checkpoints only')
         if self.not_trained_yet:
@@ -487,7 +499,8 @@ class GANLearner(object):
         ck = {
             'config': ckpt.saved_config_fields({k: v for k, v in vars(self.config).items() if not k.startswith('_') and
                                                 isinstance(v, (int, float, str, bool, dict, list, tuple, type(None))) and
-                                                not (k in ('self_attention', 'cgan') and v is None)}),
+                                                not (k in ('self_attention', 'cgan') and v is None) and
+                                                not (k in ('hier_latent', 'shared_embed') and not v)}),
             'gen_model_state_dict': {k: v.detach().cpu() for k, v in self.gen_model.state_dict().items()},
             'disc_model_state_dict': {k: v.detach().cpu() for k, v in self.disc_model.state_dict().items()},
             'opt_gen_state_dict': self.opt_gen.export_moments(self.gen_model.named_parameters()),

@@ -24,8 +24,9 @@ class ResBlock2d(nn.Module):
     """norm -> nl -> [up] conv [blur] -> norm -> nl -> conv [pool], plus a 1x1-conv skip (resblocks.py:15-64)."""
 
     def __init__(self, ni, nf, ks, norm_type, upsampler=None, pooler=None, init='He', nl=None, res=None,
-                 flip_sampling=False, equalized_lr=False, blur_type=None, num_classes=0):
-        """``num_classes`` > 0 (not in the reference): both norms are class-conditional (NormalizeLayer)."""
+                 flip_sampling=False, equalized_lr=False, blur_type=None, num_classes=0, cond_dim=0):
+        """``num_classes`` > 0 (not in the reference): both norms are class-conditional; ``cond_dim`` > 0 (not in the reference
+        either): both are modulated by a conditioning vector of that width instead (NormalizeLayer)."""
         super().__init__()
         assert not (upsampler is not None and pooler is not None)
         upsampler, pooler, nl = _own_resampler(upsampler), _own_resampler(pooler), _own_nl(nl)
@@ -40,8 +41,9 @@ class ResBlock2d(nn.Module):
             Conv2dEx(ni, nf, ks=1, stride=1, padding=0, init='Xavier', equalized_lr=equalized_lr),
         )
         blur_op = get_blur_op(blur_type=blur_type, num_channels=self.convs[0].nf) if blur_type is not None else None
-        norm_nls = ([NormalizeLayer(norm_type, ni=ni, res=res, num_classes=num_classes), nl],
-                    [NormalizeLayer(norm_type, ni=self.convs[0].nf, res=res, num_classes=num_classes), nl])
+        norm_kw = dict(res=res, num_classes=num_classes, **({'cond_dim': cond_dim, 'equalized_lr': equalized_lr} if cond_dim else {}))
+        norm_nls = ([NormalizeLayer(norm_type, ni=ni, **norm_kw), nl],
+                    [NormalizeLayer(norm_type, ni=self.convs[0].nf, **norm_kw), nl])
         if upsampler is not None:
             op1 = [upsampler, self.convs[0], blur_op] if blur_type is not None else [upsampler, self.convs[0]]
             op2 = [upsampler, self.convs[2], blur_op] if blur_type is not None else [upsampler, self.convs[2]]
@@ -68,9 +70,9 @@ class ResBlock2d32Pix(ResBlock2d):
     """resblocks.py:67-80: flip_sampling default True; the pooling skip is conv1x1 -> pool."""
 
     def __init__(self, ni, nf, ks, norm_type, upsampler=None, pooler=None, init='He', nl=None, res=None,
-                 flip_sampling=True, equalized_lr=False, blur_type=None, num_classes=0):
+                 flip_sampling=True, equalized_lr=False, blur_type=None, num_classes=0, cond_dim=0):
         super().__init__(ni, nf, ks, norm_type, upsampler, pooler, init, nl, res, flip_sampling, equalized_lr,
-                         blur_type, num_classes)
+                         blur_type, num_classes, cond_dim)
         pooler = _own_resampler(pooler)
         if upsampler is None and pooler is not None:
             self.skip_connection = nn.Sequential(self.convs[2], pooler)

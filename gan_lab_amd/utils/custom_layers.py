@@ -247,6 +247,39 @@ class ConditionalBatchNorm2d(nn.Module):
         return f'{self.num_features}, num_classes={self.num_classes}, eps={self.eps}, momentum={self.momentum}'
 
 
+class ModulatedBatchNorm2d(nn.Module):
+    """BatchNorm whose gain and bias are linear maps of a per-sample conditioning vector (BigGAN's hierarchical latent and shared
+    class embedding; self-modulation without labels; hier_latent.py): the buffers of ``BatchNorm2d``, no ``weight`` / ``bias``,
+    and two bias-free ``LinearEx(cond_dim, ni)`` children ``gain`` / ``shift``:
+    ``y = act((x - mean) * rstd * (1 + <gain.W[c], cond[n]>) + <shift.W[c], cond[n]>)``.  The layer computes neither linear: the
+    owning generator's ``HierModulation`` runs all of them in one launch and sets ``mod`` before it runs its Sequential (and
+    clears it afterwards); the norm reads its columns ``cols`` of that flat buffer in place (ops.mod_batch_norm_cols)."""
+
+    def __init__(self, ni, cond_dim, eps=1e-5, momentum=0.1, equalized_lr=False):
+        super().__init__()
+        if not isinstance(cond_dim, int) or cond_dim < 1:
+            raise ValueError(f'ModulatedBatchNorm2d: cond_dim must be a positive int (got {cond_dim!r})')
+        self.num_features, self.cond_dim, self.eps, self.momentum = ni, cond_dim, eps, momentum
+        self.gain = LinearEx(cond_dim, ni, init='Xavier', equalized_lr=equalized_lr, include_bias=False)
+        self.shift = LinearEx(cond_dim, ni, init='Xavier', equalized_lr=equalized_lr, include_bias=False)
+        self.register_buffer('running_mean', torch.zeros(ni))
+        self.register_buffer('running_var', torch.ones(ni))
+        self.register_buffer('num_batches_tracked', torch.tensor(0, dtype=torch.long))
+        self.mod, self.cols = None, None
+
+    def forward(self, x, act_slope=None):
+        if self.mod is None:
+            raise ValueError('ModulatedBatchNorm2d: no modulation - the layer runs inside a generator built with hier_latent / '
+                             'shared_embed, which computes the gains and shifts of all its norms at once')
+        mod, flat, sink = self.mod
+        return ops.mod_batch_norm_cols(x, mod, flat, sink, self.cols[0], self.cols[1], self.running_mean, self.running_var,
+                                       self.training, momentum=self.momentum, eps=self.eps,
+                                       batches=self.num_batches_tracked if self.training else None, act_slope=act_slope)
+
+    def extra_repr(self):
+        return f'{self.num_features}, cond_dim={self.cond_dim}, eps={self.eps}, momentum={self.momentum}'
+
+
 class LayerNorm(nn.LayerNorm):
     """nn.LayerNorm([C, R, R]) parameter container whose forward (and first / second derivatives, for
     WGAN-GP) runs on the HIP kernels (ops.layer_norm)."""
@@ -259,8 +292,9 @@ class LayerNorm(nn.LayerNorm):
 class NormalizeLayer(nn.Module):
     """All normalisation methods in one place (custom_layers.py:88-111)."""
 
-    def __init__(self, norm_type, ni=None, res=None, num_classes=0):
-        """``num_classes`` > 0: 'BatchNorm' is the class-conditional one (the other types have no conditional form)."""
+    def __init__(self, norm_type, ni=None, res=None, num_classes=0, cond_dim=0, equalized_lr=False):
+        """``num_classes`` > 0: 'BatchNorm' is the class-conditional one; ``cond_dim`` > 0: the modulated one, whose ``gain`` /
+        ``shift`` linears take ``equalized_lr`` (the other types have neither form)."""
         super().__init__()
         norm_type = norm_type.lower()
         if norm_type in ('pixelnorm', 'pixel norm',):
@@ -269,7 +303,10 @@ class NormalizeLayer(nn.Module):
             self.norm = InstanceNorm2d(eps=1.e-8)
         elif norm_type in ('batchnorm', 'batch norm',):
             assert isinstance(ni, int)
-            self.norm = ConditionalBatchNorm2d(ni, num_classes) if num_classes else BatchNorm2d(ni)
+            if cond_dim:
+                self.norm = ModulatedBatchNorm2d(ni, cond_dim, equalized_lr=equalized_lr)
+            else:
+                self.norm = ConditionalBatchNorm2d(ni, num_classes) if num_classes else BatchNorm2d(ni)
         elif norm_type in ('layernorm', 'layer norm',):
             assert isinstance(ni, int)
             assert isinstance(res, int)
@@ -281,7 +318,7 @@ class NormalizeLayer(nn.Module):
         """``act_slope``: the LeakyReLU that follows (fused_sequential) - Batch / LayerNorm apply it in their own passes."""
         if act_slope is None:
             return self.norm(x)
-        if isinstance(self.norm, (BatchNorm2d, ConditionalBatchNorm2d, LayerNorm)):
+        if isinstance(self.norm, (BatchNorm2d, ConditionalBatchNorm2d, ModulatedBatchNorm2d, LayerNorm)):
             return self.norm(x, act_slope=act_slope)
         return ops.bias_act(self.norm(x), act='lrelu', slope=act_slope)
 

@@ -891,6 +891,48 @@ int ganlab_proj_dweight_f32(const float* g, const float* f, const int* labels, f
 /* n integers uniform in [0, high), high <= 2^24, from the Philox stream: element e is word e % 4 of counter offset + e / 4 */
 int ganlab_randint_i32(int* out, long long n, int high, uint64_t seed, uint64_t offset, void* stream);
 
+/* ---- BigGAN hierarchical latents + shared class embedding for the ResNet GAN generator (config.hier_latent /
+ * config.shared_embed; csrc/hier.hip).  No atomics, fixed summation order: bitwise reproducible.  Stream-ordered,
+ * nothing is read back by the host (graph-capturable); the job table is uploaded once.
+ * Modulation, batched over the linears of every norm: z (N, Lz) (NULL when Lz = 0), shared (K, E) and labels int32 (N,) (both
+ * NULL when E = 0; labels are clamped into [0, K)).  Job j is a bias-free linear w (C, D = z_len + E) reading
+ * cond[n,:] = [z[n, z_off : z_off + z_len], shared[l_n,:]], which is never materialised:
+ *   hier_fwd: out[n, col + c] = one + scale * <w[c,:], cond[n,:]> into the (N, T) buffer `out`; one launch.  Job j owns blocks
+ *             [blk_f0, + ceil(C / 64)) of grid.x; jobs are sorted by blk_f0 and blk_w0, blocks_fwd / blocks_dw are the totals.
+ *   hier_bwd: from g (N, T): every job's dW[c,d] = scale * sum_n g[n, col + c] cond[n,d] WRITTEN to its `gw` (own_slots = 0)
+ *             or `gw_own` (own_slots = 1) - job j owns blocks [blk_w0, + ceil(C * D / 256)); dz (N, Lz) (may be NULL), zero where
+ *             no job reads z; dshared (K, E) (may be NULL; needs the (N, E) scratch `de`), every row written.  At most three
+ *             launches whatever n_jobs is.
+ * The caller guarantees z_off + z_len <= Lz and col + C <= T for every job. */
+typedef struct ganlab_hier_job {
+  const float* w;        /* the parameter (C * D floats): read only */
+  float* gw;             /* its gradient slot in the arena (may be NULL: own_slots = 1 only) */
+  float* gw_own;         /* its gradient slot in the table's own buffer */
+  int C, z_off, z_len, col;
+  float scale, one;
+  long long blk_f0, blk_w0;
+} ganlab_hier_job;
+int ganlab_hier_job_size(void);
+int ganlab_hier_fwd_f32(const ganlab_hier_job* jobs_device, int n_jobs, long long blocks_fwd, const float* z,
+                        const float* shared, const int* labels, float* out, int N, long long T, int Lz, int E, int K,
+                        void* stream);
+int ganlab_hier_bwd_f32(const ganlab_hier_job* jobs_device, int n_jobs, long long blocks_dw, const float* g, const float* z,
+                        const float* shared, const int* labels, float* dz, float* de, float* dshared, int N, long long T,
+                        int Lz, int E, int K, int own_slots, void* stream);
+/* Modulated BatchNorm: ganlab_cbn_* with per-sample rows instead of class tables.  gain / shift are (N, C) with row strides
+ * (floats; views into the (N, T) buffer above), mean / rstd as for ganlab_cbn_apply_f32.
+ *   mbn_apply: y[n,c,:] = act((x - mean[c]) * (rstd[c] * gain[n,c]) + shift[n,c])    (equal rows give ganlab_bn_apply_f32's bits)
+ *   mbn_bwd:   as ganlab_cbn_bwd_f32 with ghat = gz * gain[n,c]; dshift[n,c] = sum_hw gz and dgain[n,c] = sum_hw gz * xhat are
+ *              written with row stride grad_stride (both may be NULL).  Three launches; workspace ganlab_mbn_bwd_workspace. */
+int ganlab_mbn_apply_f32(const float* x, const float* mean, const float* rstd, const float* gain, long long gain_stride,
+                         const float* shift, long long shift_stride, float* y, int N, int C, long long HW, int act,
+                         float slope, void* stream);
+size_t ganlab_mbn_bwd_workspace(int N, int C);
+int ganlab_mbn_bwd_f32(const float* gy, const float* x, const float* mean, const float* rstd, const float* gain,
+                       long long gain_stride, const float* yact, float* gz, float* gx, float* dgain, float* dshift,
+                       long long grad_stride, float* sums, int N, int C, long long HW, int batch_stats, float slope,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
