@@ -55,6 +55,11 @@ class OrthoJob(ctypes.Structure):
                 ('K', _c_int), ('form', _c_int), ('n_part', _c_int), ('blk_g0', _c_ll), ('blk_a0', _c_ll)]
 
 
+class EwmaJob(ctypes.Structure):
+    """Mirror of `ganlab_ewma_job` (include/ganlab_hip.h): one (dst, src, count) segment of the batched moving average."""
+    _fields_ = [('dst', _c_p), ('src', _c_p), ('count', _c_ll)]
+
+
 ORTHO_TILE, ORTHO_QROWS, ORTHO_ROW, ORTHO_COL = 64, 4, 0, 1      # GANLAB_ORTHO_* (include/ganlab_hip.h)
 
 
@@ -300,6 +305,9 @@ SIGNATURES = {
     'ganlab_hier_job_size': (_c_int, []),
     'ganlab_hier_fwd_f32': (_c_int, [_c_p, _c_int, _c_ll, _c_p, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_int, _c_int, _c_p]),
     'ganlab_hier_bwd_f32': (_c_int, [_c_p, _c_int, _c_ll] + [_c_p] * 7 + [_c_int, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    'ganlab_trunc_randn_f32': (_c_int, [_c_p, _c_ll, _c_f, _c_u64, _c_u64, _c_p]),
+    'ganlab_ewma_job_size': (_c_int, []),
+    'ganlab_ewma_many_f32': (_c_int, [_c_p, _c_int, _c_f, _c_p]),
     'ganlab_mbn_apply_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_ll, _c_p, _c_int, _c_int, _c_ll, _c_int, _c_f,
                                       _c_p]),
     'ganlab_mbn_bwd_workspace': (_c_sz, [_c_int, _c_int]),
@@ -360,6 +368,9 @@ def lib():
         if handle.ganlab_hier_job_size() != ctypes.sizeof(HierJob):
             raise GanlabLibraryError(f'HierJob mirror is {ctypes.sizeof(HierJob)} bytes, the library\'s '
                                      f'ganlab_hier_job {handle.ganlab_hier_job_size()}: header and binding disagree')
+        if handle.ganlab_ewma_job_size() != ctypes.sizeof(EwmaJob):
+            raise GanlabLibraryError(f'EwmaJob mirror is {ctypes.sizeof(EwmaJob)} bytes, the library\'s '
+                                     f'ganlab_ewma_job {handle.ganlab_ewma_job_size()}: header and binding disagree')
         _LIB = handle
     return _LIB
 

@@ -54,7 +54,15 @@ entries, so 128 is 28 + 4 x 25 at 64 pixels), with ``shared_embed`` = E > 0 (nee
 class is embedded once into ``shared.weight`` (num_classes, E); both norms of every block then take their gain and bias from
 bias-free linears of ``[z_b, e(y)]`` (without labels: self-modulation, Chen et al. 2019), computed for the whole network in one
 launch, and the (num_classes, C) tables are gone.  ``len_latent < B + 1``, a negative value, ``shared_embed`` without ``cgan`` or
-a progressive model raises when the learner is built, and ProGAN / StyleGAN have no such field.
+a progressive model raises when the learner is built, and ProGAN / StyleGAN have no such field;
+for the ResNet GAN, ``use_ewma_gen`` (bool, default False there; the progressive models' own field of this name is untouched) /
+``ewma_decay`` (0.9999; in [0, 1)) / ``ewma_start`` (0; >= 0) keep BigGAN's averaged generator (sampling.py): a copy of the
+generator whose parameters and BatchNorm buffers follow ``avg = d avg + (1 - d) live`` after every generator update, in two
+launches, with ``d = 0`` (a plain copy) while fewer than ``ewma_start`` updates have happened and ``d = ewma_decay`` afterwards;
+``truncation`` (None = off, else > 0) is the default threshold of ``learner.generate()``'s truncation trick - latents from the
+standard normal truncated to [-t, t] by inverse CDF on the project's Philox stream - and ``standing_stat_batches`` (16; >= 1)
+the default number of batches over which ``generate(standing_stats=True)`` re-estimates every BatchNorm's statistics as a plain
+average; a value outside these ranges raises when the learner is built, and ProGAN / StyleGAN have none of the four new fields.
 ``--gradient_penalty=none`` on the command line means no penalty (None), as ``make_config(gradient_penalty=None)`` does.
 """
 import argparse
@@ -115,7 +123,9 @@ def _spec(model_type):
                  ('res_samples', int, 64), ('res_dataset', int, 64), ('blur_type', str.casefold, None),
                  ('eps_drift', float, 0.), ('len_latent', int, 128), ('nonlinearity', str.casefold, 'relu'),
                  ('leakiness', float, .01), ('use_equalized_lr', bool, False), ('spectral_norm', bool, False),
-                 ('ortho_reg', float, 0.), ('ortho_reg_d', float, 0.), ('hier_latent', bool, False), ('shared_embed', int, 0)]
+                 ('ortho_reg', float, 0.), ('ortho_reg_d', float, 0.), ('hier_latent', bool, False), ('shared_embed', int, 0),
+                 ('use_ewma_gen', bool, False), ('ewma_decay', float, 0.9999), ('ewma_start', int, 0),
+                 ('truncation', _float_or_none, None), ('standing_stat_batches', int, 16)]
     else:
         rows += [('batch_size', int, BS),
                  ('bs_dict', dict, {4: BS, 8: BS, 16: BS, 32: BS, 64: BS, 128: BS, 256: BS, 512: BS // 2,

@@ -1337,6 +1337,27 @@ def randn(shape, seed, offset, device):
     return out
 
 
+def check_truncation(threshold, what='threshold'):
+    """The truncation threshold of ``trunc_randn`` as a float: finite and > 0, else ValueError."""
+    try:
+        t = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f'{what} must be a finite number > 0 (got {threshold!r})') from None
+    if isinstance(threshold, bool) or not (0.0 < t < float('inf')) or float(np.float32(t)) in (0.0, float('inf')):
+        raise ValueError(f'{what} must be a finite number > 0 (got {threshold!r})')
+    return t
+
+
+def trunc_randn(shape, threshold, seed, offset, device):
+    """Counter-based draws of N(0,1) truncated to [-threshold, threshold] by inverse CDF (csrc/sample.hip): ``randn``'s Philox
+    counters - element i is word i % 4 of counter ``offset + i // 4`` - and its advance of ceil(n / 4), no rejection loop."""
+    t = check_truncation(threshold)
+    out = _c(torch.empty(shape, dtype=torch.float32, device=device), 'trunc_randn output')
+    check(_lib.lib().ganlab_trunc_randn_f32(_p(out), out.numel(), t, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                            _st()), 'trunc_randn')
+    return out
+
+
 def randn_dev(shape, seed, base, delta, device):
     """``randn`` at stream position ``*base + delta`` (``base``: the step-scalar block of graphs.GraphedStep)."""
     out = torch.empty(shape, dtype=torch.float32, device=device)
@@ -1903,6 +1924,50 @@ def set_step_scalars(block, rng_base, floats):
 
 def ewma_step(lagged, p, beta):
     check(_lib.lib().ganlab_ewma_f32(_p(lagged), _p(p), p.numel(), beta, _st()), 'ewma')
+
+
+class EwmaTable(object):
+    """Device-resident job table of ``ganlab_ewma_many_f32``.  ``pairs``: [(lagged, src)], contiguous float32 GPU tensors of equal
+    size on one device, no two of them overlapping.  Built and uploaded once (outside any capture); keeps the tensors it points
+    at alive."""
+
+    def __init__(self, pairs):
+        self.pairs = [(a, b) for a, b in pairs]
+        if not self.pairs:
+            raise ValueError('EwmaTable: no segments')
+        if len(self.pairs) > 65535:
+            raise ValueError(f'EwmaTable: at most 65535 segments (got {len(self.pairs)})')
+        dev = self.pairs[0][0].device
+        arr = (_lib.EwmaJob * len(self.pairs))()
+        for j, (lagged, src) in zip(arr, self.pairs):
+            for t, what in ((lagged, 'EwmaTable lagged'), (src, 'EwmaTable src')):
+                _c(t, what)
+                if not t.is_contiguous() or t.device != dev:
+                    raise ValueError(f'{what} must be contiguous and on {dev} (got {tuple(t.shape)} on {t.device})')
+            if lagged.numel() != src.numel() or lagged.numel() < 1 or lagged.data_ptr() == src.data_ptr():
+                raise ValueError(f'EwmaTable: a segment needs two distinct tensors of one size >= 1 (got {tuple(lagged.shape)}, '
+                                 f'{tuple(src.shape)})')
+            j.dst, j.src, j.count = lagged.data_ptr(), src.data_ptr(), lagged.numel()
+        self.n = len(self.pairs)
+        self.pointers = self._pointers()
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+
+    def _pointers(self):
+        return tuple(t.data_ptr() for pair in self.pairs for t in pair)
+
+    def is_current(self):
+        """Do the tensors still lie where the uploaded table points?"""
+        return self.pointers == self._pointers()
+
+
+def ewma_many(table, decay):
+    """``lagged = decay * lagged + (1 - decay) * src`` for every segment of ``table`` in one launch; ``decay`` = 0 copies."""
+    decay = float(decay)
+    if not (0.0 <= decay < 1.0):
+        raise ValueError(f'ewma_many: decay must lie in [0, 1) (got {decay!r})')
+    if not table.is_current():
+        raise RuntimeError('ewma_many: a tensor of the table moved since it was built; build a new EwmaTable')
+    check(_lib.lib().ganlab_ewma_many_f32(table.table.data_ptr(), table.n, decay, _st()), 'ewma_many')
 
 
 # ---------------------------------------------------------------------------------------------- #

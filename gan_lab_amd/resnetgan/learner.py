@@ -18,7 +18,9 @@ SAGAN's self-attention block to the generator / critic (attention.py); ``config.
 (ResNet GAN only) add the gradient of BigGAN's orthogonal regulariser to the generator's / critic's weight gradients before
 the optimiser step (ortho_reg.py); ``config.hier_latent`` / ``config.shared_embed`` (ResNet GAN only) give the generator BigGAN's
 conditioning - hierarchical latents and a shared class embedding modulating every block norm (hier_latent.py) - without touching
-the critic or the label routing; all of them are off by default.
+the critic or the label routing; ``config.use_ewma_gen`` / ``config.truncation`` / ``config.standing_stat_batches`` (ResNet GAN
+only) are the sampling side - an averaged copy of the generator updated after every generator step, and ``generate()`` with the
+truncation trick and standing statistics (sampling.py); all of them are off by default.
 Validation metrics, image grids and plotting (:249-461, :950-1046) are outside the hot path."""
 import os
 import warnings
@@ -28,6 +30,7 @@ import torch
 from .. import _lib, ops, parallel
 from .._int import FMAP_SAMPLES, LearnerConfigCopy, get_current_configuration  # noqa: F401
 from ..optim import ParamArena
+from ..sampling import FROM_CONFIG
 from ..utils import backprop_utils as bp
 from ..utils.backprop_utils import configure_adam_for_gan
 from ..utils.custom_layers import LeakyReLU, Tanh, make_downsampler, make_upsampler
@@ -117,6 +120,7 @@ class GANLearner(object):
         self.gen_model = None
         self.disc_model = None
         self.sn = None          # spectral_norm.SpectralNorm of the ResNet GAN critic (config.spectral_norm)
+        self.gen_ema = None     # sampling.GeneratorEMA of the ResNet GAN generator (config.use_ewma_gen)
         # BigGAN's orthogonal regulariser (config.ortho_reg / config.ortho_reg_d; ortho_reg.py): managers over the arenas
         from .. import ortho_reg
         self._ortho_beta = ortho_reg.validate_config(config)
@@ -186,6 +190,10 @@ class GANLearner(object):
         self._set_loss()
         self._make_arenas()
         self._set_optimizer()
+        # the sampling side (config.use_ewma_gen / truncation / standing_stat_batches; sampling.py): the averaged generator
+        from .. import sampling
+        use_ema, ema_decay, ema_start, _, _ = sampling.validate_config(config)
+        self.gen_ema = sampling.GeneratorEMA(self.gen_model, self.arena_g, ema_decay, ema_start) if use_ema else None
         if parallel.rank() == 0:
             print('-------- Initialized Model Configuration --------')
             print(self.config)
@@ -215,6 +223,9 @@ class GANLearner(object):
         beta_g, beta_d = self._ortho_beta
         self.ortho_g = OrthoReg(self.gen_model, self.arena_g, beta_g) if beta_g > 0 else None
         self.ortho_d = OrthoReg(self.disc_model, self.arena_d, beta_d) if beta_d > 0 else None
+        # the averaged generator (sampling.py) reads the live parameters through their arena: re-pointed at a rebuilt one
+        if getattr(self, 'gen_ema', None) is not None:
+            self.gen_ema.rebind(self.gen_model, self.arena_g)
 
     def _set_optimizer(self):
         """resnetgan/learner.py:884-908: Adam through configure_adam_for_gan; the others are not implemented
@@ -335,7 +346,45 @@ class GANLearner(object):
             self.ortho_g.apply()
             self.last_losses['ortho_g'] = self.ortho_g.penalty      # a device tensor: no host synchronisation
         self.opt_gen.step()
+        if self.gen_ema is not None:
+            self.gen_ema.update()
         return loss.detach()
+
+    def generate(self, zs=None, n=None, labels=None, truncation=FROM_CONFIG, time_average=True, standing_stats=False):
+        """Images of the generator, sampled as BigGAN samples (sampling.py), under ``torch.no_grad()``.  ``zs``: the latents
+        (n, len_latent); None: ``n`` (default: the batch size) fresh ones from the process stream, from the standard normal
+        truncated to [-truncation, truncation] (default ``config.truncation``; None: untruncated).  ``labels`` (``config.cgan``):
+        as in ``g_step``, drawn uniformly when None.  ``time_average``: sample the averaged generator where there is one
+        (``config.use_ewma_gen``), else - and without one - the live generator in eval mode, whose train / eval state is put
+        back afterwards.  ``standing_stats`` (True: ``config.standing_stat_batches`` batches, or their number): first re-estimate
+        the BatchNorm statistics of the sampled network, which overwrites its running statistics."""
+        from .. import rng, sampling
+        c = self.config
+        if truncation is FROM_CONFIG:
+            truncation = getattr(c, 'truncation', None)
+        if truncation is not None:
+            truncation = ops.check_truncation(truncation, 'truncation')
+        if zs is None:
+            n = self.batch_size if n is None else int(n)
+            if n < 1:
+                raise ValueError(f'generate: n must be >= 1 (got {n})')
+            zs = rng.randn((n, c.len_latent), c.dev) if truncation is None else \
+                rng.trunc_randn((n, c.len_latent), truncation, c.dev)
+        elif n is not None and int(n) != zs.shape[0]:
+            raise ValueError(f'generate: {zs.shape[0]} latents were passed with n={n}')
+        labels = self._device_labels(labels, zs.shape[0], draw=True)
+        net = self.gen_ema.model if (time_average and self.gen_ema is not None) else self.gen_model
+        was_training = net.training
+        with torch.no_grad():
+            try:
+                if standing_stats:
+                    batches = getattr(c, 'standing_stat_batches', 16) if standing_stats is True else standing_stats
+                    draw = (lambda b: self._device_labels(None, b, draw=True)) if self.cgan else None
+                    sampling.standing_stats(net, batches, self.batch_size, c.len_latent, labels_fn=draw, truncation=truncation)
+                net.eval()
+                return net(zs, labels) if self.cgan else net(zs)
+            finally:
+                net.train(was_training)
 
     def _pair_critic_batches(self, xgenb, xb):
         """May the critic see the generated and the real batch as one?  Only when no critic layer couples samples (a
@@ -489,6 +538,8 @@ class GANLearner(object):
         from .. import hier_latent
         hier_latent.check_save_format(getattr(self.config, 'hier_latent', False), getattr(self.config, 'shared_embed', 0),
                                       reference_format)
+        from .. import sampling
+        sampling.check_save_format(self.gen_ema is not None, reference_format)
         if reference_format:
             raise NotImplementedError('the ResNet GAN learner writes plain-data checkpoints only')
         if self.not_trained_yet:
@@ -497,7 +548,8 @@ class GANLearner(object):
         tcpu = lambda v: None if v is None else v.detach().cpu()  # noqa: E731
         sched_steps = max(self.scheduler_gen._step_count - 1, 0) if (self.sched_bool and self.scheduler_gen) else 0
         ck = {
-            'config': ckpt.saved_config_fields({k: v for k, v in vars(self.config).items() if not k.startswith('_') and
+            'config': ckpt.saved_config_fields({k: v for k, v in sampling.saved_config_fields(vars(self.config)).items()
+                                                if not k.startswith('_') and
                                                 isinstance(v, (int, float, str, bool, dict, list, tuple, type(None))) and
                                                 not (k in ('self_attention', 'cgan') and v is None) and
                                                 not (k in ('hier_latent', 'shared_embed') and not v)}),
@@ -514,6 +566,9 @@ class GANLearner(object):
             'ds_mean': tcpu(self.ds_mean), 'ds_std': tcpu(self.ds_std), 'valid_z': tcpu(self.valid_z),
         }
         ck.update(self._ada_checkpoint_fields())
+        if self.gen_ema is not None:        # the averaged generator: only with config.use_ewma_gen, else the keys of always
+            ema = self.gen_ema.state_dict()
+            ck['gen_ema_state_dict'], ck['ewma_updates'] = ema['model'], ema['updates']
         if parallel.rank() == 0:            # replicas are identical: one writer, atomically; everyone waits for the file
             ckpt.save_atomic(ck, save_path)
         if sync:
@@ -538,6 +593,11 @@ class GANLearner(object):
         if ck.get('valid_z') is not None:
             self.valid_z = ck['valid_z'].to(self.config.dev)
         self._restore_ada(ck)
+        if self.gen_ema is not None:
+            if ck.get('gen_ema_state_dict') is not None:
+                self.gen_ema.load_state_dict({'model': ck['gen_ema_state_dict'], 'updates': ck.get('ewma_updates', 0)})
+            else:       # a checkpoint from before the option (or saved without it): the average starts from the loaded generator
+                self.gen_ema.reset()
         self.pretrained_model = True
 
     # -- gradient penalty (resnetgan/learner.py:780-827) ------------------------------------------------

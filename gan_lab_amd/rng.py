@@ -59,6 +59,20 @@ def randn(shape, device='cuda'):
     return out
 
 
+def trunc_randn(shape, threshold, device='cuda'):
+    """``randn`` truncated to [-threshold, threshold] (the truncation trick; sampling.py): the same counters, so the stream
+    advances exactly as ``randn`` of the same shape advances it.  Not available while a step graph is being captured."""
+    threshold = ops.check_truncation(threshold)
+    n = 1
+    for s in shape:
+        n *= int(s)
+    if _DEVICE_BASE['block'] is not None:
+        raise RuntimeError('rng.trunc_randn: not available while a step graph is being captured')
+    out = ops.trunc_randn(tuple(shape), threshold, _STATE['seed'], _STATE['offset'], device)
+    _STATE['offset'] += (n + 3) // 4
+    return out
+
+
 def randint(n, high, device='cuda'):
     """(n,) int32 uniform in [0, high): the class labels a conditional generator step draws (conditional.py); advances the stream
     by ceil(n / 4) counters.  Not available while a step graph is being captured (the ResNet GAN steps eagerly)."""

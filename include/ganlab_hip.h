@@ -933,6 +933,25 @@ int ganlab_mbn_bwd_f32(const float* gy, const float* x, const float* mean, const
                        long long grad_stride, float* sums, int N, int C, long long HW, int batch_stats, float slope,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the sampling side of the ResNet GAN: truncated-normal latents, the moving average of the averaged generator's BatchNorm
+ * buffers (config.use_ewma_gen / config.truncation; csrc/sample.hip).  No atomics, every element a pure function
+ * of its own inputs: bitwise reproducible whatever the launch geometry.  Stream-ordered, nothing is read back by the host.
+ *   trunc_randn: n draws of the standard normal truncated to [-threshold, threshold] (threshold finite and > 0) by inverse CDF.
+ *             Element i takes word i % 4 of Philox counter offset + i / 4 - the counters of ganlab_randn_f32, ceil(n / 4) of them:
+ *             u = ((word >> 9) + 1/2) 2^-23 in (0, 1), x = sqrt(2) erfinv((2u - 1) erf(threshold / sqrt(2))), clamped to
+ *             [-threshold, threshold].
+ *   ewma_many: dst[i] = decay * dst[i] + (1 - decay) * src[i] (fp64 arithmetic, rounded once) for i < count of every job of the
+ *             device-resident table, 0 <= decay < 1, n_jobs <= 65535; one launch.  decay = 0 copies src and does not read dst.
+ *             dst and src of a job do not overlap; no two jobs share a dst. */
+int ganlab_trunc_randn_f32(float* out, long long n, float threshold, uint64_t seed, uint64_t offset, void* stream);
+typedef struct ganlab_ewma_job {
+  float* dst;            /* the average: read (decay > 0) and written */
+  const float* src;      /* the live values: read only */
+  long long count;       /* floats */
+} ganlab_ewma_job;
+int ganlab_ewma_job_size(void);
+int ganlab_ewma_many_f32(const ganlab_ewma_job* jobs_device, int n_jobs, float decay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
