@@ -317,6 +317,9 @@ SIGNATURES = {
     'ganlab_proj_dfeat_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_p]),
     'ganlab_proj_dweight_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_ll, _c_int, _c_p]),
     'ganlab_randint_i32': (_c_int, [_c_p, _c_ll, _c_int, _c_u64, _c_u64, _c_p]),
+    'ganlab_prdc_norms_f32': (_c_int, [_c_p, _c_p, _c_ll, _c_int, _c_p]),
+    'ganlab_prdc_knn_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_p]),
+    'ganlab_prdc_cross_f32': (_c_int, [_c_p] * 5 + [_c_int, _c_p, _c_p, _c_p, _c_ll, _c_ll, _c_int, _c_p]),
     'ganlab_step_scalars_size': (_c_int, []),
     'ganlab_set_step_scalars': (_c_int, [_c_p, _c_u64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
 }

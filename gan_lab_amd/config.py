@@ -26,6 +26,11 @@ radii and over the upper half of them: the number that moves when an upsample, a
 high-frequency tail) with ``spectrum_window``: ``'hann'`` (the default) tapers each image with a periodic Hann window before the
 transform, so that the jump between opposite image borders does not leak a 1/f^2 cross into every radius; ``'none'`` transforms
 the image as it is (right for periodic textures, and the setting under which a circular shift leaves the profile unchanged);
+``'prdc'`` as an entry of ``gen_metrics`` (improved precision / recall and density / coverage of prdc.py between the generated
+validation images and the validation reals: k-nearest-neighbour statistics that separate fidelity from diversity and need no
+pretrained network; all three models) with ``prdc_k`` (the neighbour that sets a row's radius, in [1, 16], default 5) and
+``prdc_res`` (a power of two >= 4, default 32: images are reduced by 2x2 means to at most this size and flattened into the feature
+rows), validated when the learner is built;
 ``spectral_norm`` (ResNet GAN only; False = off): every Conv2dEx / LinearEx weight of the critic is divided by its largest
 singular value, estimated by one power iteration per critic update (spectral_norm.py; excludes ``use_equalized_lr``; validated
 when the learner is built), and ``loss='hinge'`` (ResNet GAN only) is the loss usually trained with it - with both on,
@@ -115,6 +120,7 @@ def _spec(model_type):
         ('ada_kimg', float, 500.0),
         ('swd_nhoods', int, 128), ('swd_dir_repeats', int, 4), ('swd_dirs_per_repeat', int, 128), ('swd_seed', int, 0),
         ('msssim_range', float, 2.0), ('spectrum_window', str.casefold, 'hann'),
+        ('prdc_k', int, 5), ('prdc_res', int, 32),
         ('self_attention', _str_or_none, None), ('cgan', _str_or_none, None),
     ]
     if model_type == 'ResNet GAN':

@@ -1607,6 +1607,78 @@ def swd_directions(n_dirs, seed, offset, device):
     return out
 
 
+# ---- k-nearest-neighbour precision / recall / density / coverage (csrc/prdc.hip; composed in gan_lab_amd/prdc.py) --------------
+PRDC_MAX_K = 16                      # GANLAB_PRDC_MAX_K (include/ganlab_hip.h)
+
+
+def _prdc_rows(t, what):
+    t = _c(t, what)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f'{what}: needs a non-empty (rows, width) matrix, got {tuple(t.shape)}')
+    return t
+
+
+def _prdc_vector(t, dtype, n, what):
+    t = _ct(t, dtype, what)
+    if tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError(f'{what}: must be a contiguous ({n},) tensor, got {tuple(t.shape)}')
+    return t
+
+
+def prdc_norms(rows, out=None):
+    """(N,) squared Euclidean norms of the rows of an (N, D) matrix: fp64 sums in a fixed order, rounded once."""
+    rows = _prdc_rows(rows, 'prdc_norms rows')
+    n, d = rows.shape
+    out = _new((n,), rows) if out is None else _prdc_vector(out, torch.float32, n, 'prdc_norms out')
+    check(_lib.lib().ganlab_prdc_norms_f32(_p(rows), _p(out), n, d, _st()), 'prdc_norms')
+    return out
+
+
+def prdc_knn(rows, k, norms=None, out=None):
+    """(N, k): per row of the (N, D) matrix the ``k`` smallest squared distances to the OTHER rows, ascending - the row itself is
+    excluded by index, a duplicate at another index counts; the last column is the k-NN radius.  ``norms``: ``prdc_norms(rows)``
+    when the caller already has them."""
+    rows = _prdc_rows(rows, 'prdc_knn rows')
+    n, d = rows.shape
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= PRDC_MAX_K:
+        raise ValueError(f'prdc_knn: k must be an integer in [1, {PRDC_MAX_K}], got {k!r}')
+    if k >= n:
+        raise ValueError(f'prdc_knn: k must be below the number of rows (k = {k}, rows = {n})')
+    norms = prdc_norms(rows) if norms is None else _prdc_vector(norms, torch.float32, n, 'prdc_knn norms')
+    if out is None:
+        out = _new((n, k), rows)
+    elif tuple(_c(out, 'prdc_knn out').shape) != (n, k) or not out.is_contiguous():
+        raise ValueError(f'prdc_knn: out must be a contiguous ({n}, {k}) tensor, got {tuple(out.shape)}')
+    check(_lib.lib().ganlab_prdc_knn_f32(_p(rows), _p(norms), _p(out), n, d, k, _st()), 'prdc_knn')
+    return out
+
+
+def prdc_cross(queries, keys, radii, radius_of='key', query_norms=None, key_norms=None, out=None):
+    """Queries (M, D) against keys (N, D) under a radius per key (``radius_of='key'``: ``radii`` is (N,)) or per query
+    (``'query'``: (M,)).  Returns per query row (count int32, smallest squared distance fp32, its key index int32): the number of
+    keys with squared distance <= the radius, and the nearest key, the lowest index of a tie.  ``out``: the three tensors."""
+    queries, keys = _prdc_rows(queries, 'prdc_cross queries'), _prdc_rows(keys, 'prdc_cross keys')
+    (m, d), (n, dk) = queries.shape, keys.shape
+    if d != dk:
+        raise ValueError(f'prdc_cross: queries and keys must have one width, got {d} and {dk}')
+    if radius_of not in ('key', 'query'):
+        raise ValueError(f"prdc_cross: radius_of must be 'key' or 'query', got {radius_of!r}")
+    radii = _prdc_vector(radii, torch.float32, n if radius_of == 'key' else m, f'prdc_cross radii (one per {radius_of})')
+    query_norms = prdc_norms(queries) if query_norms is None else \
+        _prdc_vector(query_norms, torch.float32, m, 'prdc_cross query_norms')
+    key_norms = prdc_norms(keys) if key_norms is None else _prdc_vector(key_norms, torch.float32, n, 'prdc_cross key_norms')
+    if out is None:
+        out = (torch.empty((m,), dtype=torch.int32, device=queries.device), _new((m,), queries),
+               torch.empty((m,), dtype=torch.int32, device=queries.device))
+    count = _prdc_vector(out[0], torch.int32, m, 'prdc_cross count')
+    dmin = _prdc_vector(out[1], torch.float32, m, 'prdc_cross smallest distance')
+    imin = _prdc_vector(out[2], torch.int32, m, 'prdc_cross nearest index')
+    check(_lib.lib().ganlab_prdc_cross_f32(_p(queries), _p(query_norms), _p(keys), _p(key_norms), _p(radii),
+                                           1 if radius_of == 'query' else 0, _p(count), _p(dmin), _p(imin), m, n, d, _st()),
+          'prdc_cross')
+    return count, dmin, imin
+
+
 # ---- multi-scale structural similarity (csrc/msssim.hip; composed in gan_lab_amd/msssim.py) -------------------------------------
 MSSSIM_LEVELS = 5                    # GANLAB_MSSSIM_LEVELS (include/ganlab_hip.h)
 

@@ -74,6 +74,9 @@ class GANLearner(object):
         # ... and the radial power-spectrum distance's ('spectrum' in config.gen_metrics; spectrum.py)
         from .. import spectrum
         spectrum.validate_config(config)
+        # ... and the k-nearest-neighbour precision / recall / density / coverage's ('prdc' in config.gen_metrics; prdc.py)
+        from .. import prdc
+        prdc.validate_config(config)
         # self-attention (config.self_attention; attention.py): a ResNet GAN option, and first order only - a critic with a
         # block excludes the gradient penalties
         from .. import attention
@@ -186,6 +189,8 @@ class GANLearner(object):
         self.reducer = parallel.GradReducer()
         self.log_every = getattr(config, 'log_every', 50)
         self.last_losses = {}
+        self.last_metrics = {}      # compute_metrics: {'generator': {'prdc': {...}}}
+        self._prdc_eval = None
         self._loss = config.loss.casefold()
         self._set_loss()
         self._make_arenas()
@@ -386,6 +391,61 @@ class GANLearner(object):
             finally:
                 net.train(was_training)
 
+    def compute_metrics(self, metrics, metrics_type, z_valid_dl, valid_dl=None):
+        """Validation metrics of the ResNet GAN over the validation latents and reals.  ``'prdc'`` - improved precision / recall
+        and density / coverage (prdc.py) - is the one metric this learner has; any other entry raises.  The generated set is
+        ``generate(zs=zb, truncation=None, time_average=True)`` per batch of ``z_valid_dl`` (the averaged generator where there
+        is one; with ``config.cgan`` the classes are drawn as ``generate`` draws them), the real set the batches of ``valid_dl``,
+        both reduced to rows by ``prdc.features`` and truncated to min(latents, reals) in whole batches.  The process stream is
+        put back where it was, so an evaluation does not move the training run.  Returns the formatted lines; the numbers are
+        kept in ``self.last_metrics['generator']['prdc']``."""
+        from .. import prdc, rng
+        c = self.config
+        metrics_type = metrics_type.casefold()
+        if metrics_type not in ('generator', 'critic', 'discriminator'):
+            raise Exception('Invalid metrics_type. Only "generator", "critic", or "discriminator" are accepted.')
+        metrics = [m.casefold() for m in metrics]
+        unsupported = [m for m in metrics if m != 'prdc']
+        if unsupported:
+            raise ValueError(f"the ResNet GAN learner computes 'prdc' only; unsupported metrics: {unsupported}")
+        if not metrics:
+            return []
+        if metrics_type != 'generator':
+            raise ValueError("'prdc' is a generator metric: it compares the generated validation images with the validation "
+                             "reals and cannot be listed among the critic's metrics (config.disc_metrics)")
+        if z_valid_dl is None or valid_dl is None:
+            raise ValueError("'prdc' needs the validation latents and reals: pass z_valid_dl and valid_dl "
+                             "(train(train_dl, valid_dl, z_valid_dl))")
+        n_use = min(len(z_valid_dl.dataset), len(valid_dl.dataset)) // self.batch_size * self.batch_size
+        if n_use < 1:
+            raise ValueError(f"'prdc' needs at least one whole batch of {self.batch_size} validation latents and reals (got "
+                             f"{len(z_valid_dl.dataset)} and {len(valid_dl.dataset)})")
+        key = (n_use, c.prdc_k, c.prdc_res)
+        if self._prdc_eval is None or self._prdc_eval[0] != key:
+            dim = prdc.feature_dim(3, c.res_samples, c.prdc_res)
+            self._prdc_eval = (key, prdc.PRDC(dim, n_use, n_use, k=c.prdc_k, device=c.dev))
+        ev = self._prdc_eval[1]
+        ev.reset()
+        offset, left, valid_iter = rng._STATE['offset'], n_use, iter(valid_dl)
+        try:
+            for zbatch in z_valid_dl:
+                if left <= 0:
+                    break
+                zb = zbatch[0].to(c.dev).float()
+                xb = next(valid_iter)[0].to(c.dev).float()
+                if len(zb) != len(xb) or len(zb) > left:
+                    raise ValueError(f"'prdc': validation latents and reals must come in equal batches (got {len(zb)} and "
+                                     f"{len(xb)} with {left} images to go)")
+                ev.feed_fake(prdc.features(self.generate(zs=zb, truncation=None, time_average=True), c.prdc_res))
+                ev.feed_real(prdc.features(xb, c.prdc_res))
+                left -= len(zb)
+        finally:
+            rng._STATE['offset'] = offset
+        out = ev.result()
+        self.last_metrics[metrics_type] = {'prdc': out}
+        names = ('precision', 'recall', 'density', 'coverage')
+        return ['    ' + ('%-12s' % (name + ':')) + '%.4g' % out[name] + '\n' for name in names]
+
     def _pair_critic_batches(self, xgenb, xb):
         """May the critic see the generated and the real batch as one?  Only when no critic layer couples samples (a
         BatchNorm would take its statistics over both) and the output is the plain score.  GANLAB_RESNET_PAIR=0: A/B."""
@@ -477,12 +537,20 @@ class GANLearner(object):
             per_epoch = max(self.dataset_sz // self.batch_size * self.batch_size, 1)
             self.tot_num_epochs = num_main_iters * self.batch_size * num_disc_iters // per_epoch + 1
         loss_d = loss_g = None
+        # the one validation metric of this learner ('prdc' in config.gen_metrics; compute_metrics): with both loaders only
+        from .. import prdc
+        want_prdc = prdc.wanted(c.gen_metrics) and valid_dl is not None and z_valid_dl is not None
         try:
             for itr in range(num_main_iters):
                 # ---------------------------- TRAIN GENERATOR ----------------------------
                 self.set_requires_grad_disc(False)
                 for _ in range(num_gen_iters):
                     loss_g = self.g_step()
+                if want_prdc and ((itr + 1) % c.num_iters_valid == 0 or itr == 0):
+                    vals = self.compute_metrics(metrics=['prdc'], metrics_type='Generator', z_valid_dl=z_valid_dl,
+                                                valid_dl=valid_dl)
+                    if parallel.rank() == 0:
+                        print('|\n', 'Generator Validation Metrics:\n', *vals)
                 # -------------------------- TRAIN DISCRIMINATOR --------------------------
                 self.set_requires_grad_disc(True)
                 for _ in range(num_disc_iters):

@@ -952,6 +952,24 @@ typedef struct ganlab_ewma_job {
 int ganlab_ewma_job_size(void);
 int ganlab_ewma_many_f32(const ganlab_ewma_job* jobs_device, int n_jobs, float decay, void* stream);
 
+/* ---- k-nearest-neighbour precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020) between two
+ * sets of fp32 feature rows (csrc/prdc.hip; composed in gan_lab_amd/prdc.py).  Rows are (rows, D) row-major, any
+ * D >= 1, at most 2^30 rows (more: GANLAB_EUNSUPPORTED).  Squared distances are max(|q|^2 + |k|^2 - 2 q.k, 0) with the product on the
+ * exact-fp32 MFMA; no N x M matrix is ever stored.  No atomics, nothing is read back by the host, stream-ordered, bitwise
+ * reproducible.
+ *   norms: out[i] = |x_i|^2, summed in fp64 in a fixed order and rounded once.
+ *   knn:   out (N, k): per row the k smallest squared distances to the other rows of x, ascending; the row itself is excluded by
+ *          index (a duplicate at another index counts).  1 <= k <= GANLAB_PRDC_MAX_K, k < N.  norms: ganlab_prdc_norms_f32 of x.
+ *   cross: per query row j of (M, D) against the keys (N, D): count[j] = #{i: d2(j, i) <= radius}, the radius being radii[i] (N of
+ *          them, radius_of_query = 0) or radii[j] (M of them, radius_of_query = 1); dmin[j] = min_i d2(j, i) and imin[j] its index,
+ *          the lowest index of a tie. */
+#define GANLAB_PRDC_MAX_K 16
+int ganlab_prdc_norms_f32(const float* x, float* out, long long rows, int D, void* stream);
+int ganlab_prdc_knn_f32(const float* x, const float* norms, float* out, long long N, int D, int k, void* stream);
+int ganlab_prdc_cross_f32(const float* queries, const float* query_norms, const float* keys, const float* key_norms,
+                          const float* radii, int radius_of_query, int* count, float* dmin, int* imin, long long M, long long N,
+                          int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
