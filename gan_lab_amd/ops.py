@@ -53,6 +53,33 @@ def _c(t, what='tensor'):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _inplace(t, what):
+    """``_c`` for an operand that a kernel updates in place through its raw pointer: a non-contiguous view is an error
+    (``.contiguous()`` would update a copy)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        raise TypeError(f'gan_lab_amd.ops: {what} must be a float32 tensor on the GPU (got '
+                        f'{type(t).__name__}, {getattr(t, "device", None)}, {getattr(t, "dtype", None)}); '
+                        f'the HIP path has no CPU fallback')
+    if not t.is_contiguous():
+        raise ValueError(f'gan_lab_amd.ops: {what} must be contiguous (shape {tuple(t.shape)}, strides {t.stride()}): '
+                         f'the kernel updates it in place')
+    return t
+
+
+def _same_numel(op, named):
+    """The raw-pointer ops walk every operand with the first one's element count."""
+    n, dev = named[0][1].numel(), named[0][1].device
+    for what, t in named[1:]:
+        if t.numel() != n or t.device != dev:
+            raise ValueError(f'gan_lab_amd.ops: {op}: {what} must have the {n} elements of {named[0][0]} on {dev} (got '
+                             f'{t.numel()} on {t.device})')
+
+
+def _gpu_device(device, what):
+    if torch.device(device).type != 'cuda':
+        raise TypeError(f'gan_lab_amd.ops: {what} draws on the GPU (got device {device!r}); the HIP path has no CPU fallback')
+
+
 def _new(shape, like):
     return torch.empty(shape, dtype=torch.float32, device=like.device)
 
@@ -1332,6 +1359,7 @@ def k_sum(x, scale=1.0, squared=False):
 def randn(shape, seed, offset, device):
     """Counter-based N(0,1) (Philox4x32-10 + Box-Muller) - replaces torch.randn for latents
     (utils/latent_utils.py:15) and per-layer noise (stylegan/architectures.py:115-116)."""
+    _gpu_device(device, 'randn')
     out = torch.empty(shape, dtype=torch.float32, device=device)
     check(_lib.lib().ganlab_randn_f32(_p(out), out.numel(), int(seed) & (2 ** 64 - 1), int(offset), _st()), 'randn')
     return out
@@ -1360,6 +1388,13 @@ def trunc_randn(shape, threshold, seed, offset, device):
 
 def randn_dev(shape, seed, base, delta, device):
     """``randn`` at stream position ``*base + delta`` (``base``: the step-scalar block of graphs.GraphedStep)."""
+    _gpu_device(device, 'randn_dev')
+    if not isinstance(base, torch.Tensor) or not base.is_cuda:
+        raise TypeError(f'gan_lab_amd.ops: randn_dev base must be the step-scalar block, a tensor on the GPU (got '
+                        f'{type(base).__name__}, {getattr(base, "device", None)}); the HIP path has no CPU fallback')
+    if not base.is_contiguous() or base.numel() * base.element_size() < 8:
+        raise ValueError(f'gan_lab_amd.ops: randn_dev base must be contiguous and hold the 8-byte stream position (got '
+                         f'{base.numel()} x {base.dtype}, strides {base.stride()})')
     out = torch.empty(shape, dtype=torch.float32, device=device)
     check(_lib.lib().ganlab_randn_dev_f32(_p(out), out.numel(), int(seed) & (2 ** 64 - 1), _p(base), int(delta), _st()),
           'randn_dev')
@@ -1977,13 +2012,25 @@ def lerp_rows(a, b, t):
     return out
 
 
+def _adam_operands(op, p, g, m, v):
+    named = [('p', p), ('g', g), ('m', m), ('v', v)]
+    for what, t in named:
+        _inplace(t, f'{op} {what}')
+    _same_numel(op, named)
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, wd, bc1, bc2):
+    _adam_operands('adam_step', p, g, m, v)
     check(_lib.lib().ganlab_adam_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, wd, bc1, bc2,
                                      _st()), 'adam')
 
 
 def adam_step_dev(p, g, m, v, scalars, beta1, beta2, eps, wd):
     """``adam_step`` with (lr, 1 - beta1^t, 1 - beta2^t) read from the three floats at ``scalars`` (a device pointer)."""
+    _adam_operands('adam_step_dev', p, g, m, v)
+    if isinstance(scalars, bool) or not isinstance(scalars, int) or scalars <= 0:
+        raise TypeError(f'gan_lab_amd.ops: adam_step_dev scalars must be a device address inside the step-scalar block (got '
+                        f'{scalars!r})')
     check(_lib.lib().ganlab_adam_dev_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), ctypes.c_void_p(scalars), beta1, beta2, eps,
                                          wd, _st()), 'adam_dev')
 
@@ -1995,6 +2042,10 @@ def set_step_scalars(block, rng_base, floats):
 
 
 def ewma_step(lagged, p, beta):
+    named = [('lagged', lagged), ('p', p)]
+    for what, t in named:
+        _inplace(t, f'ewma_step {what}')
+    _same_numel('ewma_step', named)
     check(_lib.lib().ganlab_ewma_f32(_p(lagged), _p(p), p.numel(), beta, _st()), 'ewma')
 
 
