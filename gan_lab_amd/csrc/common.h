@@ -129,6 +129,16 @@ __device__ __forceinline__ float4 gl_few_dot(const float4 (&xv)[4], const float*
   return a;
 }
 
+// The three-plane split of the split-product kernels (conv_x3.hip): v = h + m + l exactly, round-to-nearest at each cut.  One
+// definition for the weights (the pack functions below) and the activations (x3_common.h).
+struct gl_bf16x3 { __bf16 h, m, l; };
+__device__ __forceinline__ gl_bf16x3 gl_split3(float v) {
+  const __bf16 h = (__bf16)v;
+  const float r1 = v - (float)h;
+  const __bf16 m = (__bf16)r1;
+  return gl_bf16x3{h, m, (__bf16)(r1 - (float)m)};
+}
+
 // ---- conv_x3.hip packed weights: [co tile 64][k-step][plane 3][k-group 4][co 64][8] bf16, three planes that sum to the fp32
 // weight exactly.  k-step s of a 32-channel chunk: lane groups 0,1 = (tap_lo(s), half_lo(s)), 2,3 = (tap_hi(s), half_hi(s)) with
 //   steps 0-3: taps (0,1) (2,3) (4,5) (6,7) of half 0 | step 4: tap 8 of half 0 and of half 1 | steps 5-8: half 1.
@@ -146,14 +156,11 @@ __device__ __forceinline__ void gl_x3_pack_position(const float* __restrict__ w9
     const int kg = hi * 2 + g;
     float v = w9[flip ? 8 - t : t] * scale;
     asm volatile("" : "+v"(v));      // the ROUNDED product is what is split: no contraction of this multiply into v - h below
-    const __bf16 h = (__bf16)v;
-    const float r1 = v - (float)h;
-    const __bf16 m = (__bf16)r1;
-    const __bf16 l = (__bf16)(r1 - (float)m);
+    const gl_bf16x3 p = gl_split3(v);
     __bf16* base = out + (((long long)ct * steps + c * 9 + s) * (3 * 4 * 64)) * 8;
-    base[((0 * 4 + kg) * 64 + col) * 8 + j] = h;
-    base[((1 * 4 + kg) * 64 + col) * 8 + j] = m;
-    base[((2 * 4 + kg) * 64 + col) * 8 + j] = l;
+    base[((0 * 4 + kg) * 64 + col) * 8 + j] = p.h;
+    base[((1 * 4 + kg) * 64 + col) * 8 + j] = p.m;
+    base[((2 * 4 + kg) * 64 + col) * 8 + j] = p.l;
   }
 }
 
@@ -188,16 +195,13 @@ __device__ __forceinline__ void gl_x3_up_pack_position(const float* __restrict__
             }
           v = v * (up ? scale : 0.25f * scale);
           asm volatile("" : "+v"(v));
-          const __bf16 h = (__bf16)v;
-          const float r1 = v - (float)h;
-          const __bf16 mm = (__bf16)r1;
-          const __bf16 l = (__bf16)(r1 - (float)mm);
+          const gl_bf16x3 p = gl_split3(v);
           __bf16* base = out + (((c32 ? (long long)ct : (long long)ct * 2 + py) * nsteps + (ci >> 3)) * (3 * 4 * 128)) * 8;
           const int col = c32 ? py * 32 + (co & 31) : co & 63;
           const int kgq = ty * 2 + tx;
-          base[((0 * 4 + kgq) * 128 + px * 64 + col) * 8 + j] = h;
-          base[((1 * 4 + kgq) * 128 + px * 64 + col) * 8 + j] = mm;
-          base[((2 * 4 + kgq) * 128 + px * 64 + col) * 8 + j] = l;
+          base[((0 * 4 + kgq) * 128 + px * 64 + col) * 8 + j] = p.h;
+          base[((1 * 4 + kgq) * 128 + px * 64 + col) * 8 + j] = p.m;
+          base[((2 * 4 + kgq) * 128 + px * 64 + col) * 8 + j] = p.l;
         }
 }
 
@@ -230,14 +234,11 @@ __device__ __forceinline__ void gl_x3_down_pack_position(const float* __restrict
         for (int kx = 0; kx < 3; ++kx) v += gl_comb_s2(up, a, ky) * gl_comb_s2(up, b, kx) * k9[ky * 3 + kx];
       v = v * scale;
       asm volatile("" : "+v"(v));
-      const __bf16 h = (__bf16)v;
-      const float r1 = v - (float)h;
-      const __bf16 mm = (__bf16)r1;
-      const __bf16 l = (__bf16)(r1 - (float)mm);
+      const gl_bf16x3 p = gl_split3(v);
       __bf16* base = out + (((long long)ct * nsteps + q * 4 + a) * (3 * 4 * 128)) * 8;
-      base[((0 * 4 + b) * 128 + col) * 8 + j] = h;
-      base[((1 * 4 + b) * 128 + col) * 8 + j] = mm;
-      base[((2 * 4 + b) * 128 + col) * 8 + j] = l;
+      base[((0 * 4 + b) * 128 + col) * 8 + j] = p.h;
+      base[((1 * 4 + b) * 128 + col) * 8 + j] = p.m;
+      base[((2 * 4 + b) * 128 + col) * 8 + j] = p.l;
     }
 }
 

@@ -22,7 +22,8 @@
 //   steps 0-3: taps (0,1) (2,3) (4,5) (6,7) of half 0 | step 4: tap 8 of half 0 and of half 1 | steps 5-8: half 1.
 // The weights of TWO k-steps (a "stage", 24 KB) are double buffered; one barrier per stage (96 MFMAs per wave).
 // Staging is register-staged (buffer loads -> split -> ds_write), loads issued one to two stages ahead of their ds_write.
-#include "common.h"
+// The inline-asm loads, counted waits, MFMA / drain / settle and the split are x3_common.h's, shared with the other four files.
+#include "x3_common.h"
 
 #include <type_traits>
 
@@ -34,11 +35,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int X3_NT = 64;                      // output channels per workgroup
 constexpr int X3_PL = 336;                     // units (16 B) per (channel group, plane) of a half patch: 18 x 18 = 324, padded
                                                // to a multiple of 16 units so the k-groups stay 256 bytes apart (no conflicts)
@@ -47,8 +43,6 @@ constexpr int X3_WSTEP = 3 * 4 * X3_NT;        // units of one k-step of weights
 constexpr int X3_AOFF = 0, X3_WOFF = 3 * X3_HALF;
 constexpr int X3_WSTAGE = 2 * X3_WSTEP;         // two k-steps per barrier
 constexpr int X3_LDS = 3 * X3_HALF + 2 * X3_WSTAGE;  // 9120 units = 145,920 bytes
-
-__device__ __forceinline__ float x3_up(__bf16 b) { return (float)b; }
 
 // (tap, half) of lane groups 0,1 and 2,3 at step s of a 32-channel chunk
 __host__ __device__ constexpr int x3_tap_lo(int s) { return s < 4 ? 2 * s : s == 4 ? 8 : 2 * (s - 5); }
@@ -89,53 +83,16 @@ struct X3Args {
   double* spart;
 };
 
-// Activation loads are inline asm: hipcc neither sees them in its vmcnt bookkeeping (beside an LDS-DMA it waits vmcnt(0) in
-// front of the first use of any load it does see: the whole prefetch pipeline drained several times per stage) nor may recycle
-// their registers before x3_ld_wait, which is tied to them and counts the younger operations by hand.
-__device__ __forceinline__ u32x4 x3_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long b = reinterpret_cast<unsigned long long>(base);
-  return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32)) & 0xffffu,
-               (unsigned)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
-__device__ __forceinline__ void x3_ld(f32x4& d, const u32x4& rs, int voff, int soff) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(d) : "v"(voff), "s"(rs), "s"(soff));
-}
-template <int YOUNGER>
-__device__ __forceinline__ void x3_ld_wait(f32x4 (&a)[4]) {
-  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : "n"(YOUNGER));
-}
-template <int YOUNGER>
-__device__ __forceinline__ void x3_ld_wait(f32x4 (&a)[4], f32x4& s_, f32x4& t_) {
-  asm volatile("s_waitcnt vmcnt(%6)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(s_), "+v"(t_) : "n"(YOUNGER));
-}
-
 // kernel forms
 constexpr int X3_PLAIN = 0, X3_MASK = 1, X3_AFF = 2, X3_AFF_TAIL = 3;
 
-// The MFMAs are inline asm: accumulators pinned in the accumulation registers (tied operand, "a" class), issued in exactly
-// this order.  hipcc's hazard recogniser does not see through asm: an accumulator read by the vector ALU needs the matrix
-// pipe drained first (X3_MFMA_DRAIN before the chain dump and the epilogue).
-#define X3_MFMA(acc, a, b) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b))
-// drain / settle: wait states tied to a whole accumulator set (the set counts as rewritten by them, so neither the vector
-// ALU code in front of the block nor the MFMAs behind it can be scheduled across)
+// the accumulator set of a wave: operand list of X3_DRAIN / X3_SETTLE
 #define X3_ACC8(a) "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[2][0]), "+v"(a[2][1]), "+v"(a[3][0]), "+v"(a[3][1])
-#define X3_MFMA_DRAIN(a) asm volatile("s_nop 15\n\ts_nop 15" : X3_ACC8(a))
-#define X3_VALU_SETTLE(a) asm volatile("s_nop 7\n\ts_nop 7" : X3_ACC8(a))
 
 // tap offset (units) inside the halo patch
 __host__ __device__ constexpr int x3_toff(int tap) { return (tap / 3) * 18 + tap % 3; }
 
 struct X3Tile { int n, oy0, ox0, co_t; };
-
-// One barrier per stage, in its second k-step: everything a wave must have finished before it (its LDS-DMA of the next stage's
-// weights: all but the `YOUNGER` vector-memory operations issued after them; its ds_writes and ds_reads)
-template <int YOUNGER>
-__device__ __forceinline__ void x3_barrier() {
-  if constexpr (YOUNGER == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else if constexpr (YOUNGER == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  static_assert(YOUNGER == 0 || YOUNGER == 4 || YOUNGER == 6, "the activation staging issues four loads (six with the affine)");
-}
 
 // Persistent workgroups: workgroup b takes the tiles remap(b) + i * gridDim.x; the k-loop runs on across tiles (the next tile's
 // first two half patches and first weight stages are staged during the last stages of this one).
@@ -219,10 +176,7 @@ __global__ __launch_bounds__(512) void conv_x3_fwd_kernel(X3Args p) {
       float v = i == 0 ? ar[j].x : i == 1 ? ar[j].y : i == 2 ? ar[j].z : ar[j].w;
       if constexpr (AFF) v = fmaf(v, j == 0 ? a_sv.x : j == 1 ? a_sv.y : j == 2 ? a_sv.z : a_sv.w,
                                   j == 0 ? a_tv.x : j == 1 ? a_tv.y : j == 2 ? a_tv.z : a_tv.w);
-      h[j] = (__bf16)v;
-      const float r1 = v - x3_up(h[j]);
-      m[j] = (__bf16)r1;
-      l[j] = (__bf16)(r1 - x3_up(m[j]));
+      x3_split_lane(v, j, h, m, l);
     }
     *reinterpret_cast<u32x2*>(dst + i * 16) = __builtin_bit_cast(u32x2, h);
     *reinterpret_cast<u32x2*>(dst + i * 16 + X3_PL * 16) = __builtin_bit_cast(u32x2, m);
@@ -376,12 +330,12 @@ __global__ __launch_bounds__(512) void conv_x3_fwd_kernel(X3Args p) {
         }
         offA = offN;
         if (s18 == 8 || s18 == 17) {     // a 32-channel chunk is done: close its hi*hi chain
-          X3_MFMA_DRAIN(accH);
+          X3_DRAIN(X3_ACC8(accH));
 #pragma unroll
           for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int q = 0; q < 2; ++q) { accT[m][q] += accH[m][q]; accH[m][q] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-          X3_VALU_SETTLE(accH);
+          X3_SETTLE(X3_ACC8(accH));
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -392,7 +346,7 @@ __global__ __launch_bounds__(512) void conv_x3_fwd_kernel(X3Args p) {
 
     // ---- epilogue: T + S + bias, activation; lane = 4 consecutive pixels of one channel --------------------------------
     {
-      X3_MFMA_DRAIN(accS);
+      X3_DRAIN(X3_ACC8(accS));
       // the epilogue's arguments are read from the kernel-argument segment HERE: held in scalar registers across the k-loop
       // they cost a dozen spills
       // (a copy in registers, read once per tile by scalar loads: through the laundered pointer every use would be a flat load
@@ -467,7 +421,7 @@ __global__ __launch_bounds__(512) void conv_x3_fwd_kernel(X3Args p) {
           }
         }
       }
-      X3_VALU_SETTLE(accS);
+      X3_SETTLE(X3_ACC8(accS));
     }
     if (!nvalid) break;
     tile = ntile;
@@ -476,22 +430,25 @@ __global__ __launch_bounds__(512) void conv_x3_fwd_kernel(X3Args p) {
   }
 }
 
+// The launch's limits (buffer-resource ranges, 32-bit offsets, the tile count): the number of tiles, 0 past a limit
+long long x3_tiles(int N, int CI, int CO, int H, int W) {
+  const long long ntiles = (long long)N * (W / 16) * (H / 16) * (CO / X3_NT);
+  const bool fits = ntiles > 0 && ntiles <= 0x7fffffffLL && (long long)(CO / X3_NT) * (CI / 64 * 9) * X3_WSTAGE * 16 <= 0xffffffffLL &&
+                    (long long)CI * H * W * 4 <= 0x7fffffffLL && (long long)N * CI * 4 <= 0x7fffffffLL;
+  return fits ? ntiles : 0;
+}
+
 bool x3_ok(const ganlab_conv_geom* g, int dgrad) {
   if (g == nullptr || g->ks != 3 || g->pad != 1 || g->up || g->pool) return false;
   const int CI = dgrad ? g->Cout : g->Cin, CO = dgrad ? g->Cin : g->Cout;
   if (!(CI % 64 == 0 && CO % X3_NT == 0 && g->Hin % 16 == 0 && g->Win % 16 == 0 && g->N > 0)) return false;
-  // the launch's byte limits (buffer-resource ranges, 32-bit offsets): a geometry past them takes the exact kernels
-  const long long ntiles = (long long)g->N * (g->Win / 16) * (g->Hin / 16) * (CO / X3_NT);
-  return ntiles > 0 && ntiles <= 0x7fffffffLL && (long long)(CO / X3_NT) * (CI / 64 * 9) * X3_WSTAGE * 16 <= 0xffffffffLL &&
-         (long long)CI * g->Hin * g->Win * 4 <= 0x7fffffffLL && (long long)g->N * CI * 4 <= 0x7fffffffLL;
+  return x3_tiles(g->N, CI, CO, g->Hin, g->Win) > 0;       // a geometry past the limits takes the exact kernels
 }
 
 int x3_launch(int form, X3Args a, hipStream_t st) {
   a.tiles_x = a.W / 16; a.tiles_y = a.H / 16; a.tiles_co = a.CO / X3_NT;
-  const long long ntiles = (long long)a.N * a.tiles_x * a.tiles_y * a.tiles_co;
-  if (ntiles <= 0 || ntiles > 0x7fffffffLL || (long long)a.tiles_co * (a.CI / 64 * 9) * X3_WSTAGE * 16 > 0xffffffffLL ||
-      (long long)a.CI * a.H * a.W * 4 > 0x7fffffffLL || (long long)a.N * a.CI * 4 > 0x7fffffffLL)
-    return GANLAB_EINVAL;           // (x3_ok refuses these geometries already)
+  const long long ntiles = x3_tiles(a.N, a.CI, a.CO, a.H, a.W);
+  if (ntiles <= 0) return GANLAB_EINVAL;
   a.ntiles = (int)ntiles;
   const unsigned grid = (unsigned)(ntiles < 256 ? ntiles : 256);       // one workgroup per CU (146 KB of LDS), persistent
   switch (form) {

@@ -11,16 +11,11 @@
 // tap column b) x 8 input channels; the patch is staged in QUARTERS of 8 channels (4 parity planes of 9 x 17 units x 3 bf16
 // planes = 30 KB) that ring through three slots, four k-steps per quarter; the weights of ONE k-step (24 KB) per LDS-DMA stage,
 // double buffered: 141 KB of LDS, one barrier per k-step (48 MFMAs per wave).  Persistent workgroups, k-loop across tiles.
-#include "common.h"
+#include "x3_common.h"
 
 #include <type_traits>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int XD_NT = 128;                      // output channels per workgroup
 constexpr int XD_PP = 160;                      // units (16 B) of one parity plane of a quarter: 9 rows x 17 = 153, padded to 10 x 16
@@ -30,29 +25,8 @@ constexpr int XD_WSTEP = 3 * 4 * XD_NT;         // weights of a k-step: [plane][
 constexpr int XD_WOFF = 3 * XD_Q;
 constexpr int XD_LDS = 3 * XD_Q + 2 * XD_WSTEP; // 8832 units = 141,312 bytes
 
-#define XD_MFMA(acc, a, b) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b))
+// the accumulator set of a wave: operand list of X3_DRAIN / X3_SETTLE
 #define XD_ACC8(a) "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[0][2]), "+v"(a[0][3]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[1][2]), "+v"(a[1][3])
-#define XD_MFMA_DRAIN(a) asm volatile("s_nop 15\n\ts_nop 15" : XD_ACC8(a))
-#define XD_VALU_SETTLE(a) asm volatile("s_nop 7\n\ts_nop 7" : XD_ACC8(a))
-
-__device__ __forceinline__ u32x4 xd_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long b = reinterpret_cast<unsigned long long>(base);
-  return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32)) & 0xffffu,
-               (unsigned)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
-__device__ __forceinline__ void xd_ld(f32x4& d, const u32x4& rs, int voff, int soff) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(d) : "v"(voff), "s"(rs), "s"(soff));
-}
-template <int YOUNGER>
-__device__ __forceinline__ void xd_ld_wait(f32x4 (&a)[4]) {
-  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : "n"(YOUNGER));
-}
-template <int YOUNGER>
-__device__ __forceinline__ void xd_barrier() {       // this wave's LDS-DMA of the next k-step's weights has landed: all but the
-  if constexpr (YOUNGER == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");      // YOUNGER loads behind it
-  else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  static_assert(YOUNGER == 0 || YOUNGER == 4, "a quarter's staging issues four loads");
-}
 
 struct XDArgs {
   const float* x;           // (N, CI, 2 Hl, 2 Wl)
@@ -102,7 +76,7 @@ __global__ __launch_bounds__(512) void conv_x3_down_kernel(XDArgs p) {
   const int cstride = plane * 4;
   f32x4 arA[4], arB[4];
   auto a_load_to = [&](f32x4 (&ar)[4], const XDTile& c, int q) {       // channels 8 q + 4 cq + j
-    const u32x4 rs = xd_rsrc(p.x + (long long)c.n * p.CI * plane, (unsigned)((long long)p.CI * plane * 4));
+    const u32x4 rs = x3_rsrc(p.x + (long long)c.n * p.CI * plane, (unsigned)((long long)p.CI * plane * 4));
     int r = a_r;
     asm volatile("" : "+v"(r));
     const int iy = 2 * c.oy0 - 1 + r, ix = 2 * c.ox0 - 4 + 4 * a_cg;
@@ -110,7 +84,7 @@ __global__ __launch_bounds__(512) void conv_x3_down_kernel(XDArgs p) {
     const int off = ok ? ((a_cq * 4) * plane + iy * Wi + ix) * 4 : (int)0x80000000;
     const int soff = q * 8 * plane * 4;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) xd_ld(ar[j], rs, off + j * cstride, soff);
+    for (int j = 0; j < 4; ++j) x3_ld(ar[j], rs, off + j * cstride, soff);
   };
   // element i (one input pixel, 4 channels) of the item -> its parity plane: patch column c = 4 cg - 3 + i; row class r & 1,
   // row index r >> 1; column class c & 1, column index c >> 1; unit = ((rowclass * 2 + colclass) * XD_PP + (r >> 1) * 17 + (c >> 1))
@@ -122,13 +96,7 @@ __global__ __launch_bounds__(512) void conv_x3_down_kernel(XDArgs p) {
     if (c < 0 || c > 33) return;
     bf16x4 h, m, l;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float v = ar[j][i];
-      h[j] = (__bf16)v;
-      const float r1 = v - (float)h[j];
-      m[j] = (__bf16)r1;
-      l[j] = (__bf16)(r1 - (float)m[j]);
-    }
+    for (int j = 0; j < 4; ++j) x3_split_lane(ar[j][i], j, h, m, l);
     const int unit = slot * XD_Q + ((r & 1) * 2 + (c & 1)) * XD_PP + (r >> 1) * 17 + (c >> 1);
     unsigned char* dst = reinterpret_cast<unsigned char*>(lds + unit) + a_cq * 8;
     *reinterpret_cast<u32x2*>(dst) = __builtin_bit_cast(u32x2, h);
@@ -139,7 +107,7 @@ __global__ __launch_bounds__(512) void conv_x3_down_kernel(XDArgs p) {
   auto a_store_px = [&](int set, int slot, int i) { if (set == 0) a_store_from(arA, slot, i); else a_store_from(arB, slot, i); };
   auto a_wait = [&](int set, auto younger) {
     constexpr int Y = decltype(younger)::value;
-    if (set == 0) xd_ld_wait<Y>(arA); else xd_ld_wait<Y>(arB);
+    if (set == 0) x3_ld_wait<Y>(arA); else x3_ld_wait<Y>(arB);
   };
 
   // ---- weights: LDS-DMA, one k-step image (24 pieces of 1 KB, 3 per wave) ---------------------------------------------------
@@ -161,8 +129,8 @@ __global__ __launch_bounds__(512) void conv_x3_down_kernel(XDArgs p) {
     for (int nn = 0; nn < 4; ++nn) {
       accS[m][nn] = f32x4{0.f, 0.f, 0.f, 0.f}; accH[m][nn] = f32x4{0.f, 0.f, 0.f, 0.f}; accT[m][nn] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-  XD_VALU_SETTLE(accS);
-  XD_VALU_SETTLE(accH);
+  X3_SETTLE(XD_ACC8(accS));
+  X3_SETTLE(XD_ACC8(accH));
 
   // lane's patch unit: column class kg & 1, column offset kg >> 1; rows 2 wm + m
   const int laneA = (kg & 1) * XD_PP + (2 * wm) * 17 + l16 + (kg >> 1);
@@ -192,7 +160,7 @@ __global__ __launch_bounds__(512) void conv_x3_down_kernel(XDArgs p) {
   a_wait(0, std::integral_constant<int, 0>{});
 #pragma unroll
   for (int i = 0; i < 4; ++i) { a_store_px(0, sa, i); __builtin_amdgcn_sched_barrier(0); }
-  xd_barrier<0>();
+  x3_barrier<0>();
   w_dma(cur, 1, 1);
   __builtin_amdgcn_sched_barrier(0);
   a_load(1, cur, 1);
@@ -220,7 +188,7 @@ __global__ __launch_bounds__(512) void conv_x3_down_kernel(XDArgs p) {
           if (nn < 3) b_frags(buf, nn + 1, (nn + 1) & 1);
           if (nn == 3) {
             // ---- the step's barrier: the next k-step's weights are visible behind it; this step's buffer is free --------------
-            if (a == 1 && (qq + 2 < nq || nvalid)) xd_barrier<4>(); else xd_barrier<0>();       // (quarter qq + 2's loads: issued in step a = 0)
+            if (a == 1 && (qq + 2 < nq || nvalid)) x3_barrier<4>(); else x3_barrier<0>();       // (quarter qq + 2's loads: issued in step a = 0)
             {
               const int st2 = qq * 4 + a + 2;          // weights two k-steps on
               if (st2 < nsteps) w_dma(cur, st2, buf);
@@ -236,12 +204,12 @@ __global__ __launch_bounds__(512) void conv_x3_down_kernel(XDArgs p) {
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int m = 0; m < 2; ++m) {
-            XD_MFMA(accS[m][nn], aF[cs][m][2], bF[nn & 1][0]);
-            XD_MFMA(accS[m][nn], aF[cs][m][0], bF[nn & 1][2]);
-            XD_MFMA(accS[m][nn], aF[cs][m][1], bF[nn & 1][1]);
-            XD_MFMA(accS[m][nn], aF[cs][m][1], bF[nn & 1][0]);
-            XD_MFMA(accS[m][nn], aF[cs][m][0], bF[nn & 1][1]);
-            XD_MFMA(accH[m][nn], aF[cs][m][0], bF[nn & 1][0]);
+            X3_MFMA(accS[m][nn], aF[cs][m][2], bF[nn & 1][0]);
+            X3_MFMA(accS[m][nn], aF[cs][m][0], bF[nn & 1][2]);
+            X3_MFMA(accS[m][nn], aF[cs][m][1], bF[nn & 1][1]);
+            X3_MFMA(accS[m][nn], aF[cs][m][1], bF[nn & 1][0]);
+            X3_MFMA(accS[m][nn], aF[cs][m][0], bF[nn & 1][1]);
+            X3_MFMA(accH[m][nn], aF[cs][m][0], bF[nn & 1][0]);
           }
           __builtin_amdgcn_sched_barrier(0);
           if (nn == 1 && next_q) {
@@ -256,18 +224,18 @@ __global__ __launch_bounds__(512) void conv_x3_down_kernel(XDArgs p) {
       }
       gs += 8;
       // 16 channels x 16 taps = 256 terms: close the hi*hi chain
-      XD_MFMA_DRAIN(accH);
+      X3_DRAIN(XD_ACC8(accH));
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int nn = 0; nn < 4; ++nn) { accT[m][nn] += accH[m][nn]; accH[m][nn] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-      XD_VALU_SETTLE(accH);
+      X3_SETTLE(XD_ACC8(accH));
       __builtin_amdgcn_sched_barrier(0);
     }
 
     // ---- epilogue ---------------------------------------------------------------------------------------------------------------
     {
-      XD_MFMA_DRAIN(accS);
+      X3_DRAIN(XD_ACC8(accS));
       typedef const __attribute__((address_space(4))) XDArgs* XDArgsK;
       unsigned long long kpi = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
       asm volatile("" : "+s"(kpi));
@@ -295,7 +263,7 @@ __global__ __launch_bounds__(512) void conv_x3_down_kernel(XDArgs p) {
           accS[m][nn] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
       }
-      XD_VALU_SETTLE(accS);
+      X3_SETTLE(XD_ACC8(accS));
     }
     if (!nvalid) break;
     tile = ntile;
@@ -316,6 +284,14 @@ __global__ void x3_down_pack_kernel(const float* __restrict__ w, __bf16* __restr
   gl_x3_down_pack_position(w9, up, scale, out, CI, ci, co);
 }
 
+// The launch's limits (buffer-resource range, 32-bit offsets, the tile count): the number of tiles, 0 past a limit
+long long xd_tiles(int N, int CI, int CO, int Hl, int Wl) {
+  const long long ntiles = (long long)N * (Wl / 16) * (Hl / 8) * (CO / XD_NT);
+  const bool fits = ntiles > 0 && ntiles <= 0x7fffffffLL && (long long)(CO / XD_NT) * (CI / 8 * 4) * XD_WSTEP * 16 <= 0xffffffffLL &&
+                    (long long)CI * Hl * Wl * 16 <= 0x7fffffffLL;
+  return fits ? ntiles : 0;
+}
+
 bool xd_ok(const ganlab_conv_geom* g, int dgrad) {
   if (g == nullptr || g->ks != 3 || g->pad != 1 || g->N <= 0) return false;
   if (dgrad ? !(g->up == 1 && g->pool == 0) : !(g->pool == 1 && g->up == 0)) return false;
@@ -323,11 +299,8 @@ bool xd_ok(const ganlab_conv_geom* g, int dgrad) {
   // low resolution: the pooled layer's output; the up layer's INPUT
   if (!dgrad && ((g->Hin | g->Win) & 1)) return false;
   const int Hl = dgrad ? g->Hin : g->Hin / 2, Wl = dgrad ? g->Win : g->Win / 2;
-  if ((long long)CI * Hl * Wl * 16 > 0x7fffffffLL) return false;
   if (!(CI % 16 == 0 && CO % XD_NT == 0 && Hl % 8 == 0 && Wl % 16 == 0)) return false;
-  // xd_launch's limits: tile count, weight image
-  const long long ntiles = (long long)g->N * (Wl / 16) * (Hl / 8) * (CO / XD_NT);
-  return ntiles > 0 && ntiles <= 0x7fffffffLL && (long long)(CO / XD_NT) * (CI / 8 * 4) * XD_WSTEP * 16 <= 0xffffffffLL;
+  return xd_tiles(g->N, CI, CO, Hl, Wl) > 0;
 }
 
 int xd_launch(const float* x, const void* wp, const float* bias, float* y, int N, int CI, int CO, int Hl, int Wl, float bias_scale,
@@ -337,8 +310,8 @@ int xd_launch(const float* x, const void* wp, const float* bias, float* y, int N
   a.N = N; a.CI = CI; a.CO = CO; a.Hl = Hl; a.Wl = Wl;
   a.tiles_x = Wl / 16; a.tiles_y = Hl / 8; a.tiles_co = CO / XD_NT;
   a.bias_scale = bias_scale; a.slope = slope; a.act = act;
-  const long long ntiles = (long long)N * a.tiles_x * a.tiles_y * a.tiles_co;
-  if (ntiles <= 0 || ntiles > 0x7fffffffLL || (long long)a.tiles_co * (CI / 8 * 4) * XD_WSTEP * 16 > 0xffffffffLL) return GANLAB_EINVAL;
+  const long long ntiles = xd_tiles(N, CI, CO, Hl, Wl);
+  if (ntiles <= 0) return GANLAB_EINVAL;
   a.ntiles = (int)ntiles;
   const unsigned grid = (unsigned)(ntiles < 256 ? ntiles : 256);
   GL_LAUNCH(conv_x3_down_kernel, dim3(grid), dim3(512), 0, st, a);

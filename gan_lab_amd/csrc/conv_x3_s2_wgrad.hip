@@ -26,14 +26,9 @@
 // Staging: threads 0..255 build VP, 256..511 VQ (item = one channel's 8 high pixels of two rows + a halo dword), all 512 one
 // L item; loads two k-steps ahead of their stores (inline asm, hand-counted waits - extra memory operations only make a
 // counted wait stricter).  One barrier per k-step.
-#include "common.h"
+#include "x3_common.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int XS_CL = 64, XS_CB = 32;
 // ablation builds: 1 no chain closing, 2 no matrix work, 4 no staging (loads only), 8 no global loads, 16 no fragment reads,
@@ -56,28 +51,9 @@ constexpr int XS_LDS = XS_SP + XS_VROW;            // 8640 units = 138,240 bytes
 constexpr int XS_SLOT = XS_CL * XS_CB * 9;         // floats of one partial slot: [wave 8][tap 9][lane 64][4]
 constexpr int XS_LOADS = 7;                        // vector-memory loads per thread and k-step
 
-#define XS_MFMA(acc, a, b) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b))
+// an accumulator set of a wave: operand list of X3_DRAIN / X3_SETTLE
 #define XS_ACC3(a, o) "+v"(a[o]), "+v"(a[o + 1]), "+v"(a[o + 2])
 #define XS_ACC9(a) XS_ACC3(a, 0), XS_ACC3(a, 3), XS_ACC3(a, 6)
-#define XS_MFMA_DRAIN9(a) asm volatile("s_nop 15\n\ts_nop 15" : XS_ACC9(a))
-#define XS_VALU_SETTLE9(a) asm volatile("s_nop 7\n\ts_nop 7" : XS_ACC9(a))
-#define XS_MFMA_DRAIN3(a, o) asm volatile("s_nop 15\n\ts_nop 15" : XS_ACC3(a, o))
-#define XS_VALU_SETTLE3(a, o) asm volatile("s_nop 7\n\ts_nop 7" : XS_ACC3(a, o))
-
-__device__ __forceinline__ u32x4 xs_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long b = reinterpret_cast<unsigned long long>(base);
-  return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32)) & 0xffffu,
-               (unsigned)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
-__device__ __forceinline__ void xs_ld(f32x4& d, const u32x4& rs, int voff) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(d) : "v"(voff), "s"(rs) : "memory");
-}
-__device__ __forceinline__ void xs_ld16(f32x4& d, const u32x4& rs, int voff) {       // ... the next 16 bytes
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:16" : "=v"(d) : "v"(voff), "s"(rs) : "memory");
-}
-__device__ __forceinline__ void xs_ld1(float& d, const u32x4& rs, int voff) {
-  asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=v"(d) : "v"(voff), "s"(rs) : "memory");
-}
 
 struct XSArgs {
   const float* low;         // [N][CL][Hl][Wl]
@@ -100,13 +76,14 @@ __device__ __forceinline__ void xs_wait(XSSet& s) {
   asm volatile("s_waitcnt vmcnt(%7)" : "+v"(s.a0), "+v"(s.a1), "+v"(s.b0), "+v"(s.b1), "+v"(s.lv), "+v"(s.ha), "+v"(s.hb) : "n"(YOUNGER));
 }
 
-// split four values into planes (8 bytes each): two values per v_cvt_pk_bf16_f32 (round to nearest even, like the scalar cast)
+// x3_split4's planes by another instruction sequence: two values per v_cvt_pk_bf16_f32 (round to nearest even, like the scalar
+// cast).  Kept apart from x3_split4: the same bits, but not the same instruction stream.
 __device__ __forceinline__ unsigned xs_cvt_pk(float a, float b) {
   unsigned r;
   asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
-__device__ __forceinline__ void xs_split4(const f32x4& v, u32x2& h, u32x2& m, u32x2& l) {
+__device__ __forceinline__ void xs_split4_pk(const f32x4& v, u32x2& h, u32x2& m, u32x2& l) {
   float r[4], q[4];
   h[0] = xs_cvt_pk(v[0], v[1]); h[1] = xs_cvt_pk(v[2], v[3]);
 #pragma unroll
@@ -139,10 +116,10 @@ __global__ __launch_bounds__(512) void conv_x3_s2_wgrad_kernel(XSArgs p) {
   const int lplane = p.Hl * p.Wl, W2 = 2 * p.Wl;
 
   const unsigned lbytes = (unsigned)((long long)p.N * p.CL * lplane * 4), hbytes = (unsigned)((long long)p.N * p.CB * lplane * 16);
-  const u32x4 rs_l = xs_rsrc(p.low, lbytes);
-  const u32x4 rs_h = xs_rsrc(p.high, hbytes);
+  const u32x4 rs_l = x3_rsrc(p.low, lbytes);
+  const u32x4 rs_h = x3_rsrc(p.high, hbytes);
   float* const twave = p.part + ((long long)pair * p.splits + split) * XS_SLOT + wv * 9 * 256;   // this wave's nine T tiles
-  const u32x4 rs_t = xs_rsrc(twave, 9 * 1024);                                                   // tile t of this lane: t * 1024 + lane * 16
+  const u32x4 rs_t = x3_rsrc(twave, 9 * 1024);                                                   // tile t of this lane: t * 1024 + lane * 16
   auto t_store = [&](const f32x4& v, int t) {
     // (a store of more than 8 bytes reads its data registers over several cycles: the wait states behind it keep the next
     // instruction - the compiler does not see this store - from overwriting them; without: elements 2, 3 of lanes 12..15 of
@@ -208,23 +185,20 @@ __global__ __launch_bounds__(512) void conv_x3_s2_wgrad_kernel(XSArgs p) {
     const f32x4 qv{v0[1] + v0[2], v0[3] + v1[0], v1[1] + v1[2], v1[3] + e8};
     u32x2 h, m, l;
     unsigned char* d = reinterpret_cast<unsigned char*>(lds + base) + p_dst;
-    xs_split4(pv, h, m, l);
+    xs_split4_pk(pv, h, m, l);
     *reinterpret_cast<u32x2*>(d) = h;
     *reinterpret_cast<u32x2*>(d + XS_VPL * 16) = m;
     *reinterpret_cast<u32x2*>(d + 2 * XS_VPL * 16) = l;
-    xs_split4(qv, h, m, l);
+    xs_split4_pk(qv, h, m, l);
     d += (XS_VARR + 1) * 16;
     *reinterpret_cast<u32x2*>(d) = h;
     *reinterpret_cast<u32x2*>(d + XS_VPL * 16) = m;
     *reinterpret_cast<u32x2*>(d + 2 * XS_VPL * 16) = l;
     if (b_q == 0) {                               // Q[x0 - 1]: the last bf16 of the halo unit in front of the row
       const float qm = vh + v0[0];
-      const __bf16 hh = (__bf16)qm;
-      const float r1 = qm - (float)hh;
-      const __bf16 mm = (__bf16)r1;
-      const __bf16 ll = (__bf16)(r1 - (float)mm);
+      const gl_bf16x3 s = gl_split3(qm);
       __bf16* dh = reinterpret_cast<__bf16*>(d - 16) + 7;
-      dh[0] = hh; dh[XS_VPL * 8] = mm; dh[2 * XS_VPL * 8] = ll;
+      dh[0] = s.h; dh[XS_VPL * 8] = s.m; dh[2 * XS_VPL * 8] = s.l;
     }
   };
   // k-step g's images: L -> buffer g & 1;  VP -> buffer g & 1 (and, first row of a strip, SP = high row 0 alone);  VQ -> slot g & 3
@@ -241,7 +215,7 @@ __global__ __launch_bounds__(512) void conv_x3_s2_wgrad_kernel(XSArgs p) {
       for (int j = 0; j < 4; ++j) v[j] = (g < F && thrL != OOB) ? fmaf(v[j], a_s, a_t) : 0.f;      // (pixels that do not exist stay zero)
     }
     u32x2 h, m, l;
-    xs_split4(v, h, m, l);
+    xs_split4_pk(v, h, m, l);
     unsigned char* d = reinterpret_cast<unsigned char*>(lds + (u & 1) * XS_LROW) + l_dst;
     *reinterpret_cast<u32x2*>(d) = h;
     *reinterpret_cast<u32x2*>(d + XS_LPL * 16) = m;
@@ -253,8 +227,8 @@ __global__ __launch_bounds__(512) void conv_x3_s2_wgrad_kernel(XSArgs p) {
   f32x4 accS[9], accH[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t) { accS[t] = f32x4{0.f, 0.f, 0.f, 0.f}; accH[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  XS_VALU_SETTLE9(accS);
-  XS_VALU_SETTLE9(accH);
+  X3_SETTLE(XS_ACC9(accS));
+  X3_SETTLE(XS_ACC9(accH));
 
   // fragment addresses (units)
   const int laneL = (wl * 16 + l16) * XS_P + kg;
@@ -291,8 +265,8 @@ __global__ __launch_bounds__(512) void conv_x3_s2_wgrad_kernel(XSArgs p) {
 // (alternating the P and Q taps' accumulators - no MFMA behind the one that wrote its accumulator, none of hipcc's s_nop between
 // them - was measured 1 % SLOWER here and 4 % slower in conv_x3.hip: dependent MFMAs issue back to back at full rate)
 #define XS_TAP(t, A, Bf)                                                                                      \
-  XS_MFMA(accS[t], A[2], Bf[0]); XS_MFMA(accS[t], A[0], Bf[2]); XS_MFMA(accS[t], A[1], Bf[1]);                \
-  XS_MFMA(accS[t], A[1], Bf[0]); XS_MFMA(accS[t], A[0], Bf[1]); XS_MFMA(accH[t], A[0], Bf[0])
+  X3_MFMA(accS[t], A[2], Bf[0]); X3_MFMA(accS[t], A[0], Bf[2]); X3_MFMA(accS[t], A[1], Bf[1]);                \
+  X3_MFMA(accS[t], A[1], Bf[0]); X3_MFMA(accS[t], A[0], Bf[1]); X3_MFMA(accH[t], A[0], Bf[0])
 #define XS_GROUP(ty, A, set) do {                                                  \
     XS_TAP(3 * (ty) + 1, A, bP[set]); XS_TAP(3 * (ty) + 2, A, bQ[set]);            \
     __builtin_amdgcn_sched_barrier(0);                                             \
@@ -334,7 +308,7 @@ __global__ __launch_bounds__(512) void conv_x3_s2_wgrad_kernel(XSArgs p) {
     const int y = f & hmask;
     const int ph = (XS_EXP & 1) ? -1 : (f & 31) - 23;      // >= 0: tap ph closes its hi*hi chain in this k-step
     f32x4 tq;
-    if (ph >= 0) xs_ld(tq, rs_t, ph * 1024 + lane * 16);
+    if (ph >= 0) x3_ld(tq, rs_t, ph * 1024 + lane * 16);
     // staging: the images of k-step f + 1 (loads requested two k-steps ago; behind them the seven of the k-step before - and, in
     // a closing k-step, tq's: a stricter wait, nothing else), then the requests of k-step f + 3
     auto stage = [&]() {
@@ -365,10 +339,10 @@ __global__ __launch_bounds__(512) void conv_x3_s2_wgrad_kernel(XSArgs p) {
       asm volatile("s_waitcnt vmcnt(%1)" : "+v"(tq) : "n"(XS_LOADS));
       auto close1 = [&](auto O) {
         constexpr int o = decltype(O)::value;
-        asm volatile("s_nop 15\n\ts_nop 15" : "+v"(accH[o]));
+        X3_DRAIN("+v"(accH[o]));
         tq += accH[o];
         accH[o] = f32x4{0.f, 0.f, 0.f, 0.f};
-        asm volatile("s_nop 7\n\ts_nop 7" : "+v"(accH[o]));
+        X3_SETTLE("+v"(accH[o]));
         t_store(tq, o);
       };
       switch (ph) {
@@ -394,12 +368,12 @@ __global__ __launch_bounds__(512) void conv_x3_s2_wgrad_kernel(XSArgs p) {
 
   // ---- this workgroup's partial sums, in place: T + H + S ---------------------------------------------------------------------
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  XS_MFMA_DRAIN9(accS);
-  XS_MFMA_DRAIN9(accH);
+  X3_DRAIN(XS_ACC9(accS));
+  X3_DRAIN(XS_ACC9(accH));
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
     f32x4 v;
-    xs_ld(v, rs_t, t * 1024 + lane * 16);
+    x3_ld(v, rs_t, t * 1024 + lane * 16);
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(v));
     t_store(v + accH[t] + accS[t], t);
   }

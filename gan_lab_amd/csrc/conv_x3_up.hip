@@ -11,16 +11,11 @@
 // (ty, tx)) x 8 input channels; the patch (10 x 18 units) is staged in halves of 16 channels = 2 k-steps that ring through three
 // slots; the operand fragments of column parity px = 1 are those of px = 0 one unit to the right.  Weights: one k-step image
 // [plane][tap][px][co 64] (24 KB) per LDS-DMA stage, double buffered; one barrier per k-step (48 MFMAs per wave).
-#include "common.h"
+#include "x3_common.h"
 
 #include <type_traits>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int XU_CO = 64;                       // output channels per workgroup (x 2 column parities = 128 GEMM columns)
 constexpr int XU_PL = 192;                      // units (16 B) of one bf16 plane of an 8-channel group: 10 rows x 18 = 180, padded
@@ -30,34 +25,8 @@ constexpr int XU_WSTEP = 3 * 4 * 128;           // weights of a k-step: [plane][
 constexpr int XU_WOFF = 3 * XU_HALF;
 constexpr int XU_LDS = 3 * XU_HALF + 2 * XU_WSTEP;   // 6528 units = 104,448 bytes
 
-#define XU_MFMA(acc, a, b) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b))
+// the accumulator set of a wave: operand list of X3_DRAIN / X3_SETTLE
 #define XU_ACC8(a) "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[0][2]), "+v"(a[0][3]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[1][2]), "+v"(a[1][3])
-#define XU_MFMA_DRAIN(a) asm volatile("s_nop 15\n\ts_nop 15" : XU_ACC8(a))
-#define XU_VALU_SETTLE(a) asm volatile("s_nop 7\n\ts_nop 7" : XU_ACC8(a))
-
-__device__ __forceinline__ u32x4 xu_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long b = reinterpret_cast<unsigned long long>(base);
-  return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32)) & 0xffffu,
-               (unsigned)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
-__device__ __forceinline__ void xu_ld(f32x4& d, const u32x4& rs, int voff, int soff) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(d) : "v"(voff), "s"(rs), "s"(soff));
-}
-template <int YOUNGER>
-__device__ __forceinline__ void xu_ld_wait(f32x4 (&a)[4]) {
-  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : "n"(YOUNGER));
-}
-template <int YOUNGER>
-__device__ __forceinline__ void xu_ld_wait(f32x4 (&a)[4], f32x4& s_, f32x4& t_) {
-  asm volatile("s_waitcnt vmcnt(%6)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(s_), "+v"(t_) : "n"(YOUNGER));
-}
-template <int YOUNGER>
-__device__ __forceinline__ void xu_barrier() {
-  if constexpr (YOUNGER == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else if constexpr (YOUNGER == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  static_assert(YOUNGER == 0 || YOUNGER == 4 || YOUNGER == 6, "a half's staging issues four loads (six with the affine)");
-}
 
 struct XUArgs {
   const float* x;           // (N, CI, Hl, Wl)
@@ -115,7 +84,7 @@ __global__ __launch_bounds__(512) void conv_x3_up_kernel(XUArgs p) {
   const int cstride = plane * 4;
   f32x4 arA[4], arB[4], svA, tvA, svB, tvB;
   auto a_load_to = [&](f32x4 (&ar)[4], f32x4& a_sv, f32x4& a_tv, const XUTile& c, int half) {     // channels 16 half + 8 g + 4 cq + j
-    const u32x4 rs = xu_rsrc(p.x + (long long)c.n * p.CI * plane, (unsigned)((long long)p.CI * plane * 4));
+    const u32x4 rs = x3_rsrc(p.x + (long long)c.n * p.CI * plane, (unsigned)((long long)p.CI * plane * 4));
     int r = a_r;
     asm volatile("" : "+v"(r));
     const int iy = c.oy0 - 1 + r, ix = c.ox0 - 4 + 4 * a_cg;
@@ -123,14 +92,14 @@ __global__ __launch_bounds__(512) void conv_x3_up_kernel(XUArgs p) {
     const int off = ok ? ((a_gq * 4) * plane + iy * p.Wl + ix) * 4 : (int)0x80000000;
     const int soff = half * 16 * plane * 4;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) xu_ld(ar[j], rs, off + j * cstride, soff);
+    for (int j = 0; j < 4; ++j) x3_ld(ar[j], rs, off + j * cstride, soff);
     if constexpr (AFF) {       // an item outside the image reads zeros for s and t as well: 0 * 0 + 0 keeps the padding zero
       const unsigned tab = (unsigned)((long long)p.N * p.CI * 4);
-      const u32x4 rss = xu_rsrc(p.aff_s, tab), rst = xu_rsrc(p.aff_t, tab);
+      const u32x4 rss = x3_rsrc(p.aff_s, tab), rst = x3_rsrc(p.aff_t, tab);
       const int o = ok ? a_gq * 16 : (int)0x80000000;
       const int so = (c.n * p.CI + half * 16) * 4;
-      xu_ld(a_sv, rss, o, so);
-      xu_ld(a_tv, rst, o, so);
+      x3_ld(a_sv, rss, o, so);
+      x3_ld(a_tv, rst, o, so);
     }
   };
   auto a_store_from = [&](const f32x4 (&ar)[4], const f32x4& a_sv, const f32x4& a_tv, int slot, int i) {
@@ -144,10 +113,7 @@ __global__ __launch_bounds__(512) void conv_x3_up_kernel(XUArgs p) {
     for (int j = 0; j < 4; ++j) {
       float v = ar[j][i];
       if constexpr (AFF) v = fmaf(v, a_sv[j], a_tv[j]);
-      h[j] = (__bf16)v;
-      const float r1 = v - (float)h[j];
-      m[j] = (__bf16)r1;
-      l[j] = (__bf16)(r1 - (float)m[j]);
+      x3_split_lane(v, j, h, m, l);
     }
     const int unit = slot * XU_HALF + (a_gq >> 1) * XU_G + r * 18 + c;
     unsigned char* dst = reinterpret_cast<unsigned char*>(lds + unit) + (a_gq & 1) * 8;
@@ -163,8 +129,8 @@ __global__ __launch_bounds__(512) void conv_x3_up_kernel(XUArgs p) {
   };
   auto a_wait = [&](int set, auto younger) {
     constexpr int Y = decltype(younger)::value;
-    if (set == 0) { if constexpr (AFF) xu_ld_wait<Y>(arA, svA, tvA); else xu_ld_wait<Y>(arA); }
-    else { if constexpr (AFF) xu_ld_wait<Y>(arB, svB, tvB); else xu_ld_wait<Y>(arB); }
+    if (set == 0) { if constexpr (AFF) x3_ld_wait<Y>(arA, svA, tvA); else x3_ld_wait<Y>(arA); }
+    else { if constexpr (AFF) x3_ld_wait<Y>(arB, svB, tvB); else x3_ld_wait<Y>(arB); }
   };
 
   // ---- weights: LDS-DMA, one k-step image per stage ----------------------------------------------------------------------------
@@ -185,8 +151,8 @@ __global__ __launch_bounds__(512) void conv_x3_up_kernel(XUArgs p) {
     for (int nn = 0; nn < 4; ++nn) {
       accS[m][nn] = f32x4{0.f, 0.f, 0.f, 0.f}; accH[m][nn] = f32x4{0.f, 0.f, 0.f, 0.f}; accT[m][nn] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-  XU_VALU_SETTLE(accS);
-  XU_VALU_SETTLE(accH);
+  X3_SETTLE(XU_ACC8(accS));
+  X3_SETTLE(XU_ACC8(accH));
 
   // lane's patch unit for column parity 0: tap (ty, tx) = (kg >> 1, kg & 1); rows 2 wm + m + py + ty, columns l16 + px + tx
   const int laneA = (2 * wm + (kg >> 1) + (C32 ? wn : 0)) * 18 + l16 + (kg & 1);
@@ -217,7 +183,7 @@ __global__ __launch_bounds__(512) void conv_x3_up_kernel(XUArgs p) {
   a_wait(0, std::integral_constant<int, 0>{});
 #pragma unroll
   for (int i = 0; i < 4; ++i) { a_store_px(0, sa, i); __builtin_amdgcn_sched_barrier(0); }
-  xu_barrier<0>();
+  x3_barrier<0>();
   w_dma(cur, 1, 1);
   __builtin_amdgcn_sched_barrier(0);
   a_load(1, cur, 1);
@@ -249,7 +215,7 @@ __global__ __launch_bounds__(512) void conv_x3_up_kernel(XUArgs p) {
           if (nn == 0) a_frags(offA, 1);                   // column parity 1: one unit to the right
           if (nn == 3) {
             // ---- the step's barrier: the next k-step's weights are visible behind it; this step's buffer is free --------------
-            if (g == 1 && (2 * (h + 2) < nsteps || nvalid)) xu_barrier<NLOADS>(); else xu_barrier<0>();   // (half h + 2's loads: step g = 0)
+            if (g == 1 && (2 * (h + 2) < nsteps || nvalid)) x3_barrier<NLOADS>(); else x3_barrier<0>();   // (half h + 2's loads: step g = 0)
             {
               const int st2 = st + 2;                      // weights two k-steps on
               if (st2 < nsteps) w_dma(cur, st2, buf);
@@ -265,12 +231,12 @@ __global__ __launch_bounds__(512) void conv_x3_up_kernel(XUArgs p) {
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int m = 0; m < 2; ++m) {
-            XU_MFMA(accS[m][nn], aF[nn >> 1][m][2], bF[nn & 1][0]);
-            XU_MFMA(accS[m][nn], aF[nn >> 1][m][0], bF[nn & 1][2]);
-            XU_MFMA(accS[m][nn], aF[nn >> 1][m][1], bF[nn & 1][1]);
-            XU_MFMA(accS[m][nn], aF[nn >> 1][m][1], bF[nn & 1][0]);
-            XU_MFMA(accS[m][nn], aF[nn >> 1][m][0], bF[nn & 1][1]);
-            XU_MFMA(accH[m][nn], aF[nn >> 1][m][0], bF[nn & 1][0]);
+            X3_MFMA(accS[m][nn], aF[nn >> 1][m][2], bF[nn & 1][0]);
+            X3_MFMA(accS[m][nn], aF[nn >> 1][m][0], bF[nn & 1][2]);
+            X3_MFMA(accS[m][nn], aF[nn >> 1][m][1], bF[nn & 1][1]);
+            X3_MFMA(accS[m][nn], aF[nn >> 1][m][1], bF[nn & 1][0]);
+            X3_MFMA(accS[m][nn], aF[nn >> 1][m][0], bF[nn & 1][1]);
+            X3_MFMA(accH[m][nn], aF[nn >> 1][m][0], bF[nn & 1][0]);
           }
           __builtin_amdgcn_sched_barrier(0);
           if ((nn == 1 || nn == 2) && next_h) {
@@ -286,18 +252,18 @@ __global__ __launch_bounds__(512) void conv_x3_up_kernel(XUArgs p) {
       }
       gs += 8;
       // 64 channels x 4 taps = 256 terms: close the hi*hi chain
-      XU_MFMA_DRAIN(accH);
+      X3_DRAIN(XU_ACC8(accH));
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int nn = 0; nn < 4; ++nn) { accT[m][nn] += accH[m][nn]; accH[m][nn] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-      XU_VALU_SETTLE(accH);
+      X3_SETTLE(XU_ACC8(accH));
       __builtin_amdgcn_sched_barrier(0);
     }
 
     // ---- epilogue: output row 2 (oy0 + 2wm + m) + py, columns 2 (ox0 + 4kg) .. + 7: the two column parities interleaved --------------
     {
-      XU_MFMA_DRAIN(accS);
+      X3_DRAIN(XU_ACC8(accS));
       typedef const __attribute__((address_space(4))) XUArgs* XUArgsK;
       unsigned long long kpi = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
       asm volatile("" : "+s"(kpi));
@@ -328,7 +294,7 @@ __global__ __launch_bounds__(512) void conv_x3_up_kernel(XUArgs p) {
           accT[m][2 + cb] = f32x4{0.f, 0.f, 0.f, 0.f}; accS[m][2 + cb] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
       }
-      XU_VALU_SETTLE(accS);
+      X3_SETTLE(XU_ACC8(accS));
     }
     if (!nvalid) break;
     tile = ntile;
@@ -355,6 +321,15 @@ __global__ void x3_up_pack_kernel(const float* __restrict__ w, __bf16* __restric
   gl_x3_up_pack_position(w9, up, scale, out, CI, CO, ci, co);
 }
 
+// The launch's limits (buffer-resource ranges, 32-bit offsets, the tile count): the number of tiles, 0 past a limit.  Either
+// form has CO / 32 weight images of CI / 8 k-steps: (row parity, 64 channels) or both parities of 32 channels.
+long long xu_tiles(int N, int CI, int CO, int Hl, int Wl) {
+  const long long ntiles = (long long)N * (Wl / 16) * (Hl / 8) * (CO / 32);
+  const bool fits = ntiles > 0 && ntiles <= 0x7fffffffLL && (long long)(CO / 32) * (CI / 8) * XU_WSTEP * 16 <= 0xffffffffLL &&
+                    (long long)CI * Hl * Wl * 4 <= 0x7fffffffLL && (long long)N * CI * 4 <= 0x7fffffffLL;
+  return fits ? ntiles : 0;
+}
+
 // the transposed form takes: an up layer's forward (dgrad = 0) or a pooled layer's input gradient (dgrad = 1)
 bool xu_ok(const ganlab_conv_geom* g, int dgrad) {
   if (g == nullptr || g->ks != 3 || g->pad != 1 || g->N <= 0) return false;
@@ -362,19 +337,15 @@ bool xu_ok(const ganlab_conv_geom* g, int dgrad) {
   const int CI = dgrad ? g->Cout : g->Cin, CO = dgrad ? g->Cin : g->Cout;
   if (dgrad && ((g->Hin | g->Win) & 1)) return false;
   const int Hl = dgrad ? g->Hin / 2 : g->Hin, Wl = dgrad ? g->Win / 2 : g->Win;      // the up layer's input; the pooled layer's OUTPUT
-  if ((long long)CI * Hl * Wl * 4 > 0x7fffffffLL || (long long)g->N * CI * 4 > 0x7fffffffLL) return false;
   if (!(CI % 64 == 0 && CO % 32 == 0 && Hl % 8 == 0 && Wl % 16 == 0)) return false;
-  // xu_launch's limits: tile count, weight image (CO / 32 images of CI / 8 k-steps, either form)
-  const long long ntiles = (long long)g->N * (Wl / 16) * (Hl / 8) * (CO / 32);
-  return ntiles > 0 && ntiles <= 0x7fffffffLL && (long long)(CO / 32) * (CI / 8) * XU_WSTEP * 16 <= 0xffffffffLL;
+  return xu_tiles(g->N, CI, CO, Hl, Wl) > 0;
 }
 
 int xu_launch(bool aff, XUArgs a, hipStream_t st) {
   const bool c32 = a.CO % XU_CO != 0;      // the 32-channel form (gl_x3_up_pack_position packs by the same rule)
   a.tiles_x = a.Wl / 16; a.tiles_y = a.Hl / 8; a.tiles_co = c32 ? a.CO / 32 : a.CO / XU_CO;
-  const int images = a.tiles_co * (c32 ? 1 : 2);
-  const long long ntiles = (long long)a.N * a.tiles_x * a.tiles_y * images;
-  if (ntiles <= 0 || ntiles > 0x7fffffffLL || (long long)images * (a.CI / 8) * XU_WSTEP * 16 > 0xffffffffLL) return GANLAB_EINVAL;
+  const long long ntiles = xu_tiles(a.N, a.CI, a.CO, a.Hl, a.Wl);
+  if (ntiles <= 0) return GANLAB_EINVAL;
   a.ntiles = (int)ntiles;
   const unsigned grid = (unsigned)(ntiles < 256 ? ntiles : 256);
   if (c32) {

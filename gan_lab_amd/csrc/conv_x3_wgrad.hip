@@ -12,14 +12,9 @@
 // row (the k-loop runs on across strips and images), stages one gy row (with a 4-pixel halo) and one X row per k-step two
 // steps ahead of their use (inline-asm loads, hand-counted waits), splits them on the way into LDS, and dumps T + H + S into
 // its slot of the workspace at the end; x3w_reduce_kernel adds the slots in a fixed order.
-#include "common.h"
+#include "x3_common.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int XW_CO = 32, XW_CI = 64;
 // LDS images are channel-major with an ODD-ish channel pitch: a fragment read takes 16 channels x 16 bytes (pitch 7 resp. 5 units
@@ -35,23 +30,8 @@ constexpr int XW_ZERO = 4;
 constexpr int XW_LDS = 2 * XW_GROW + 5 * XW_XROW;  // 6144 units = 98,304 bytes
 constexpr int XW_DUMP = 32;                        // k-steps per hi*hi chain
 
-#define XW_MFMA(acc, a, b) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b))
+// the accumulator set of a wave: operand list of X3_DRAIN / X3_SETTLE
 #define XW_ACC9(a) "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(a[8])
-#define XW_MFMA_DRAIN(a) asm volatile("s_nop 15\n\ts_nop 15" : XW_ACC9(a))
-#define XW_VALU_SETTLE(a) asm volatile("s_nop 7\n\ts_nop 7" : XW_ACC9(a))
-
-__device__ __forceinline__ u32x4 xw_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long b = reinterpret_cast<unsigned long long>(base);
-  return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32)) & 0xffffu,
-               (unsigned)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
-__device__ __forceinline__ void xw_ld(f32x4& d, const u32x4& rs, int voff) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(d) : "v"(voff), "s"(rs));
-}
-template <int YOUNGER>
-__device__ __forceinline__ void xw_ld_wait(f32x4& a, f32x4& b) {
-  asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(YOUNGER));
-}
 
 struct XWArgs {
   const float* gy;
@@ -64,19 +44,6 @@ struct XWArgs {
   int strips_x, nstrips;    // W / 32, N * W / 32
   int tiles_ci, splits, sps;   // input-channel tiles, k-splits per channel-tile pair, strips per split
 };
-
-// split four values into planes: 8 bytes each
-__device__ __forceinline__ void xw_split4(const f32x4& v, u32x2& h, u32x2& m, u32x2& l) {
-  bf16x4 hh, mm, ll;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    hh[j] = (__bf16)v[j];
-    const float r1 = v[j] - (float)hh[j];
-    mm[j] = (__bf16)r1;
-    ll[j] = (__bf16)(r1 - (float)mm[j]);
-  }
-  h = __builtin_bit_cast(u32x2, hh); m = __builtin_bit_cast(u32x2, mm); l = __builtin_bit_cast(u32x2, ll);
-}
 
 template <bool AFF>
 __global__ __launch_bounds__(512) void conv_x3_wgrad_kernel(XWArgs p) {
@@ -97,8 +64,8 @@ __global__ __launch_bounds__(512) void conv_x3_wgrad_kernel(XWArgs p) {
   const int hmask = p.H - 1;
   const long long plane = (long long)p.H * p.W;
 
-  const u32x4 rs_g = xw_rsrc(p.gy, (unsigned)((long long)p.N * p.CO * plane * 4));
-  const u32x4 rs_x = xw_rsrc(p.x, (unsigned)((long long)p.N * p.CI * plane * 4));
+  const u32x4 rs_g = x3_rsrc(p.gy, (unsigned)((long long)p.N * p.CO * plane * 4));
+  const u32x4 rs_x = x3_rsrc(p.x, (unsigned)((long long)p.N * p.CI * plane * 4));
 
   // ---- staging items: gy (co = tid / 10, 4 pixels x0 - 4 + 4q, q = tid % 10; threads >= 320 issue an out-of-range load so
   //      every wave's operation count is the same), X (ci = tid / 8, pixels x0 + 4q, q = tid % 8) -----------------------------
@@ -131,7 +98,7 @@ __global__ __launch_bounds__(512) void conv_x3_wgrad_kernel(XWArgs p) {
   auto g_store = [&](const f32x4& v, int buf) {
     if (!g_item) return;
     u32x2 h, m, l;
-    xw_split4(v, h, m, l);
+    x3_split4(v, h, m, l);
     unsigned char* d = reinterpret_cast<unsigned char*>(lds + buf * XW_GROW) + g_dst;
     *reinterpret_cast<u32x2*>(d) = h;
     *reinterpret_cast<u32x2*>(d + XW_GPL * 16) = m;
@@ -150,7 +117,7 @@ __global__ __launch_bounds__(512) void conv_x3_wgrad_kernel(XWArgs p) {
       for (int j = 0; j < 4; ++j) v[j] = fmaf(v[j], a_s, a_t);
     }
     u32x2 h, m, l;
-    xw_split4(v, h, m, l);
+    x3_split4(v, h, m, l);
     unsigned char* d = reinterpret_cast<unsigned char*>(lds + XW_XOFF + slot * XW_XROW) + x_dst;
     *reinterpret_cast<u32x2*>(d) = h;
     *reinterpret_cast<u32x2*>(d + XW_XPL * 16) = m;
@@ -161,8 +128,8 @@ __global__ __launch_bounds__(512) void conv_x3_wgrad_kernel(XWArgs p) {
 #pragma unroll
   for (int t = 0; t < 9; ++t) { accS[t] = f32x4{0.f, 0.f, 0.f, 0.f}; accH[t] = f32x4{0.f, 0.f, 0.f, 0.f}; accT[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
-  XW_VALU_SETTLE(accS);
-  XW_VALU_SETTLE(accH);
+  X3_SETTLE(XW_ACC9(accS));
+  X3_SETTLE(XW_ACC9(accH));
   // fragment addresses (units): gy centre unit 1 + kg of row image `buf`; X unit kg of slot
   const int laneG = (wc * 16 + l16) * XW_GP + 1 + kg;
   const int laneX = XW_XOFF + (wi * 16 + l16) * XW_XP + kg;
@@ -202,14 +169,14 @@ __global__ __launch_bounds__(512) void conv_x3_wgrad_kernel(XWArgs p) {
   // ---- prologue: the zero slot; gy row 0 and X rows 0, 1 in LDS; rows (gy 1, X 2) and (gy 2, X 3) in flight ---------------------
   for (int i = tid; i < XW_XROW; i += 512) lds[XW_XOFF + XW_ZERO * XW_XROW + i] = u32x4{0u, 0u, 0u, 0u};
   f32x4 gA, xA, gB, xB;      // two load sets: (gy f + 1, X f + 2) of even / odd k-steps f
-  xw_ld(gA, rs_g, g_off(0)); xw_ld(xA, rs_x, x_off(0));
-  xw_ld(gB, rs_g, (int)0x80000000); xw_ld(xB, rs_x, x_off(1));
-  xw_ld_wait<0>(gA, xA);
-  xw_ld_wait<0>(gB, xB);
+  x3_ld(gA, rs_g, g_off(0)); x3_ld(xA, rs_x, x_off(0));
+  x3_ld(gB, rs_g, (int)0x80000000); x3_ld(xB, rs_x, x_off(1));
+  x3_ld_wait<0>(gA, xA);
+  x3_ld_wait<0>(gB, xB);
   g_store(gA, 0); x_store(xA, 0, 0); x_store(xB, 1, 1);
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  xw_ld(gA, rs_g, g_off(1)); xw_ld(xA, rs_x, x_off(2));
-  xw_ld(gB, rs_g, g_off(2)); xw_ld(xB, rs_x, x_off(3));
+  x3_ld(gA, rs_g, g_off(1)); x3_ld(xA, rs_x, x_off(2));
+  x3_ld(gB, rs_g, g_off(2)); x3_ld(xB, rs_x, x_off(3));
   g_frags(0);
   x_frags(XW_ZERO, 0);       // k-step 0: row -1 of the first strip
 
@@ -228,27 +195,27 @@ __global__ __launch_bounds__(512) void conv_x3_wgrad_kernel(XWArgs p) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
-        XW_MFMA(accS[kx], aS[kx][2], bX[0][0]); XW_MFMA(accS[kx], aS[kx][0], bX[0][2]); XW_MFMA(accS[kx], aS[kx][1], bX[0][1]);
-        XW_MFMA(accS[kx], aS[kx][1], bX[0][0]); XW_MFMA(accS[kx], aS[kx][0], bX[0][1]); XW_MFMA(accH[kx], aS[kx][0], bX[0][0]);
+        X3_MFMA(accS[kx], aS[kx][2], bX[0][0]); X3_MFMA(accS[kx], aS[kx][0], bX[0][2]); X3_MFMA(accS[kx], aS[kx][1], bX[0][1]);
+        X3_MFMA(accS[kx], aS[kx][1], bX[0][0]); X3_MFMA(accS[kx], aS[kx][0], bX[0][1]); X3_MFMA(accH[kx], aS[kx][0], bX[0][0]);
       }
       __builtin_amdgcn_sched_barrier(0);
       // ---- staging: rows gy f + 1 and X f + 2 (requested two steps ago) go to LDS; behind them only the loads of the step
       //      before (2) are younger -----------------------------------------------------------------------------------------
-      if (u & 1) { xw_ld_wait<2>(gB, xB); g_store(gB, (u + 1) & 1); x_store(xB, (u + 2) & 3, f + 2); }
-      else { xw_ld_wait<2>(gA, xA); g_store(gA, (u + 1) & 1); x_store(xA, (u + 2) & 3, f + 2); }
+      if (u & 1) { x3_ld_wait<2>(gB, xB); g_store(gB, (u + 1) & 1); x_store(xB, (u + 2) & 3, f + 2); }
+      else { x3_ld_wait<2>(gA, xA); g_store(gA, (u + 1) & 1); x_store(xA, (u + 2) & 3, f + 2); }
       __builtin_amdgcn_sched_barrier(0);
       x_frags(slot2, 0);
       __builtin_amdgcn_sched_barrier(0);
       // ---- ky = 1 (X row y) ----------------------------------------------------------------------------------------------------
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
-        XW_MFMA(accS[3 + kx], aS[kx][2], bX[1][0]); XW_MFMA(accS[3 + kx], aS[kx][0], bX[1][2]); XW_MFMA(accS[3 + kx], aS[kx][1], bX[1][1]);
-        XW_MFMA(accS[3 + kx], aS[kx][1], bX[1][0]); XW_MFMA(accS[3 + kx], aS[kx][0], bX[1][1]); XW_MFMA(accH[3 + kx], aS[kx][0], bX[1][0]);
+        X3_MFMA(accS[3 + kx], aS[kx][2], bX[1][0]); X3_MFMA(accS[3 + kx], aS[kx][0], bX[1][2]); X3_MFMA(accS[3 + kx], aS[kx][1], bX[1][1]);
+        X3_MFMA(accS[3 + kx], aS[kx][1], bX[1][0]); X3_MFMA(accS[3 + kx], aS[kx][0], bX[1][1]); X3_MFMA(accH[3 + kx], aS[kx][0], bX[1][0]);
       }
       __builtin_amdgcn_sched_barrier(0);
       // rows gy f + 3, X f + 4 requested
-      if (u & 1) { xw_ld(gB, rs_g, g_off(f + 3)); xw_ld(xB, rs_x, x_off(f + 4)); }
-      else { xw_ld(gA, rs_g, g_off(f + 3)); xw_ld(xA, rs_x, x_off(f + 4)); }
+      if (u & 1) { x3_ld(gB, rs_g, g_off(f + 3)); x3_ld(xB, rs_x, x_off(f + 4)); }
+      else { x3_ld(gA, rs_g, g_off(f + 3)); x3_ld(xA, rs_x, x_off(f + 4)); }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");        // the rows stored above are visible behind it
       __builtin_amdgcn_sched_barrier(0);
       // next k-step's gy fragments and its row y' - 1 (= this row y, or the zero slot at the top of a strip)
@@ -257,25 +224,25 @@ __global__ __launch_bounds__(512) void conv_x3_wgrad_kernel(XWArgs p) {
       // ---- ky = 2 (X row y + 1) ------------------------------------------------------------------------------------------------
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
-        XW_MFMA(accS[6 + kx], aS[kx][2], bX[0][0]); XW_MFMA(accS[6 + kx], aS[kx][0], bX[0][2]); XW_MFMA(accS[6 + kx], aS[kx][1], bX[0][1]);
-        XW_MFMA(accS[6 + kx], aS[kx][1], bX[0][0]); XW_MFMA(accS[6 + kx], aS[kx][0], bX[0][1]); XW_MFMA(accH[6 + kx], aS[kx][0], bX[0][0]);
+        X3_MFMA(accS[6 + kx], aS[kx][2], bX[0][0]); X3_MFMA(accS[6 + kx], aS[kx][0], bX[0][2]); X3_MFMA(accS[6 + kx], aS[kx][1], bX[0][1]);
+        X3_MFMA(accS[6 + kx], aS[kx][1], bX[0][0]); X3_MFMA(accS[6 + kx], aS[kx][0], bX[0][1]); X3_MFMA(accH[6 + kx], aS[kx][0], bX[0][0]);
       }
       __builtin_amdgcn_sched_barrier(0);
       x_frags(y == hmask ? XW_ZERO : u, 0);      // row y' - 1 of the next k-step
       if (++since_dump == XW_DUMP) {
         since_dump = 0;
-        XW_MFMA_DRAIN(accH);
+        X3_DRAIN(XW_ACC9(accH));
 #pragma unroll
         for (int t = 0; t < 9; ++t) { accT[t] += accH[t]; accH[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        XW_VALU_SETTLE(accH);
+        X3_SETTLE(XW_ACC9(accH));
       }
       __builtin_amdgcn_sched_barrier(0);
     }
   }
 
   // ---- this workgroup's partial sums: part[slot = split][co][ci][tap] -------------------------------------------------------------
-  XW_MFMA_DRAIN(accS);
-  XW_MFMA_DRAIN(accH);
+  X3_DRAIN(XW_ACC9(accS));
+  X3_DRAIN(XW_ACC9(accH));
   float* dst = p.part + (long long)split * p.CO * p.CI * 9;
 #pragma unroll
   for (int t = 0; t < 9; ++t) {

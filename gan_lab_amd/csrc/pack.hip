@@ -11,15 +11,6 @@ namespace {
 
 constexpr int round_up_c(int v, int m) { return (v + m - 1) / m * m; }
 
-__device__ __forceinline__ float comb_s2(int up, int a, int k) {          // conv_s2.hip: the 4x3 combination matrices
-  if (up) {
-    const int lo = (a == 0) ? 2 : (a == 1 ? 1 : 0), hi = (a == 0) ? 2 : (a == 1 ? 2 : (a == 2 ? 1 : 0));
-    return (k >= lo && k <= hi) ? 1.f : 0.f;
-  }
-  const int lo = (a <= 1) ? 0 : (a == 2 ? 1 : 2), hi = (a == 0) ? 0 : (a == 1 ? 1 : 2);
-  return (k >= lo && k <= hi) ? 0.5f : 0.f;
-}
-
 __global__ __launch_bounds__(256) void pack_many_kernel(const ganlab_pack_desc* __restrict__ descs, int n_desc) {
   // binary search: last descriptor whose first block is <= blockIdx.x
   int lo = 0, hi = n_desc - 1;
@@ -68,7 +59,7 @@ __global__ __launch_bounds__(256) void pack_many_kernel(const ganlab_pack_desc* 
 #pragma unroll
       for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx) v += comb_s2(d.up, a, ky) * comb_s2(d.up, bb, kx) * k9[ky * 3 + kx];
+        for (int kx = 0; kx < 3; ++kx) v += gl_comb_s2(d.up, a, ky) * gl_comb_s2(d.up, bb, kx) * k9[ky * 3 + kx];
       out[tap * plane] = v * d.scale;
     }
   } else if (d.kind == GANLAB_PACKKIND_X3 && d.ks == 4) {      // conv_x3.hip, transposed stride-2 form (d.up: 1 = up layer's

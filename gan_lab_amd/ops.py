@@ -467,57 +467,38 @@ def x3_s2_down_ok(g, dgrad=False):
     return bool(_lib.lib().ganlab_conv_s2_down_x3_supported(g.ref(), 1 if dgrad else 0))
 
 
-def _packed_x3_s2_down(w, up, scale):
-    """``up``: 0 = a pooled layer's forward weights, 1 = an up layer's input-gradient weights."""
-    key = (w.data_ptr(), w._version, tuple(w.shape), int(up), float(scale), 'x3s2d')
+def _packed_x3_any(name, tag, w, sel, scale, ks):
+    """A weight's three bf16 planes in the layout of one split-product kernel: library function ``ganlab_<name>``, cache tag
+    ``tag``; ``sel`` is the function's mode / up argument, ``ks`` the descriptor's form (3: ``sel`` is its mode; 4, 5: its up)."""
+    key = (w.data_ptr(), w._version, tuple(w.shape), sel, float(scale), tag)
     hit = _pack_lookup(key)
     if hit is not None:
         return hit
     cout, cin = w.shape[0], w.shape[1]
-    L = _lib.lib()
-    n = L.ganlab_conv_s2_down_x3_pack(None, None, cout, cin, int(up), scale, None)
+    pack = getattr(_lib.lib(), 'ganlab_' + name)
+    n = pack(None, None, cout, cin, sel, scale, None)
     if n <= 0:
-        raise _lib.GanlabLibraryError(f'conv_s2_down_x3_pack size query failed ({n}) for weight {tuple(w.shape)}')
+        raise _lib.GanlabLibraryError(f'{name} size query failed ({n}) for weight {tuple(w.shape)}')
     out = torch.empty((n,), dtype=torch.bfloat16, device=w.device)
-    rc = L.ganlab_conv_s2_down_x3_pack(_p(w), out.data_ptr(), cout, cin, int(up), scale, _st())
+    rc = pack(_p(w), out.data_ptr(), cout, cin, sel, scale, _st())
     if rc != n:
-        raise _lib.GanlabLibraryError(f'conv_s2_down_x3_pack failed ({rc})')
-    return _pack_store(key, w, out, (_KIND_X3, cout, cin, 5, 0, int(up), float(scale), int(n)))
+        raise _lib.GanlabLibraryError(f'{name} failed ({rc})')
+    mode, up = (sel, 0) if ks == 3 else (0, sel)
+    return _pack_store(key, w, out, (_KIND_X3, cout, cin, ks, mode, up, float(scale), int(n)))
+
+
+def _packed_x3_s2_down(w, up, scale):
+    """``up``: 0 = a pooled layer's forward weights, 1 = an up layer's input-gradient weights."""
+    return _packed_x3_any('conv_s2_down_x3_pack', 'x3s2d', w, int(up), scale, 5)
 
 
 def _packed_x3_s2(w, up, scale):
     """``up``: 1 = an up layer's forward weights, 0 = a pooled layer's input-gradient weights."""
-    key = (w.data_ptr(), w._version, tuple(w.shape), int(up), float(scale), 'x3s2')
-    hit = _pack_lookup(key)
-    if hit is not None:
-        return hit
-    cout, cin = w.shape[0], w.shape[1]
-    L = _lib.lib()
-    n = L.ganlab_conv_s2_x3_pack(None, None, cout, cin, int(up), scale, None)
-    if n <= 0:
-        raise _lib.GanlabLibraryError(f'conv_s2_x3_pack size query failed ({n}) for weight {tuple(w.shape)}')
-    out = torch.empty((n,), dtype=torch.bfloat16, device=w.device)
-    rc = L.ganlab_conv_s2_x3_pack(_p(w), out.data_ptr(), cout, cin, int(up), scale, _st())
-    if rc != n:
-        raise _lib.GanlabLibraryError(f'conv_s2_x3_pack failed ({rc})')
-    return _pack_store(key, w, out, (_KIND_X3, cout, cin, 4, 0, int(up), float(scale), int(n)))
+    return _packed_x3_any('conv_s2_x3_pack', 'x3s2', w, int(up), scale, 4)
 
 
 def _packed_x3(w, mode, scale):
-    key = (w.data_ptr(), w._version, tuple(w.shape), mode, float(scale), 'x3')
-    hit = _pack_lookup(key)
-    if hit is not None:
-        return hit
-    cout, cin = w.shape[0], w.shape[1]
-    L = _lib.lib()
-    n = L.ganlab_conv_x3_pack(None, None, cout, cin, mode, scale, None)
-    if n <= 0:
-        raise _lib.GanlabLibraryError(f'conv_x3_pack size query failed ({n}) for weight {tuple(w.shape)}')
-    out = torch.empty((n,), dtype=torch.bfloat16, device=w.device)
-    rc = L.ganlab_conv_x3_pack(_p(w), out.data_ptr(), cout, cin, mode, scale, _st())
-    if rc != n:
-        raise _lib.GanlabLibraryError(f'conv_x3_pack failed ({rc})')
-    return _pack_store(key, w, out, (_KIND_X3, cout, cin, 3, mode, 0, float(scale), int(n)))
+    return _packed_x3_any('conv_x3_pack', 'x3', w, mode, scale, 3)
 
 
 # ---- "input gradient only" mode ---------------------------------------------------------------------
