@@ -320,6 +320,13 @@ SIGNATURES = {
     'ganlab_prdc_norms_f32': (_c_int, [_c_p, _c_p, _c_ll, _c_int, _c_p]),
     'ganlab_prdc_knn_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_p]),
     'ganlab_prdc_cross_f32': (_c_int, [_c_p] * 5 + [_c_int, _c_p, _c_p, _c_p, _c_ll, _c_ll, _c_int, _c_p]),
+    'ganlab_cr_params_i32': (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_u64, _c_u64, _c_p, _c_p]),
+    'ganlab_cr_transform_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p]),
+    'ganlab_cr_msd_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_p]),
+    'ganlab_cr_msd_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p]),
+    'ganlab_cr_imsd_workspace': (_c_sz, [_c_ll]),
+    'ganlab_cr_imsd_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_p, _c_sz, _c_p]),
+    'ganlab_cr_imsd_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_p]),
     'ganlab_step_scalars_size': (_c_int, []),
     'ganlab_set_step_scalars': (_c_int, [_c_p, _c_u64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
 }

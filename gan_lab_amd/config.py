@@ -67,7 +67,18 @@ launches, with ``d = 0`` (a plain copy) while fewer than ``ewma_start`` updates 
 ``truncation`` (None = off, else > 0) is the default threshold of ``learner.generate()``'s truncation trick - latents from the
 standard normal truncated to [-t, t] by inverse CDF on the project's Philox stream - and ``standing_stat_batches`` (16; >= 1)
 the default number of batches over which ``generate(standing_stats=True)`` re-estimates every BatchNorm's statistics as a plain
-average; a value outside these ranges raises when the learner is built, and ProGAN / StyleGAN have none of the four new fields.
+average; a value outside these ranges raises when the learner is built, and ProGAN / StyleGAN have none of the four new fields;
+``cr_real`` / ``cr_fake`` / ``cr_latent_d`` / ``cr_latent_g`` (ResNet GAN only; 0 = off) are the weights of consistency
+regularisation (consistency.py): bCR (Zhang et al. 2020) adds ``cr_real * msd(D(x), D(T(x))) + cr_fake * msd(D(G(z)), D(T(G(z))))``
+to the critic's loss, ``T`` a horizontal flip (``cr_flip``, default True) and a shift by up to ``cr_shift`` pixels per axis with
+zero fill (None = ``res_samples // 8``: 4 at 32 pixels, 8 at 64; ``--cr_shift=none`` on the command line), drawn afresh for every
+image from the project's Philox stream; zCR (Zhao et al. 2020) adds ``cr_latent_d * msd(D(G(z)), D(G(z')))`` to the critic's loss
+and ``- cr_latent_g * imsd(G(z), G(z'))`` to the generator's, ``z' = z + cr_sigma * n`` (``cr_sigma`` 0.03) with a fresh normal
+``n``; ``msd`` is the batch mean of squared score differences, ``imsd`` the mean over all elements of squared image differences.
+ICR's CIFAR-10 BigGAN setting is 10 / 10 / 5 / 0.5.  The terms are first order in the critic and compose with every loss and
+penalty, ``spectral_norm``, ``self_attention`` and ``cgan``; with all four weights at 0 nothing is built, drawn or launched.  A
+negative or non-finite weight, ``cr_sigma <= 0`` with a latent weight on, ``cr_shift`` outside [0, res_samples), or a positive
+weight together with ``diffaugment`` / ``ada`` raises when the learner is built, and ProGAN / StyleGAN have no such field.
 ``--gradient_penalty=none`` on the command line means no penalty (None), as ``make_config(gradient_penalty=None)`` does.
 """
 import argparse
@@ -89,6 +100,11 @@ _MODELS = {'resnetgan': 'ResNet GAN', 'resnet gan': 'ResNet GAN', 'progan': 'Pro
 def _float_or_none(v):
     """CLI type of an optional float: 'none' (any case) -> None."""
     return None if v is None or str(v).casefold() == 'none' else float(v)
+
+
+def _int_or_none(v):
+    """CLI type of an optional integer: 'none' (any case) -> None."""
+    return None if v is None or str(v).casefold() == 'none' else int(v)
 
 
 def _str_or_none(v):
@@ -131,7 +147,9 @@ def _spec(model_type):
                  ('leakiness', float, .01), ('use_equalized_lr', bool, False), ('spectral_norm', bool, False),
                  ('ortho_reg', float, 0.), ('ortho_reg_d', float, 0.), ('hier_latent', bool, False), ('shared_embed', int, 0),
                  ('use_ewma_gen', bool, False), ('ewma_decay', float, 0.9999), ('ewma_start', int, 0),
-                 ('truncation', _float_or_none, None), ('standing_stat_batches', int, 16)]
+                 ('truncation', _float_or_none, None), ('standing_stat_batches', int, 16),
+                 ('cr_real', float, 0.), ('cr_fake', float, 0.), ('cr_latent_d', float, 0.), ('cr_latent_g', float, 0.),
+                 ('cr_sigma', float, 0.03), ('cr_shift', _int_or_none, None), ('cr_flip', bool, True)]
     else:
         rows += [('batch_size', int, BS),
                  ('bs_dict', dict, {4: BS, 8: BS, 16: BS, 32: BS, 64: BS, 128: BS, 256: BS, 512: BS // 2,

@@ -20,7 +20,9 @@ the optimiser step (ortho_reg.py); ``config.hier_latent`` / ``config.shared_embe
 conditioning - hierarchical latents and a shared class embedding modulating every block norm (hier_latent.py) - without touching
 the critic or the label routing; ``config.use_ewma_gen`` / ``config.truncation`` / ``config.standing_stat_batches`` (ResNet GAN
 only) are the sampling side - an averaged copy of the generator updated after every generator step, and ``generate()`` with the
-truncation trick and standing statistics (sampling.py); all of them are off by default.
+truncation trick and standing statistics (sampling.py); ``config.cr_real`` / ``cr_fake`` / ``cr_latent_d`` / ``cr_latent_g``
+(ResNet GAN only) add consistency regularisation - bCR on a flipped and shifted copy of the critic's inputs, zCR on a perturbed
+latent - to the critic's and the generator's loss (consistency.py); all of them are off by default.
 Validation metrics, image grids and plotting (:249-461, :950-1046) are outside the hot path."""
 import os
 import warnings
@@ -127,6 +129,9 @@ class GANLearner(object):
         # BigGAN's orthogonal regulariser (config.ortho_reg / config.ortho_reg_d; ortho_reg.py): managers over the arenas
         from .. import ortho_reg
         self._ortho_beta = ortho_reg.validate_config(config)
+        # consistency regularisation (config.cr_*; consistency.py): None with every weight at 0 - nothing drawn, nothing launched
+        from .. import consistency
+        self.cr = consistency.validate_config(config)
         self.ortho_g = self.ortho_d = None
         self._gradient_penalty = config.gradient_penalty
         self._optimizer = config.optimizer.casefold()
@@ -325,10 +330,11 @@ class GANLearner(object):
     def _disc(self, x, labels):
         return self.disc_model(x, labels) if self.cgan else self.disc_model(x)
 
-    def g_step(self, zb=None, aug_params=None, labels=None):
+    def g_step(self, zb=None, aug_params=None, labels=None, cr_noise=None):
         """resnetgan/learner.py:545-597 (critic parameters frozen by the caller).  ``aug_params``: the DiffAugment rows
         of the generated batch (tests; drawn when None).  ``labels`` (``config.cgan``): the classes to generate, drawn
-        uniformly on the device when None."""
+        uniformly on the device when None.  ``cr_noise`` (``config.cr_latent_g``): the latent perturbation n of
+        ``z' = z + cr_sigma * n`` (tests; drawn when None)."""
         c = self.config
         self.arena_g.zero_grad()
         if self.sn is not None:
@@ -337,12 +343,25 @@ class GANLearner(object):
             zb = gen_rand_latent_vars(num_samples=self.batch_size * c.gen_bs_mult, length=c.len_latent,
                                       distribution=self.latent_distribution, device=c.dev)
         labels = self._device_labels(labels, zb.shape[0], draw=True)
-        fake = self._gen(zb, labels)
+        cr_term = None
+        if self.cr is not None and self.cr.latent_g > 0:
+            # zCR, generator side: ONE pass over [z; z'] (BatchNorm statistics over both halves; consistency.py); the first
+            # half goes on to the critic, the term's gradient reaches both halves as a single (2N, C, H, W) cotangent
+            n = zb.shape[0]
+            both = self._gen(torch.cat((zb, self.cr.perturb(zb, cr_noise))),
+                             torch.cat((labels, labels)) if labels is not None else None)
+            cr_term = ops.cr_imsd(both)
+            fake = both[:n]
+        else:
+            fake = self._gen(zb, labels)
         if self.critic_aug is not None:
             fake = self._augment(fake, aug_params)
         out = self._disc(fake, labels)
         # :573-578 - the minimax generator loss here is -BCE(D(G(z)), 0), like backprop_utils
         loss = self.loss_func_gen(out)
+        if cr_term is not None:
+            loss = loss - self.cr.latent_g * cr_term
+            self.last_losses['cr_latent_g'] = cr_term.detach()      # unweighted; a device tensor: no host synchronisation
         self.reducer.arm(self.arena_g)
         with ops.direct_param_grads(ops.direct_grads_enabled()):      # first-use gradients land in the arena directly
             loss.backward()
@@ -458,12 +477,14 @@ class GANLearner(object):
             self._pairable = (id(self.disc_model), ok)
         return ok
 
-    def d_step(self, xb, zb=None, eps_interp=None, aug_params=None, labels=None):
+    def d_step(self, xb, zb=None, eps_interp=None, aug_params=None, labels=None, cr_noise=None, cr_params=None):
         """resnetgan/learner.py:606-672: generator frozen but in train mode (its BatchNorm running
         statistics keep moving, :621-622); no drift term on this path.  ``aug_params``: the DiffAugment rows, [0, B) for
         the generated batch and [B, 2B) for the real one (tests; drawn when None).  ``labels`` (``config.cgan``; required
         then): the real batch's classes; the generated batch is produced with the SAME labels, so that row i of a WGAN-GP
-        interpolate lies between two images of one class."""
+        interpolate lies between two images of one class.  ``cr_noise`` / ``cr_params`` (``config.cr_*``; tests, drawn when
+        None): the latent perturbation n of ``z' = z + cr_sigma * n``, and the (2B, 4) int32 transform rows, [0, B) for the
+        generated batch and [B, 2B) for the real one."""
         c = self.config
         labels = self._device_labels(labels, xb.shape[0], draw=False)
         self.arena_d.zero_grad()
@@ -474,9 +495,31 @@ class GANLearner(object):
                                       distribution=self.latent_distribution, device=c.dev)
         if labels is not None and zb.shape[0] != labels.shape[0]:
             raise ValueError(f'd_step: {zb.shape[0]} latents for {labels.shape[0]} labelled real images')
+        cr = self.cr
+        xgen_p = None
         with torch.no_grad():
-            xgenb = self._gen(zb, labels)
+            if cr is not None and cr.latent_d > 0:
+                # zCR, critic side: ONE generator pass over [z; z'] with the same labels - its BatchNorm statistics are taken
+                # over both halves (consistency.py)
+                both = self._gen(torch.cat((zb, cr.perturb(zb, cr_noise))),
+                                 torch.cat((labels, labels)) if labels is not None else None)
+                xgenb, xgen_p = both[:zb.shape[0]], both[zb.shape[0]:]
+            else:
+                xgenb = self._gen(zb, labels)
         n, aug = xgenb.shape[0], self.critic_aug
+        # the further critic inputs of the consistency terms, in this order: T(x), T(G(z)), G(z') - only those with a weight
+        extra = []
+        if cr is not None:
+            if cr.balanced:
+                if xb.shape[0] != n:
+                    raise ValueError(f'd_step: bCR needs as many real as generated images (got {xb.shape[0]} and {n})')
+                cr_params = cr.draw_params(n, xb.device) if cr_params is None else cr.check_params(cr_params, n)
+            if cr.real > 0:
+                extra.append(('cr_real', cr.real, cr.transform(xb.reshape(xgenb.shape), cr_params[n:])))
+            if cr.fake > 0:
+                extra.append(('cr_fake', cr.fake, cr.transform(xgenb, cr_params[:n])))
+            if xgen_p is not None:
+                extra.append(('cr_latent_d', cr.latent_d, xgen_p))
         if aug is not None and aug_params is None:
             aug_params = aug.draw(n + xb.shape[0], xb.shape[2], xb.shape[3], xb.device)
         if self._pair_critic_batches(xgenb, xb):
@@ -487,13 +530,23 @@ class GANLearner(object):
             if aug is not None:        # one launch over the pair: per sample, the same as two
                 both = aug(both, aug_params)
                 xgenb, xb = both[:n], both[n:]
-            out = self._disc(both, torch.cat((labels, labels)) if labels is not None else None)
-            d_gen, d_real = out[:n], out[n:]
+            # the consistency terms' inputs ride along behind the pair: rows [0, 2n) stay [generated; real]
+            parts = 2 + len(extra)
+            if extra:
+                both = torch.cat([both] + [x for _, _, x in extra])
+            out = self._disc(both, torch.cat((labels,) * parts) if labels is not None else None)
+            d_gen, d_real = out[:n], out[n:2 * n]
+            d_extra = [out[(2 + i) * n:(3 + i) * n] for i in range(len(extra))]
         else:
             if aug is not None:
                 xgenb, xb = aug(xgenb, aug_params[:n]), aug(xb, aug_params[n:])
             d_gen, d_real = self._disc(xgenb, labels), self._disc(xb, labels)
+            d_extra = [self._disc(x, labels) for _, _, x in extra]
         loss = self.loss_func_disc(d_gen, d_real)
+        for (name, weight, _), d_x in zip(extra, d_extra):
+            term = ops.cr_msd(d_real if name == 'cr_real' else d_gen, d_x)
+            loss = loss + weight * term
+            self.last_losses[name] = term.detach()      # unweighted; a device tensor: no host synchronisation
         self._ada_update(d_real)
         if self.gradient_penalty is not None:
             loss = loss + self.calc_gp(xgenb, xb, eps_interp=eps_interp, labels=labels)
@@ -574,7 +627,7 @@ class GANLearner(object):
                     self.last_losses = dict(itr=itr, loss_d=float(loss_d) if loss_d is not None else None,
                                             loss_g=float(loss_g) if loss_g is not None else None,
                                             res=c.res_samples, batch=self.batch_size,
-                                            **{k: v for k, v in self.last_losses.items() if k.startswith('ortho_')})
+                                            **{k: v for k, v in self.last_losses.items() if k.startswith(('ortho_', 'cr_'))})
                     if parallel.rank() == 0:
                         print(('%9s' * 5) % (f'{self.curr_epoch_num}/{self.tot_num_epochs}',
                                              f'{c.res_samples}X{c.res_samples}',
@@ -615,8 +668,10 @@ class GANLearner(object):
         from .. import checkpoint as ckpt
         tcpu = lambda v: None if v is None else v.detach().cpu()  # noqa: E731
         sched_steps = max(self.scheduler_gen._step_count - 1, 0) if (self.sched_bool and self.scheduler_gen) else 0
+        from .. import consistency
         ck = {
-            'config': ckpt.saved_config_fields({k: v for k, v in sampling.saved_config_fields(vars(self.config)).items()
+            'config': ckpt.saved_config_fields({k: v for k, v in
+                                                consistency.saved_config_fields(sampling.saved_config_fields(vars(self.config))).items()
                                                 if not k.startswith('_') and
                                                 isinstance(v, (int, float, str, bool, dict, list, tuple, type(None))) and
                                                 not (k in ('self_attention', 'cgan') and v is None) and

@@ -96,6 +96,20 @@ def augment_params(n, h, w, device='cuda'):
     return out
 
 
+def cr_params(n, shift, flip, device='cuda'):
+    """(n, 4) int32 rows (flip, dx, dy, 0) of the consistency-regularisation image transform (consistency.py): flip in {0, 1}
+    (always 0 when ``flip`` is False), dx, dy uniform in [-shift, shift]; advances the stream by 1 counter per row, so a short
+    draw is a prefix of a long one from the same position."""
+    n = int(n)
+    if _DEVICE_BASE['block'] is not None:
+        out = ops.cr_params(n, shift, flip, _STATE['seed'], _STATE['offset'] - _DEVICE_BASE['start'], device,
+                            base=_DEVICE_BASE['block'])
+    else:
+        out = ops.cr_params(n, shift, flip, _STATE['seed'], _STATE['offset'], device)
+    _STATE['offset'] += n
+    return out
+
+
 def ada_params(n, h, w, state, policy, device='cuda'):
     """(n, 32) ADA parameter rows for (h, w) images at the probability held in the device block ``state`` (ada.py);
     advances the stream by 8 counters per row."""

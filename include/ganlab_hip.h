@@ -970,6 +970,29 @@ int ganlab_prdc_cross_f32(const float* queries, const float* query_norms, const 
                           const float* radii, int radius_of_query, int* count, float* dmin, int* imin, long long M, long long N,
                           int D, void* stream);
 
+/* ---- consistency regularisation of the ResNet GAN: bCR (Zhang et al. 2020) and zCR (Zhao et al. 2020) (config.cr_*;
+ * csrc/cr.hip; composed in gan_lab_amd/consistency.py).  No atomics, every sum in a fixed order: bitwise
+ * reproducible.  Stream-ordered, graph-capturable, nothing is read back by the host.
+ *   cr_params:    row n of the (N, 4) int32 table = (flip, dx, dy, 0) from ONE Philox counter, offset + n (+ *base when base is not
+ *                 NULL: the step-scalar block of a captured step): flip in {0, 1} (always 0 when `flip` is 0), dx, dy uniform
+ *                 integers in [-shift, shift].  out is 16-byte aligned.
+ *   cr_transform: y[n,c,i,j] = x[n,c,i-dy, f(j-dx)] with f(k) = W-1-k when the row's flip is set, else k, and 0 where i-dy or j-dx
+ *                 leaves the image; any N, C, H, W >= 1; x and y do not overlap.  Values are moved or zeroed: bit-exact.
+ *   cr_msd:       out[0] = (1/N) sum_n (a_n - b_n)^2: fp32 differences squared in fp32, summed in fp64 in a fixed order, rounded
+ *                 once; one launch.  bwd: ga = (2/N)(a - b) gout[0], gb = -ga; one launch.
+ *   cr_imsd:      the same mean over the n elements of two equal-shaped image batches; the forward keeps one fp64 partial per
+ *                 workgroup in the workspace (ganlab_cr_imsd_workspace(n) bytes, 8-byte aligned) and a second one-workgroup launch
+ *                 adds them in index order; the value does not depend on the operands' alignment.  bwd: one launch reads a and b
+ *                 and writes ga and gb, which may be the two halves of one tensor (as a and b may be). */
+int ganlab_cr_params_i32(int* out, int N, int shift, int flip, uint64_t seed, uint64_t offset, const void* base, void* stream);
+int ganlab_cr_transform_f32(const float* x, const int* params, float* y, int N, int C, int H, int W, void* stream);
+int ganlab_cr_msd_fwd_f32(const float* a, const float* b, float* out, int N, void* stream);
+int ganlab_cr_msd_bwd_f32(const float* a, const float* b, const float* gout, float* ga, float* gb, int N, void* stream);
+size_t ganlab_cr_imsd_workspace(long long n);
+int ganlab_cr_imsd_fwd_f32(const float* a, const float* b, float* out, long long n, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int ganlab_cr_imsd_bwd_f32(const float* a, const float* b, const float* gout, float* ga, float* gb, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
