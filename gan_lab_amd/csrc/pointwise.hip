@@ -620,9 +620,9 @@ __global__ void bias_act_kernel(const float* __restrict__ x, const float* __rest
   }
 }
 
+// n4 float4 (the host passes n / 4, or 0 when a pointer is not 16-byte aligned), then the remaining n - 4 * n4 elements
 __global__ void act_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ y, float* __restrict__ gz,
-                               long long n, float slope) {
-  const long long n4 = n >> 2;
+                               long long n, long long n4, float slope) {
   GRID_STRIDE(i, n4) {
     const float4 g = reinterpret_cast<const float4*>(gy)[i];
     const float4 o = reinterpret_cast<const float4*>(y)[i];
@@ -635,9 +635,8 @@ __global__ void act_bwd_kernel(const float* __restrict__ gy, const float* __rest
   }
   // tail
   const long long base = n4 << 2;
-  const long long tid = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (tid < n - base) {
-    const long long j = base + tid;
+  GRID_STRIDE(t, n - base) {
+    const long long j = base + t;
     gz[j] = y[j] > 0.f ? gy[j] : gy[j] * slope;
   }
 }
@@ -648,12 +647,12 @@ __global__ void act_bwd_kernel(const float* __restrict__ gy, const float* __rest
 // ---------------------------------------------------------------------------------------------- //
 __global__ __launch_bounds__(256) void channel_sum_stage1(const float* __restrict__ a, const float* __restrict__ b,
                                                           double* __restrict__ part, int N, int C, long long HW,
-                                                          int chunks) {
+                                                          int chunks, int vec) {
   __shared__ double red[4];
   const int c = blockIdx.y, chunk = blockIdx.x;
   const long long total = (long long)N * HW;
   double s = 0.0;       // fp64 from the first addition on: these sums run over 1e5..1e7 terms that mostly cancel
-  if ((HW & 3) == 0 && (total >> 2) < 0x7fffffffLL) {
+  if (vec) {      // HW % 4 == 0, N * HW / 4 < 2^31 and a / b 16-byte aligned (decided by the host)
     // 16-byte loads and 32-bit index arithmetic (the scalar form with a 64-bit division per element ran at 2.8 TB/s)
     const unsigned hw4 = (unsigned)(HW >> 2), total4 = (unsigned)(total >> 2);
     const float4* a4 = reinterpret_cast<const float4*>(a);
@@ -739,7 +738,7 @@ inline int channel_chunks(int N, long long HW) {
 template <int T>  // threads cooperating on one plane: 64 or 256
 __global__ __launch_bounds__(256) void instnorm_stats_kernel(const float* __restrict__ x, float* __restrict__ mean,
                                                              float* __restrict__ rstd, long long planes,
-                                                             long long HW, float eps) {
+                                                             long long HW, float eps, int vec) {
   __shared__ double red[2][4];
   const int sub = (T == 64) ? (threadIdx.x >> 6) : 0;
   const int t = (T == 64) ? (threadIdx.x & 63) : threadIdx.x;
@@ -747,7 +746,7 @@ __global__ __launch_bounds__(256) void instnorm_stats_kernel(const float* __rest
   double s = 0.0, ss = 0.0;
   if (pl < planes) {
     const float* p = x + pl * HW;
-    if ((HW & 3) == 0) {
+    if (vec) {      // HW % 4 == 0 and x 16-byte aligned (decided by the host)
       const float4* p4 = reinterpret_cast<const float4*>(p);
       for (long long i = t; i < (HW >> 2); i += T) {
         const float4 v = p4[i];
@@ -1714,7 +1713,9 @@ int ganlab_pool2_f32(const float* x, float* y, long long planes, int Hout, int W
 int ganlab_bias_act_f32(const float* x, const float* bias, const float* noise, const float* noise_w, float* y,
                         int N, int C, long long HW, float bias_scale, int act, float slope, void* stream) {
   if (!x || !y || N <= 0 || C <= 0 || HW <= 0 || (noise && !noise_w)) return GANLAB_EINVAL;
-  if ((HW & 3) == 0)
+  const uintptr_t ptrs =      // the float4 form needs every operand 16-byte aligned (noise may be NULL)
+      reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(noise);
+  if ((HW & 3) == 0 && (ptrs & 15) == 0)
     GL_LAUNCH(bias_act_kernel<4>, dim3(ew_blocks((long long)N * C * HW / 4)), dim3(256), 0, ST, x, bias,
                        noise, noise_w, y, N, C, HW, bias_scale, act, slope);
   else
@@ -1725,7 +1726,11 @@ int ganlab_bias_act_f32(const float* x, const float* bias, const float* noise, c
 
 int ganlab_act_bwd_f32(const float* gy, const float* y, float* gz, long long n, float slope, void* stream) {
   if (!gy || !y || !gz || n <= 0) return GANLAB_EINVAL;
-  GL_LAUNCH(act_bwd_kernel, dim3(ew_blocks((n >> 2) + 4)), dim3(256), 0, ST, gy, y, gz, n, slope);
+  const uintptr_t ptrs = reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gz);
+  if ((ptrs & 15) == 0)
+    GL_LAUNCH(act_bwd_kernel, dim3(ew_blocks((n >> 2) + 4)), dim3(256), 0, ST, gy, y, gz, n, n >> 2, slope);
+  else      // a contiguous view may start at any element: every element through the scalar tail
+    GL_LAUNCH(act_bwd_kernel, dim3(ew_blocks(n)), dim3(256), 0, ST, gy, y, gz, n, 0LL, slope);
   return GL_CHECK_LAUNCH();
 }
 
@@ -1738,8 +1743,10 @@ int ganlab_channel_sum_f32(const float* a, const float* b, float* out, int N, in
   if (!a || !out || N <= 0 || C <= 0 || HW <= 0) return GANLAB_EINVAL;
   const int chunks = channel_chunks(N, HW);
   if (!workspace || workspace_bytes < (size_t)C * chunks * sizeof(double)) return GANLAB_EWORKSPACE;
+  const int vec = ((HW & 3) == 0 && (((long long)N * HW) >> 2) < 0x7fffffffLL &&
+                   ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0) ? 1 : 0;
   GL_LAUNCH(channel_sum_stage1, dim3(chunks, C), dim3(256), 0, ST, a, b, (double*)workspace, N, C, HW,
-                     chunks);
+                     chunks, vec);
   GL_LAUNCH(channel_sum_stage2, dim3(C), dim3(64), 0, ST, (const double*)workspace, out, C, chunks, scale);
   return GL_CHECK_LAUNCH();
 }
@@ -2016,12 +2023,14 @@ int ganlab_act_bwd_blur_f32(const float* g, const float* y, const float* noise, 
 int ganlab_instnorm_stats_f32(const float* x, float* mean, float* rstd, long long planes, long long HW, float eps,
                               void* stream) {
   if (!x || !mean || !rstd || planes <= 0 || HW <= 0) return GANLAB_EINVAL;
+  // float4 loads need whole float4 planes AND a 16-byte aligned base (a contiguous view may start at any element)
+  const int vec = ((HW & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) ? 1 : 0;
   if (HW >= 1024)
     GL_LAUNCH(instnorm_stats_kernel<256>, dim3((unsigned)planes), dim3(256), 0, ST, x, mean, rstd, planes,
-                       HW, eps);
+                       HW, eps, vec);
   else
     GL_LAUNCH(instnorm_stats_kernel<64>, dim3((unsigned)((planes + 3) / 4)), dim3(256), 0, ST, x, mean,
-                       rstd, planes, HW, eps);
+                       rstd, planes, HW, eps, vec);
   return GL_CHECK_LAUNCH();
 }
 
@@ -2036,7 +2045,8 @@ int ganlab_row_stats_f32(const float* x, float* mean, float* rstd, long long row
                          void* workspace, size_t workspace_bytes, void* stream) {
   if (!x || !mean || !rstd || rows <= 0 || M <= 0) return GANLAB_EINVAL;
   const int chunks = act_stats_chunks(M / 4);
-  if ((M & 3) != 0 || chunks < 2 || rows * chunks > 0x7fffffffLL)      // short or ragged rows: one block per row
+  // short, ragged or misaligned rows (the chunk kernel loads float4): one block per row
+  if ((M & 3) != 0 || chunks < 2 || rows * chunks > 0x7fffffffLL || (reinterpret_cast<uintptr_t>(x) & 15) != 0)
     return ganlab_instnorm_stats_f32(x, mean, rstd, rows, M, eps, stream);
   if (!workspace || workspace_bytes < ganlab_row_stats_workspace(rows, M)) return GANLAB_EWORKSPACE;
   double* sp = reinterpret_cast<double*>(workspace);
@@ -2155,7 +2165,7 @@ int ganlab_mbstd_bwdbwd_f32(const float* x, const float* gstat, const float* ggx
 int ganlab_chan_affine_f32(const float* x, const float* scale, const float* shift, float* y, int N, int C,
                            long long HW, void* stream) {
   if (!x || !y || N <= 0 || C <= 0 || HW <= 0) return GANLAB_EINVAL;
-  if ((HW & 3) == 0)
+  if ((HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0)
     GL_LAUNCH(chan_affine_kernel<4>, dim3(ew_blocks((long long)N * C * HW / 4)), dim3(256), 0, ST, x, scale, shift, y,
               N, C, HW);
   else
