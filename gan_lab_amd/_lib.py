@@ -327,6 +327,8 @@ SIGNATURES = {
     'ganlab_cr_imsd_workspace': (_c_sz, [_c_ll]),
     'ganlab_cr_imsd_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_p, _c_sz, _c_p]),
     'ganlab_cr_imsd_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_p]),
+    'ganlab_moments_accum_f32': (_c_int, [_c_p, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p]),
+    'ganlab_kid_rowsums_f32': (_c_int, [_c_p, _c_ll, _c_p, _c_ll, _c_int, _c_f, _c_f, _c_int, _c_p, _c_p]),
     'ganlab_step_scalars_size': (_c_int, []),
     'ganlab_set_step_scalars': (_c_int, [_c_p, _c_u64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
 }

@@ -31,6 +31,13 @@ validation images and the validation reals: k-nearest-neighbour statistics that 
 pretrained network; all three models) with ``prdc_k`` (the neighbour that sets a row's radius, in [1, 16], default 5) and
 ``prdc_res`` (a power of two >= 4, default 32: images are reduced by 2x2 means to at most this size and flattened into the feature
 rows), validated when the learner is built;
+``'fd'`` and ``'kid'`` as entries of ``gen_metrics`` (all three models): the Frechet distance (frechet.py) and the Kernel Inception
+Distance (kid.py: the unbiased MMD^2 under the cubic polynomial kernel, over the whole sets and as mean / standard deviation over
+blocks of ``kid_block`` rows, default 1000, >= 2) between the generated validation images and the validation reals.  The feature
+rows are ``prdc.features`` of the images at ``fd_res`` (default 16: 768 features for RGB, so the host-side eigenproblems of the
+distance stay well under a second) and ``kid_res`` (default 32), powers of two >= 4 like ``prdc_res``; with rows of a pretrained
+embedding fed to ``frechet.Frechet`` / ``kid.KID`` by hand the numbers are FID and KID proper.  Validated when the learner is
+built;
 ``spectral_norm`` (ResNet GAN only; False = off): every Conv2dEx / LinearEx weight of the critic is divided by its largest
 singular value, estimated by one power iteration per critic update (spectral_norm.py; excludes ``use_equalized_lr``; validated
 when the learner is built), and ``loss='hinge'`` (ResNet GAN only) is the loss usually trained with it - with both on,
@@ -137,6 +144,7 @@ def _spec(model_type):
         ('swd_nhoods', int, 128), ('swd_dir_repeats', int, 4), ('swd_dirs_per_repeat', int, 128), ('swd_seed', int, 0),
         ('msssim_range', float, 2.0), ('spectrum_window', str.casefold, 'hann'),
         ('prdc_k', int, 5), ('prdc_res', int, 32),
+        ('fd_res', int, 16), ('kid_res', int, 32), ('kid_block', int, 1000),
         ('self_attention', _str_or_none, None), ('cgan', _str_or_none, None),
     ]
     if model_type == 'ResNet GAN':

@@ -1695,6 +1695,52 @@ def prdc_cross(queries, keys, radii, radius_of='key', query_norms=None, key_norm
     return count, dmin, imin
 
 
+# ---- Frechet moments and KID row sums (csrc/frechet.hip, csrc/kid.hip; composed in gan_lab_amd/frechet.py and kid.py) ------------
+MOMENTS_MAX_DIM = 4096               # ganlab_moments_accum_f32: a (D, D) float64 second-moment matrix of 128 MiB
+
+
+def _accumulator(t, shape, what):
+    """A float64 tensor a kernel adds into through its raw pointer: a non-contiguous view is an error."""
+    if isinstance(t, torch.Tensor) and (tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
+        raise ValueError(f'{what}: must be a contiguous {tuple(shape)} tensor, got {tuple(t.shape)} with strides {t.stride()}')
+    return _ct(t, torch.float64, what)
+
+
+def moments_accum(rows, pivot, sum, gram):
+    """``sum[a] += sum_i (x_ia - c_a)`` and ``gram[a][b] += sum_i (x_ia - c_a)(x_ib - c_b)`` over the rows of an (n, D) fp32
+    matrix, ``c`` the (D,) fp32 ``pivot``; ``sum`` (D,) and ``gram`` (D, D) are float64 and accumulated into (zero them before the
+    first call).  ``gram`` is written in full and stays exactly symmetric.  D <= 4096."""
+    rows = _prdc_rows(rows, 'moments_accum rows')
+    n, d = rows.shape
+    if d > MOMENTS_MAX_DIM:
+        raise ValueError(f'moments_accum: the width must be at most {MOMENTS_MAX_DIM}, got {d}')
+    pivot = _prdc_vector(pivot, torch.float32, d, 'moments_accum pivot')
+    sum = _accumulator(sum, (d,), 'moments_accum sum')
+    gram = _accumulator(gram, (d, d), 'moments_accum gram')
+    check(_lib.lib().ganlab_moments_accum_f32(_p(rows), n, d, _p(pivot), _p(sum), _p(gram), _st()), 'moments_accum')
+    return sum, gram
+
+
+def kid_rowsums(queries, keys, gamma, coef0=1.0, exclude_diag=False, out=None):
+    """(M,) float64: ``out[i] = sum_j (gamma q_i.k_j + coef0)^3`` of the queries (M, D) against the keys (N, D); the dot product
+    and ``gamma dot + coef0`` (one fma) in fp32, the cube and the sum in float64.  ``exclude_diag`` leaves ``j == i`` out by index
+    and needs M == N."""
+    queries, keys = _prdc_rows(queries, 'kid_rowsums queries'), _prdc_rows(keys, 'kid_rowsums keys')
+    (m, d), (n, dk) = queries.shape, keys.shape
+    if d != dk:
+        raise ValueError(f'kid_rowsums: queries and keys must have one width, got {d} and {dk}')
+    if exclude_diag and m != n:
+        raise ValueError(f'kid_rowsums: exclude_diag leaves out the term j == i and needs as many queries as keys, got {m} and {n}')
+    gamma, coef0 = float(gamma), float(coef0)
+    if gamma != gamma or coef0 != coef0:
+        raise ValueError(f'kid_rowsums: gamma and coef0 must be numbers, got {gamma!r} and {coef0!r}')
+    out = torch.empty((m,), dtype=torch.float64, device=queries.device) if out is None else \
+        _prdc_vector(out, torch.float64, m, 'kid_rowsums out')
+    check(_lib.lib().ganlab_kid_rowsums_f32(_p(queries), m, _p(keys), n, d, gamma, coef0, 1 if exclude_diag else 0, _p(out),
+                                            _st()), 'kid_rowsums')
+    return out
+
+
 # ---- multi-scale structural similarity (csrc/msssim.hip; composed in gan_lab_amd/msssim.py) -------------------------------------
 MSSSIM_LEVELS = 5                    # GANLAB_MSSSIM_LEVELS (include/ganlab_hip.h)
 

@@ -22,7 +22,7 @@ import warnings
 import torch
 from torch import nn
 
-from .. import msssim, ops, parallel, prdc, rng, spectrum, swd
+from .. import frechet, kid, msssim, ops, parallel, prdc, rng, spectrum, swd
 from .._int import LearnerConfigCopy
 from ..optim import EwmaTracker, ParamArena
 from ..resnetgan.learner import GANLearner
@@ -491,7 +491,8 @@ class ProGANLearner(GANLearner):
                                                         valid_dl=valid_dl if swd.wanted(c.gen_metrics) or
                                                         msssim.wanted(c.gen_metrics) or
                                                         spectrum.wanted(c.gen_metrics) or
-                                                        prdc.wanted(c.gen_metrics) else None)
+                                                        prdc.wanted(c.gen_metrics) or frechet.wanted(c.gen_metrics) or
+                                                        kid.wanted(c.gen_metrics) else None)
                             if parallel.rank() == 0:
                                 print('|\n', 'Generator Validation Metrics:\n', *vals)
                     if num_gen_iters == 0:
@@ -583,6 +584,13 @@ class ProGANLearner(GANLearner):
                              "reals and cannot be listed among the critic's metrics (config.disc_metrics)")
         if want_pr and valid_dl is None:
             raise ValueError("'prdc' needs the validation reals: pass valid_dl (train(train_dl, valid_dl, z_valid_dl))")
+        want_fd, want_kid = 'fd' in metrics, 'kid' in metrics
+        for name, want in (('fd', want_fd), ('kid', want_kid)):
+            if want and metrics_type != 'generator':
+                raise ValueError(f"'{name}' is a generator metric: it compares the generated validation images with the "
+                                 f"validation reals and cannot be listed among the critic's metrics (config.disc_metrics)")
+            if want and valid_dl is None:
+                raise ValueError(f"'{name}' needs the validation reals: pass valid_dl (train(train_dl, valid_dl, z_valid_dl))")
         if want_grid and (self.ds_mean is None or self.data_config is None):
             self._update_data_config(raise_exception=True)
         self.disc_model.eval()
@@ -601,11 +609,13 @@ class ProGANLearner(GANLearner):
                 self._grid_fill = 0
             self._img_grid_constructed = False
             table = {m: torch.zeros(self.batch_size, n_batches, device=c.dev) for m in metrics
-                     if m not in ('swd', 'msssim', 'spectrum', 'prdc')}
+                     if m not in ('swd', 'msssim', 'spectrum', 'prdc', 'fd', 'kid')}
             swd_eval, swd_left = self._swd_begin(n_z, valid_dl) if want_swd else (None, 0)
             ms_fake, ms_real, ms_fake_left, ms_real_left = self._msssim_begin(n_z, valid_dl) if want_ms else (None, None, 0, 0)
             sp_fake, sp_real, sp_left = self._spectrum_begin(n_z, valid_dl) if want_sp else (None, None, 0)
             pr_eval, pr_left = self._prdc_begin(n_z, valid_dl) if want_pr else (None, 0)
+            fd_eval, fd_left = self._fd_begin(n_z, valid_dl) if want_fd else (None, 0)
+            kid_eval, kid_left = self._kid_begin(n_z, valid_dl) if want_kid else (None, 0)
             for n, zbatch in enumerate(z_valid_dl):
                 zb = zbatch[0].to(c.dev).float()
                 gen_labels = zbatch[1].cpu() if len(zbatch) > 1 else None
@@ -613,7 +623,8 @@ class ProGANLearner(GANLearner):
                 xgen = self.gen_model(zb)
                 ms_fake_now = ms_fake_left > 0 and k == self.batch_size
                 ms_real_now = ms_real_left > 0 and k == self.batch_size
-                both_left = max(swd_left, sp_left, pr_left)   # 'swd', 'spectrum' and 'prdc' score the same two sets of equal size
+                # 'swd', 'spectrum', 'prdc', 'fd' and 'kid' score the same two sets of equal size
+                both_left = max(swd_left, sp_left, pr_left, fd_left, kid_left)
                 if both_left > 0 or ms_fake_now or ms_real_now:
                     # whole batches only, so that both sets hold the same images count; the generator evaluated is the one
                     # this method evaluates, the reals follow its fade-in.  'swd', 'msssim' and 'spectrum' share the scored
@@ -623,7 +634,7 @@ class ProGANLearner(GANLearner):
                         xb = next(valid_iter)[0].to(c.dev).float()
                         if k != len(xb) or (both_left > 0 and k > both_left):
                             which = "'swd'" if swd_left > 0 else "'spectrum'" if sp_left > 0 else \
-                                "'prdc'" if pr_left > 0 else "'msssim'"
+                                "'prdc'" if pr_left > 0 else "'fd'" if fd_left > 0 else "'kid'" if kid_left > 0 else "'msssim'"
                             raise ValueError(f"{which}: validation latents and reals must come in equal batches (got {k} and "
                                              f"{len(xb)} with {both_left if both_left > 0 else ms_real_left} images to go)")
                         xr = self.fade_in_real(xb)
@@ -640,6 +651,14 @@ class ProGANLearner(GANLearner):
                         pr_eval.feed_fake(prdc.features(scored, c.prdc_res))
                         pr_eval.feed_real(prdc.features(xr, c.prdc_res))
                         pr_left -= k
+                    if fd_left > 0:
+                        fd_eval.feed_fake(prdc.features(scored, c.fd_res))
+                        fd_eval.feed_real(prdc.features(xr, c.fd_res))
+                        fd_left -= k
+                    if kid_left > 0:
+                        kid_eval.feed_fake(prdc.features(scored, c.kid_res))
+                        kid_eval.feed_real(prdc.features(xr, c.kid_res))
+                        kid_left -= k
                     if ms_fake_now:
                         ms_fake.feed(scored)
                         ms_fake_left -= k
@@ -690,6 +709,12 @@ class ProGANLearner(GANLearner):
             if want_pr:
                 vals['prdc'] = pr_eval.result()
                 swd_lines = swd_lines + [(name, vals['prdc'][name]) for name in ('precision', 'recall', 'density', 'coverage')]
+            if want_fd:
+                vals['fd'] = fd_eval.result()
+                swd_lines = swd_lines + [('fd', vals['fd']['fd'])]
+            if want_kid:
+                vals['kid'] = kid_eval.result()
+                swd_lines = swd_lines + [('kid', vals['kid']['kid'])]
         finally:
             self.gen_model.train()
             self.disc_model.train()
@@ -697,7 +722,7 @@ class ProGANLearner(GANLearner):
         names = metrics + [name for name, _ in swd_lines]
         width = '%-' + str(max(len(m) for m in names) + 3) + 's'
         return ['    ' + (width % (m + ':')) + '%.4g' % vals[m] + '\n' for m in metrics
-                if m not in ('image grid', 'swd', 'msssim', 'spectrum', 'prdc')] + \
+                if m not in ('image grid', 'swd', 'msssim', 'spectrum', 'prdc', 'fd', 'kid')] + \
             ['    ' + (width % (name + ':')) + (v if isinstance(v, str) else '%.4g' % v) + '\n' for name, v in swd_lines]
 
     def _swd_begin(self, n_z, valid_dl):
@@ -814,6 +839,36 @@ class ProGANLearner(GANLearner):
             self._prdc_eval = (key, prdc.PRDC(prdc.feature_dim(3, res, c.prdc_res), n_use, n_use, k=c.prdc_k, device=c.dev))
         self._prdc_eval[1].reset()
         return self._prdc_eval[1], n_use
+
+    def _fd_begin(self, n_z, valid_dl):
+        """(the Frechet evaluation of this resolution, images per set), counted as ``_prdc_begin`` counts them; the rows are the
+        images reduced by 2x2 means to at most ``config.fd_res`` pixels (prdc.features)."""
+        c = self.config
+        res = int(self.gen_model.curr_res)
+        n_use = min(n_z, len(valid_dl.dataset)) // self.batch_size * self.batch_size
+        if n_use < 1:
+            raise ValueError(f"'fd' needs at least one whole batch of {self.batch_size} validation latents and reals (got "
+                             f"{n_z} and {len(valid_dl.dataset)})")
+        key = (res, c.fd_res)
+        if getattr(self, '_fd_eval', None) is None or self._fd_eval[0] != key:
+            self._fd_eval = (key, frechet.Frechet(prdc.feature_dim(3, res, c.fd_res), device=c.dev))
+        self._fd_eval[1].reset()
+        return self._fd_eval[1], n_use
+
+    def _kid_begin(self, n_z, valid_dl):
+        """(the KID evaluation of this resolution, images per set), counted as ``_prdc_begin`` counts them; the rows are the
+        images reduced by 2x2 means to at most ``config.kid_res`` pixels (prdc.features)."""
+        c = self.config
+        res = int(self.gen_model.curr_res)
+        n_use = min(n_z, len(valid_dl.dataset)) // self.batch_size * self.batch_size
+        if n_use < 1:
+            raise ValueError(f"'kid' needs at least one whole batch of {self.batch_size} validation latents and reals (got "
+                             f"{n_z} and {len(valid_dl.dataset)})")
+        key = (res, n_use, c.kid_res, c.kid_block)
+        if getattr(self, '_kid_eval', None) is None or self._kid_eval[0] != key:
+            self._kid_eval = (key, kid.KID(prdc.feature_dim(3, res, c.kid_res), n_use, n_use, block=c.kid_block, device=c.dev))
+        self._kid_eval[1].reset()
+        return self._kid_eval[1], n_use
 
     def _spectrum_finish(self, fake, real):
         """(the dict kept in last_metrics: both profiles in dB, for plotting, and the two distances; [(line name, value)])."""

@@ -79,6 +79,10 @@ class GANLearner(object):
         # ... and the k-nearest-neighbour precision / recall / density / coverage's ('prdc' in config.gen_metrics; prdc.py)
         from .. import prdc
         prdc.validate_config(config)
+        # ... and the Frechet distance's and the Kernel Inception Distance's ('fd' / 'kid' in config.gen_metrics; frechet.py, kid.py)
+        from .. import frechet, kid
+        frechet.validate_config(config)
+        kid.validate_config(config)
         # self-attention (config.self_attention; attention.py): a ResNet GAN option, and first order only - a critic with a
         # block excludes the gradient penalties
         from .. import attention
@@ -194,8 +198,8 @@ class GANLearner(object):
         self.reducer = parallel.GradReducer()
         self.log_every = getattr(config, 'log_every', 50)
         self.last_losses = {}
-        self.last_metrics = {}      # compute_metrics: {'generator': {'prdc': {...}}}
-        self._prdc_eval = None
+        self.last_metrics = {}      # compute_metrics: {'generator': {'prdc': {...}, 'fd': {...}, 'kid': {...}}}
+        self._prdc_eval = self._fd_eval = self._kid_eval = None
         self._loss = config.loss.casefold()
         self._set_loss()
         self._make_arenas()
@@ -411,40 +415,56 @@ class GANLearner(object):
                 net.train(was_training)
 
     def compute_metrics(self, metrics, metrics_type, z_valid_dl, valid_dl=None):
-        """Validation metrics of the ResNet GAN over the validation latents and reals.  ``'prdc'`` - improved precision / recall
-        and density / coverage (prdc.py) - is the one metric this learner has; any other entry raises.  The generated set is
+        """Validation metrics of the ResNet GAN over the validation latents and reals: ``'prdc'`` - improved precision / recall
+        and density / coverage (prdc.py) -, ``'fd'`` - the Frechet distance (frechet.py) - and ``'kid'`` - the Kernel Inception
+        Distance (kid.py); any other entry raises.  The generated set is
         ``generate(zs=zb, truncation=None, time_average=True)`` per batch of ``z_valid_dl`` (the averaged generator where there
         is one; with ``config.cgan`` the classes are drawn as ``generate`` draws them), the real set the batches of ``valid_dl``,
-        both reduced to rows by ``prdc.features`` and truncated to min(latents, reals) in whole batches.  The process stream is
-        put back where it was, so an evaluation does not move the training run.  Returns the formatted lines; the numbers are
-        kept in ``self.last_metrics['generator']['prdc']``."""
-        from .. import prdc, rng
+        both reduced to rows by ``prdc.features`` (at ``prdc_res`` / ``fd_res`` / ``kid_res``) and truncated to min(latents, reals)
+        in whole batches; the images are generated once for all metrics.  The process stream is put back where it was, so an
+        evaluation does not move the training run.  Returns the formatted lines; the numbers are kept in
+        ``self.last_metrics['generator'][name]``."""
+        from .. import frechet, kid, prdc, rng
         c = self.config
         metrics_type = metrics_type.casefold()
         if metrics_type not in ('generator', 'critic', 'discriminator'):
             raise Exception('Invalid metrics_type. Only "generator", "critic", or "discriminator" are accepted.')
         metrics = [m.casefold() for m in metrics]
-        unsupported = [m for m in metrics if m != 'prdc']
+        unsupported = [m for m in metrics if m not in ('prdc', 'fd', 'kid')]
         if unsupported:
-            raise ValueError(f"the ResNet GAN learner computes 'prdc' only; unsupported metrics: {unsupported}")
+            raise ValueError(f"the ResNet GAN learner computes 'prdc', 'fd' and 'kid' only; unsupported metrics: {unsupported}")
         if not metrics:
             return []
+        first = "'" + metrics[0] + "'"
         if metrics_type != 'generator':
-            raise ValueError("'prdc' is a generator metric: it compares the generated validation images with the validation "
-                             "reals and cannot be listed among the critic's metrics (config.disc_metrics)")
+            raise ValueError(f"{first} is a generator metric: it compares the generated validation images with the validation "
+                             f"reals and cannot be listed among the critic's metrics (config.disc_metrics)")
         if z_valid_dl is None or valid_dl is None:
-            raise ValueError("'prdc' needs the validation latents and reals: pass z_valid_dl and valid_dl "
-                             "(train(train_dl, valid_dl, z_valid_dl))")
+            raise ValueError(f"{first} needs the validation latents and reals: pass z_valid_dl and valid_dl "
+                             f"(train(train_dl, valid_dl, z_valid_dl))")
         n_use = min(len(z_valid_dl.dataset), len(valid_dl.dataset)) // self.batch_size * self.batch_size
         if n_use < 1:
-            raise ValueError(f"'prdc' needs at least one whole batch of {self.batch_size} validation latents and reals (got "
+            raise ValueError(f"{first} needs at least one whole batch of {self.batch_size} validation latents and reals (got "
                              f"{len(z_valid_dl.dataset)} and {len(valid_dl.dataset)})")
-        key = (n_use, c.prdc_k, c.prdc_res)
-        if self._prdc_eval is None or self._prdc_eval[0] != key:
-            dim = prdc.feature_dim(3, c.res_samples, c.prdc_res)
-            self._prdc_eval = (key, prdc.PRDC(dim, n_use, n_use, k=c.prdc_k, device=c.dev))
-        ev = self._prdc_eval[1]
-        ev.reset()
+        evals = {}                   # name -> (evaluation, resolution of its feature rows)
+        if 'prdc' in metrics:
+            key = (n_use, c.prdc_k, c.prdc_res)
+            if self._prdc_eval is None or self._prdc_eval[0] != key:
+                dim = prdc.feature_dim(3, c.res_samples, c.prdc_res)
+                self._prdc_eval = (key, prdc.PRDC(dim, n_use, n_use, k=c.prdc_k, device=c.dev))
+            evals['prdc'] = (self._prdc_eval[1], c.prdc_res)
+        if 'fd' in metrics:
+            if self._fd_eval is None or self._fd_eval[0] != c.fd_res:
+                self._fd_eval = (c.fd_res, frechet.Frechet(prdc.feature_dim(3, c.res_samples, c.fd_res), device=c.dev))
+            evals['fd'] = (self._fd_eval[1], c.fd_res)
+        if 'kid' in metrics:
+            key = (n_use, c.kid_res, c.kid_block)
+            if self._kid_eval is None or self._kid_eval[0] != key:
+                dim = prdc.feature_dim(3, c.res_samples, c.kid_res)
+                self._kid_eval = (key, kid.KID(dim, n_use, n_use, block=c.kid_block, device=c.dev))
+            evals['kid'] = (self._kid_eval[1], c.kid_res)
+        for ev, _ in evals.values():
+            ev.reset()
         offset, left, valid_iter = rng._STATE['offset'], n_use, iter(valid_dl)
         try:
             for zbatch in z_valid_dl:
@@ -453,17 +473,22 @@ class GANLearner(object):
                 zb = zbatch[0].to(c.dev).float()
                 xb = next(valid_iter)[0].to(c.dev).float()
                 if len(zb) != len(xb) or len(zb) > left:
-                    raise ValueError(f"'prdc': validation latents and reals must come in equal batches (got {len(zb)} and "
+                    raise ValueError(f"{first}: validation latents and reals must come in equal batches (got {len(zb)} and "
                                      f"{len(xb)} with {left} images to go)")
-                ev.feed_fake(prdc.features(self.generate(zs=zb, truncation=None, time_average=True), c.prdc_res))
-                ev.feed_real(prdc.features(xb, c.prdc_res))
+                xgen = self.generate(zs=zb, truncation=None, time_average=True)
+                for ev, res in evals.values():
+                    ev.feed_fake(prdc.features(xgen, res))
+                    ev.feed_real(prdc.features(xb, res))
                 left -= len(zb)
         finally:
             rng._STATE['offset'] = offset
-        out = ev.result()
-        self.last_metrics[metrics_type] = {'prdc': out}
-        names = ('precision', 'recall', 'density', 'coverage')
-        return ['    ' + ('%-12s' % (name + ':')) + '%.4g' % out[name] + '\n' for name in names]
+        out = {name: evals[name][0].result() for name in ('prdc', 'fd', 'kid') if name in evals}
+        self.last_metrics[metrics_type] = out
+        lines = []
+        if 'prdc' in out:
+            lines += [(name, out['prdc'][name]) for name in ('precision', 'recall', 'density', 'coverage')]
+        lines += [(name, out[name][name]) for name in ('fd', 'kid') if name in out]
+        return ['    ' + ('%-12s' % (name + ':')) + '%.4g' % v + '\n' for name, v in lines]
 
     def _pair_critic_batches(self, xgenb, xb):
         """May the critic see the generated and the real batch as one?  Only when no critic layer couples samples (a
@@ -590,17 +615,19 @@ class GANLearner(object):
             per_epoch = max(self.dataset_sz // self.batch_size * self.batch_size, 1)
             self.tot_num_epochs = num_main_iters * self.batch_size * num_disc_iters // per_epoch + 1
         loss_d = loss_g = None
-        # the one validation metric of this learner ('prdc' in config.gen_metrics; compute_metrics): with both loaders only
-        from .. import prdc
-        want_prdc = prdc.wanted(c.gen_metrics) and valid_dl is not None and z_valid_dl is not None
+        # the validation metrics of this learner ('prdc' / 'fd' / 'kid' in config.gen_metrics; compute_metrics): with both
+        # loaders only
+        from .. import frechet, kid, prdc
+        valid_metrics = [name for name, mod in (('prdc', prdc), ('fd', frechet), ('kid', kid)) if mod.wanted(c.gen_metrics)]
+        want_valid = bool(valid_metrics) and valid_dl is not None and z_valid_dl is not None
         try:
             for itr in range(num_main_iters):
                 # ---------------------------- TRAIN GENERATOR ----------------------------
                 self.set_requires_grad_disc(False)
                 for _ in range(num_gen_iters):
                     loss_g = self.g_step()
-                if want_prdc and ((itr + 1) % c.num_iters_valid == 0 or itr == 0):
-                    vals = self.compute_metrics(metrics=['prdc'], metrics_type='Generator', z_valid_dl=z_valid_dl,
+                if want_valid and ((itr + 1) % c.num_iters_valid == 0 or itr == 0):
+                    vals = self.compute_metrics(metrics=valid_metrics, metrics_type='Generator', z_valid_dl=z_valid_dl,
                                                 valid_dl=valid_dl)
                     if parallel.rank() == 0:
                         print('|\n', 'Generator Validation Metrics:\n', *vals)

@@ -993,6 +993,21 @@ int ganlab_cr_imsd_fwd_f32(const float* a, const float* b, float* out, long long
                            void* stream);
 int ganlab_cr_imsd_bwd_f32(const float* a, const float* b, const float* gout, float* ga, float* gb, long long n, void* stream);
 
+/* ---- Frechet distance and Kernel Inception Distance (Binkowski et al. 2018) between two sets of fp32 feature rows of any
+ * embedding (csrc/frechet.hip, csrc/kid.hip; composed in gan_lab_amd/frechet.py and gan_lab_amd/kid.py).  Rows are
+ * (rows, D) row-major.  Products on the exact-fp32 MFMA in chains of at most 64 terms (moments: 32), every longer sum in float64; no atomics,
+ * nothing is read back by the host, stream-ordered, bitwise reproducible.  A bad argument returns GANLAB_EINVAL.
+ *   moments_accum: sum[a] += sum_i (x_ia - c_a), gram[a][b] += sum_i (x_ia - c_a)(x_ib - c_b) over the n rows, c = pivot (D,) fp32,
+ *                  subtracted in fp32 on load; sum (D,) and gram (D, D) are float64 and accumulated into: zero them before the
+ *                  first launch.  gram is written in full (upper tiles and their mirrors) and stays exactly symmetric.
+ *                  1 <= D <= 4096, 1 <= n <= 2^30.
+ *   kid_rowsums:   out[i] = sum_j (gamma q_i.k_j + coef0)^3 over the N keys, for the M queries; out (M,) float64.
+ *                  t = fmaf(gamma, dot, coef0) in fp32, its cube and the sums in float64.  exclude_diag = 1 leaves j == i out by
+ *                  index (a duplicate row at another index counts) and requires M == N.  D >= 1, at most 2^30 rows per set. */
+int ganlab_moments_accum_f32(const float* rows, long long n, int D, const float* pivot, double* sum, double* gram, void* stream);
+int ganlab_kid_rowsums_f32(const float* q, long long M, const float* keys, long long N, int D, float gamma, float coef0,
+                           int exclude_diag, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
