@@ -264,6 +264,11 @@ SIGNATURES = {
     'ganlab_ada_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),
     'ganlab_ada_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),
     'ganlab_ada_update_f32': (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_f, _c_f, _c_p]),
+    'ganlab_ada_filter_bank': (_c_int, [_c_p]),
+    'ganlab_ada_ext_params_f32': (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_p, _c_int, _c_u64, _c_u64, _c_p]),
+    'ganlab_ada_ext_params_dev_f32': (_c_int, [_c_p, _c_int, _c_int, _c_int, _c_p, _c_int, _c_u64, _c_p, _c_u64, _c_p]),
+    'ganlab_ada_ext_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),
+    'ganlab_ada_ext_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),
     'ganlab_swd_down_f32': (_c_int, [_c_p, _c_p, _c_ll, _c_int, _c_int, _c_p]),
     'ganlab_swd_band_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_int, _c_int, _c_p]),
     'ganlab_swd_gather_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p]),

@@ -1,23 +1,31 @@
 """Adaptive discriminator augmentation (Karras et al., "Training Generative Adversarial Networks with Limited Data",
-NeurIPS 2020): every critic input, real and generated, goes through a random affine warp and a random color matrix whose
-elementary transforms each fire with probability p, and a controller moves p from the overfitting signal
-r_t = E[sign(D(real))].
+NeurIPS 2020): every critic input, real and generated, goes through a random affine warp, a random color matrix, a random
+band filter, additive noise and a cutout, whose elementary transforms each fire with probability p, and a controller moves p
+from the overfitting signal r_t = E[sign(D(real))].
 
-A policy is a comma-separated subset of ``blit``, ``geom``, ``color``, in that order and each at most once.  The kernels are
-csrc/ada.hip (DESIGN.md "ADA"); the parameters of a batch are (N, 32) rows drawn from the device Philox stream
-(``rng.ada_params``) at the p held in a small device block, which the controller kernel updates: the host never reads it in
-a step, so captured step graphs replay it."""
+A policy is a comma-separated subset of ``blit``, ``geom``, ``color``, ``filter``, ``noise``, ``cutout``, in that order (the
+order of application) and each at most once.  The kernels are csrc/ada.hip and csrc/ada_filter.hip (DESIGN.md "ADA"); the
+parameters of a batch are (N, 32) rows drawn from the device Philox stream (``rng.ada_params``) at the p held in a small
+device block, which the controller kernel updates: the host never reads it in a step, so captured step graphs replay it.
+The last three groups add (N, 16) ``ext`` rows and, for noise, a field of normals to a draw (``ops.AdaDraw``); a policy without
+them draws, launches and computes exactly what it did before they existed.
+
+Strengths are the paper's: four filter bands, each gated at p with a log2-normal gain of std 1, noise std 0.1 |z|, cutout
+size 0.5.  This project's addition: every normal is clamped to +-3 (as the geometric draws already are), which bounds the
+sum of |h| over a drawn filter by 8.21, its value over the corners of the clamp."""
 import torch
 
 from . import ops, rng
 
 BLIT, GEOM, COLOR = 1, 2, 4
-PARTS = (('blit', BLIT), ('geom', GEOM), ('color', COLOR))
-ROW = ops.ADA_ROW
+FILTER, NOISE, CUTOUT = ops.ADA_FILTER, ops.ADA_NOISE, ops.ADA_CUTOUT
+PARTS = (('blit', BLIT), ('geom', GEOM), ('color', COLOR), ('filter', FILTER), ('noise', NOISE), ('cutout', CUTOUT))
+ROW, EXT_ROW = ops.ADA_ROW, ops.ADA_EXT_ROW
 
 
 def parse_policy(policy):
-    """'blit,geom,color' -> bit mask.  Any other spelling, a repeated part or a part out of order raises ValueError."""
+    """'blit,geom,color' -> 7, 'blit,geom,color,filter,noise,cutout' -> 63: the bit mask.  Any other spelling, a repeated part
+    or a part out of order raises ValueError."""
     if not isinstance(policy, str):
         raise ValueError(f'ADA policy must be a string such as "blit,geom,color", got {policy!r}')
     names = [name for name, _ in PARTS]
@@ -80,6 +88,50 @@ def rows_from_matrices(M, C=None):
     return rows.float()
 
 
+def filter_bank():
+    """The (4, 43) float64 filter bank of the ``filter`` group, by the official recipe: from the sym2 wavelet
+    lo = [(1 - s), (3 - s), (3 + s), (1 + s)] / (4 sqrt 2), s = sqrt 3, and hi[k] = (-1)^k lo[k], the 7-tap
+    lo2 = conv(lo, reversed lo) / 2 and hi2 likewise; start from F = eye(4, 1) and for i = 1, 2, 3 upsample every row by 2
+    (zeros between, the last zero dropped), convolve every row with lo2 and add hi2 to the centre 7 taps of row i.  Row b is
+    the impulse response of octave band b; the four rows sum to the unit impulse at tap 21.  The library holds its own copy
+    (``ops.ada_filter_bank``)."""
+    import numpy as np
+    s = np.sqrt(3.0)
+    lo = np.array([1 - s, 3 - s, 3 + s, 1 + s]) / (4 * np.sqrt(2.0))
+    hi = lo * (-1.0) ** np.arange(4)
+    lo2, hi2 = np.convolve(lo, lo[::-1]) / 2, np.convolve(hi, hi[::-1]) / 2
+    bank = np.eye(4, 1)
+    for i in range(1, 4):
+        up = np.zeros((4, 2 * bank.shape[1]))
+        up[:, ::2] = bank
+        bank = np.stack([np.convolve(row, lo2) for row in up[:, :-1]])
+        c = bank.shape[1] // 2
+        bank[i, c - 3:c + 4] += hi2
+    return torch.from_numpy(bank)
+
+
+def ext_rows(g=None, sigma=None, rect=None, gates=None, n=None):
+    """(N, 16) hand-made ``ext`` rows on the host: ``g`` (N, 4) band gains (None: ones), ``sigma`` (N,) noise scales (None:
+    zeros), ``rect`` (N, 4) integer cutout rectangles (j0, j1, i0, i1) - columns [j0, j1), rows [i0, i1) - (None: empty).
+    ``gates`` (N,) overrides the gate mask, which is otherwise: all four band bits where g differs from ones, bit 4 where
+    sigma is not zero, bit 5 where the rectangle is not empty.  The kernels act on the mask: gains, sigma and rectangle
+    behind a closed bit are ignored.  The raw-draw columns stay zero."""
+    given = [torch.as_tensor(v).shape[0] for v in (g, sigma, rect, gates) if v is not None]
+    n = int(n) if n is not None else (given[0] if given else 1)
+    rows = torch.zeros(n, EXT_ROW, dtype=torch.float64)
+    rows[:, 0:4] = 1.0 if g is None else torch.as_tensor(g, dtype=torch.float64).reshape(n, 4)
+    if sigma is not None:
+        rows[:, 4] = torch.as_tensor(sigma, dtype=torch.float64).reshape(n)
+    if rect is not None:
+        rows[:, 5:9] = torch.as_tensor(rect, dtype=torch.float64).reshape(n, 4)
+    if gates is None:
+        rows[:, 9] = 15.0 * (rows[:, 0:4] != 1.0).any(dim=1) + 16.0 * (rows[:, 4] != 0) + \
+            32.0 * ((rows[:, 6] > rows[:, 5]) & (rows[:, 8] > rows[:, 7]))
+    else:
+        rows[:, 9] = torch.as_tensor(gates, dtype=torch.float64).reshape(n)
+    return rows.float()
+
+
 class AdaptiveAugment(object):
     """``aug = AdaptiveAugment('blit,geom,color', p=0.2, target=None); y = aug(x)`` - draws fresh rows unless ``params`` is
     given.  ``target`` None keeps p fixed; otherwise ``update(real_logits)`` after every critic pass accumulates
@@ -108,11 +160,15 @@ class AdaptiveAugment(object):
         return float(self.state[0].item())
 
     def draw(self, n, h, w, device='cuda'):
+        """What ``__call__`` takes as ``params``: the (n, 32) rows, or with a filter, noise or cutout group an ``ops.AdaDraw``
+        (rows, ext rows, noise field), which slices along the batch like the rows do."""
         return rng.ada_params(n, h, w, self.state, self.mask, device)
 
     def __call__(self, x, params=None):
         if params is None:
             params = self.draw(x.shape[0], x.shape[2], x.shape[3], x.device)
+        if isinstance(params, ops.AdaDraw):
+            return ops.ada_augment(x, params.params, params.ext, params.noise)
         return ops.ada_augment(x, params)
 
     def update(self, real_logits):

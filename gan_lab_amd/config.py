@@ -10,7 +10,8 @@ bs//2 and 1024 -> bs//4) and pickles the Namespace to ``<this dir>/.config.p`` w
 New, optional fields (ignored by the reference): ``log_every``, ``compute_dtype`` ('f32' = the reference's
 arithmetic, 'bf16' = BASELINE config #2: bf16-compute 3x3 convolutions with fp32 storage / masters), ``diffaugment``
 (None = off, or a DiffAugment policy such as 'color,translation,cutout' applied to every critic input: augment.py;
-validated when the learner is built), ``ada`` (None = off, or an ADA policy such as 'blit,geom,color': ada.py) with
+validated when the learner is built), ``ada`` (None = off, or an ADA policy, a comma-separated subset of blit, geom,
+color, filter, noise, cutout in that order such as 'blit,geom,color' or 'blit,geom,color,filter,noise,cutout': ada.py) with
 ``ada_p`` (initial, or fixed, augmentation probability), ``ada_target`` (the r_t the controller steers to; None =
 fixed p), ``ada_interval`` (critic iterations per adjustment) and ``ada_kimg`` (thousands of images for p to travel 0 -> 1);
 ``'swd'`` as an entry of ``gen_metrics`` (the sliced Wasserstein distance of swd.py between the validation reals and the generated

@@ -1453,6 +1453,79 @@ def k_ada(x, params, adjoint=False):
     return out
 
 
+ADA_EXT_ROW, ADA_EXT_COUNTERS, ADA_FILTER_TAPS = 16, 4, 43      # GANLAB_ADA_EXT_ROW, ..._EXT_COUNTERS, ..._FILTER_TAPS
+ADA_FILTER, ADA_NOISE, ADA_CUTOUT = 8, 16, 32       # GANLAB_ADA_FILTER, GANLAB_ADA_NOISE, GANLAB_ADA_CUTOUT
+ADA_NEW_GROUPS = ADA_FILTER | ADA_NOISE | ADA_CUTOUT
+
+
+class AdaDraw(object):
+    """What one ADA draw with a filter, noise or cutout group holds: the (N, 32) ``params`` rows, the (N, 16) ``ext`` rows and the
+    (N, 3, H, W) ``noise`` field (None without the noise group).  Slicing along the batch slices all three, so a learner hands
+    rows [0, B) to one batch and [B, 2B) to the other as it does with a plain tensor of rows."""
+
+    def __init__(self, params, ext, noise=None):
+        self.params, self.ext, self.noise = params, ext, noise
+
+    def __getitem__(self, rows):
+        if not isinstance(rows, slice):
+            raise TypeError('AdaDraw: only slices along the batch are supported')
+        return AdaDraw(self.params[rows], self.ext[rows], None if self.noise is None else self.noise[rows])
+
+    def __len__(self):
+        return self.params.shape[0]
+
+
+def ada_filter_bank():
+    """The library's (4, 43) float64 filter bank (csrc/ada_filter_bank.h), on the host."""
+    out = torch.empty((4, ADA_FILTER_TAPS), dtype=torch.float64)
+    check(_lib.lib().ganlab_ada_filter_bank(ctypes.c_void_p(out.data_ptr())), 'ada_filter_bank')
+    return out
+
+
+def ada_ext_params(n, h, w, state, policy, seed, offset, device):
+    """(n, 16) ``ext`` rows of ADA's filter, noise and cutout groups (csrc/ada_filter.hip) from the Philox stream at ``offset``
+    (4 counters per row): the position right after the main block of the batch, i.e. ``ada_params``' offset + 8 n."""
+    state = _c(state, 'ada_ext_params state')
+    out = torch.empty((int(n), ADA_EXT_ROW), dtype=torch.float32, device=device)
+    check(_lib.lib().ganlab_ada_ext_params_f32(_p(out), int(n), int(h), int(w), _p(state), int(policy),
+                                               int(seed) & (2 ** 64 - 1), int(offset), _st()), 'ada_ext_params')
+    return out
+
+
+def ada_ext_params_dev(n, h, w, state, policy, seed, base, delta, device):
+    """``ada_ext_params`` at stream position ``*base + delta`` (``base``: the step-scalar block of graphs.GraphedStep)."""
+    state = _c(state, 'ada_ext_params state')
+    out = torch.empty((int(n), ADA_EXT_ROW), dtype=torch.float32, device=device)
+    check(_lib.lib().ganlab_ada_ext_params_dev_f32(_p(out), int(n), int(h), int(w), _p(state), int(policy),
+                                                   int(seed) & (2 ** 64 - 1), _p(base), int(delta), _st()),
+          'ada_ext_params_dev')
+    return out
+
+
+def k_ada_ext(x, ext, noise=None, adjoint=False):
+    """cutout(noise(filter(x))) of an (N, 3, H, W) batch under the (N, 16) ``ext`` rows (``adjoint``: F^T (mask o x), the
+    transpose of its linear part, applied to a cotangent; ``noise`` is not read)."""
+    x, ext = _c(x, 'ada_augment input'), _c(ext, 'ada_augment ext')
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[3] % 4 != 0 or x.shape[2] < 2 or \
+            tuple(ext.shape) != (x.shape[0], ADA_EXT_ROW):
+        raise ValueError(f'ada_augment: needs an (N, 3, H, W) batch with H >= 2, W % 4 == 0 and (N, {ADA_EXT_ROW}) ext rows, '
+                         f'got {tuple(x.shape)} and {tuple(ext.shape)}')
+    n, _, h, w = x.shape
+    out = torch.empty_like(x)
+    L = _lib.lib()
+    if adjoint:
+        check(L.ganlab_ada_ext_bwd_f32(_p(x), _p(ext), _p(out), n, h, w, _st()), 'ada_ext_bwd')
+        return out
+    if noise is not None:
+        noise = _c(noise, 'ada_augment noise')
+        if tuple(noise.shape) != tuple(x.shape):
+            raise ValueError(f'ada_augment: the noise field must have the batch\'s shape {tuple(x.shape)}, got '
+                             f'{tuple(noise.shape)}')
+    check(L.ganlab_ada_ext_fwd_f32(_p(x), _p(ext), _p(noise) if noise is not None else None, _p(out), n, h, w, _st()),
+          'ada_ext_fwd')
+    return out
+
+
 def ada_update(state, logits, interval, step_size, target):
     """The ADA controller (csrc/ada.hip) on the device block ``state`` = (p, acc_sum, acc_n, calls); ``logits`` None only
     counts the call.  In place, no host read: capturable."""
@@ -2769,23 +2842,27 @@ class _DiffAugmentAdjoint(Function):
 
 
 class _AdaAugment(Function):
-    """ADA warp + color matrix (csrc/ada.hip): affine in x, so the backward is the adjoint of its linear part."""
+    """ADA warp + color matrix (csrc/ada.hip), then with ``ext`` the filter, noise and cutout of csrc/ada_filter.hip: affine in
+    x, so the backward is the adjoint of its linear part."""
 
     @staticmethod
-    def forward(ctx, x, params):
-        ctx.params = params
-        return k_ada(x, params)
+    def forward(ctx, x, params, ext=None, noise=None):
+        ctx.params, ctx.ext = params, ext
+        y = k_ada(x, params)
+        return y if ext is None else k_ada_ext(y, ext, noise)
 
     @staticmethod
     def backward(ctx, g):
         if not ctx.needs_input_grad[0]:
-            return None, None
-        return _AdaAugmentAdjoint.apply(g, ctx.params), None
+            return None, None, None, None
+        return _AdaAugmentAdjoint.apply(g, ctx.params, ctx.ext), None, None, None
 
 
 class _AdaAugmentAdjoint(Function):
     @staticmethod
-    def forward(ctx, g, params):
+    def forward(ctx, g, params, ext=None):
+        if ext is not None:
+            g = k_ada_ext(g, ext, adjoint=True)
         return k_ada(g, params, adjoint=True)
 
     @staticmethod
@@ -4180,14 +4257,22 @@ def diff_augment(x, params, policy):
     return _DiffAugment.apply(x, params.detach(), int(policy))
 
 
-def ada_augment(x, params):
+def ada_augment(x, params, ext=None, noise=None):
     """ADA (Karras et al. 2020) of an (N, 3, H, W) fp32 batch on the GPU: affine bilinear warp with zero fill, then a 3x4
-    color matrix, per sample from the (N, 32) ``params`` rows (``rng.ada_params`` or ``ada.rows_from_matrices``).
+    color matrix, per sample from the (N, 32) ``params`` rows (``rng.ada_params`` or ``ada.rows_from_matrices``).  With
+    ``ext`` ((N, 16) rows: ``rng.ada_params`` under a policy with filter, noise or cutout, or ``ada.ext_rows``) the result
+    goes on through the per-sample 43-tap filter, ``sigma * noise`` (``noise``: an (N, 3, H, W) field of standard normals;
+    None adds none, whatever sigma says) and the cutout rectangle; with ``ext`` None nothing further is launched.
     Differentiable once in ``x``."""
-    for t, what in ((x, 'ada_augment input'), (params, 'ada_augment params')):
+    for t, what in ((x, 'ada_augment input'), (params, 'ada_augment params')) + \
+            (((ext, 'ada_augment ext'),) if ext is not None else ()) + (((noise, 'ada_augment noise'),) if noise is not None else ()):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
             _c(t, what)                 # raises TypeError: there is no CPU path
-    return _AdaAugment.apply(x, params.detach())
+    if ext is None:
+        if noise is not None:
+            raise ValueError('ada_augment: a noise field needs ext rows (their sigma scales it)')
+        return _AdaAugment.apply(x, params.detach())
+    return _AdaAugment.apply(x, params.detach(), ext.detach(), None if noise is None else noise.detach())
 
 
 def layer_tail_deferred(x, bias=None, noise=None, noise_w=None, style=None, bias_scale=1.0, act=None, slope=0.2,

@@ -112,15 +112,26 @@ def cr_params(n, shift, flip, device='cuda'):
 
 def ada_params(n, h, w, state, policy, device='cuda'):
     """(n, 32) ADA parameter rows for (h, w) images at the probability held in the device block ``state`` (ada.py);
-    advances the stream by 8 counters per row."""
+    advances the stream by 8 counters per row.  A policy with a filter, noise or cutout group returns an ``ops.AdaDraw``
+    instead: the same rows, the (n, 16) ext rows from the next 4 counters per row and, with noise, the (n, 3, h, w) field
+    ``randn`` draws right after them - all consumed whatever the gates say, since p lives on the device."""
     n = int(n)
     if _DEVICE_BASE['block'] is not None:
-        out = ops.ada_params_dev(n, h, w, state, policy, _STATE['seed'], _DEVICE_BASE['block'],
+        out = ops.ada_params_dev(n, h, w, state, policy & ~ops.ADA_NEW_GROUPS, _STATE['seed'], _DEVICE_BASE['block'],
                                  _STATE['offset'] - _DEVICE_BASE['start'], device)
     else:
-        out = ops.ada_params(n, h, w, state, policy, _STATE['seed'], _STATE['offset'], device)
+        out = ops.ada_params(n, h, w, state, policy & ~ops.ADA_NEW_GROUPS, _STATE['seed'], _STATE['offset'], device)
     _STATE['offset'] += ops.ADA_COUNTERS * n
-    return out
+    if not policy & ops.ADA_NEW_GROUPS:
+        return out
+    if _DEVICE_BASE['block'] is not None:
+        ext = ops.ada_ext_params_dev(n, h, w, state, policy, _STATE['seed'], _DEVICE_BASE['block'],
+                                     _STATE['offset'] - _DEVICE_BASE['start'], device)
+    else:
+        ext = ops.ada_ext_params(n, h, w, state, policy, _STATE['seed'], _STATE['offset'], device)
+    _STATE['offset'] += ops.ADA_EXT_COUNTERS * n
+    noise = randn((n, 3, int(h), int(w)), device) if policy & ops.ADA_NOISE else None
+    return ops.AdaDraw(out, ext, noise)
 
 
 def swd_positions(n_images, n_per_image, size, device='cuda', seed=None, offset=None):

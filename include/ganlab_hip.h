@@ -540,6 +540,33 @@ int ganlab_ada_bwd_f32(const float* gy, const float* params, float* gx, int N, i
 int ganlab_ada_update_f32(float* state, const float* logits, int N, int interval, float step_size, float target,
                           void* stream);
 
+/* ---- ADA's image-space groups: filtering, noise, cutout (csrc/ada_filter.hip) -----------------------------
+ * Applied after ganlab_ada_fwd_f32: y = cutout(noise(filter(x))).  ext: (N, GANLAB_ADA_EXT_ROW) rows - g (4 band gains), sigma,
+ * the cutout rectangle j0, j1, i0, i1 (columns [j0, j1), rows [i0, i1); empty when off), the gate mask (bit b = band b, bit 4 =
+ * noise, bit 5 = cutout), the four band z, cx, cy.  The filter is the separable GANLAB_ADA_FILTER_TAPS-tap FIR
+ * h = fp32(sum_b g_b F[b]) over the (4, 43) bank F with whole-sample reflection of any depth.  The gate mask decides what acts:
+ * the filter runs when a band bit is set, sigma counts with bit 4, the rectangle with bit 5; a row with an empty mask is copied.
+ * H >= 2, W % 4 == 0, 3 N <= 65535. */
+#define GANLAB_ADA_FILTER 8
+#define GANLAB_ADA_NOISE 16
+#define GANLAB_ADA_CUTOUT 32
+#define GANLAB_ADA_EXT_ROW 16
+#define GANLAB_ADA_EXT_COUNTERS 4
+#define GANLAB_ADA_FILTER_TAPS 43
+/* the library's copy of the bank: 4 x 43 doubles, row-major, into host memory */
+int ganlab_ada_filter_bank(double* out);
+/* the ext rows from the Philox stream: sample n uses counters offset + 4n .. offset + 4n + 3, where offset is the position
+ * right after the batch's main block (the caller adds its 8 N); policy: the whole mask, only the three new bits open gates */
+int ganlab_ada_ext_params_f32(float* out, int N, int H, int W, const float* state, int policy, uint64_t seed, uint64_t offset,
+                              void* stream);
+/* ganlab_ada_ext_params_f32 at stream position *base + delta (base: device uint64) */
+int ganlab_ada_ext_params_dev_f32(float* out, int N, int H, int W, const float* state, int policy, uint64_t seed,
+                                  const void* base, uint64_t delta, void* stream);
+/* y = cutout(x' + sigma * noise), x' = filter(x); noise: (N, 3, H, W) standard normals or null (then none is added); x != y */
+int ganlab_ada_ext_fwd_f32(const float* x, const float* ext, const float* noise, float* y, int N, int H, int W, void* stream);
+/* gx = F^T (mask o gy): the adjoint as a gather in a fixed order (no atomics; bitwise reproducible); gy != gx */
+int ganlab_ada_ext_bwd_f32(const float* gy, const float* ext, float* gx, int N, int H, int W, void* stream);
+
 /* ---- sliced Wasserstein distance between Laplacian-pyramid patch descriptors (Karras et al. 2018; csrc/swd.hip)
  * Planes are fp32, H and W even.  f = [1,4,6,4,1]/16 with mirror boundary (the edge sample is not repeated). */
 #define GANLAB_SWD_DESC 147
