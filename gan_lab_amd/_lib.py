@@ -334,6 +334,12 @@ SIGNATURES = {
     'ganlab_cr_imsd_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_p]),
     'ganlab_moments_accum_f32': (_c_int, [_c_p, _c_ll, _c_int, _c_p, _c_p, _c_p, _c_p]),
     'ganlab_kid_rowsums_f32': (_c_int, [_c_p, _c_ll, _c_p, _c_ll, _c_int, _c_f, _c_f, _c_int, _c_p, _c_p]),
+    'ganlab_class_ce_fwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_p]),
+    'ganlab_class_ce_bwd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_p]),
+    'ganlab_cl_supported': (_c_int, [_c_int, _c_int, _c_int]),
+    'ganlab_cl_fwd_f32': (_c_int, [_c_p] * 5 + [_c_int, _c_int, _c_int, _c_int, _c_f, _c_f, _c_f, _c_p]),
+    'ganlab_cl_bwd_workspace': (_c_sz, [_c_int, _c_int, _c_int]),
+    'ganlab_cl_bwd_f32': (_c_int, [_c_p] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_f, _c_f, _c_f, _c_p, _c_sz, _c_p]),
     'ganlab_step_scalars_size': (_c_int, []),
     'ganlab_set_step_scalars': (_c_int, [_c_p, _c_u64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
 }

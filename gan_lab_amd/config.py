@@ -47,13 +47,24 @@ when the learner is built), and ``loss='hinge'`` (ResNet GAN only) is the loss u
 attention map is never stored) to the generator and / or the critic - on the 32x32 map of the 64-pixel networks, the 16x16 map
 of the 32-pixel ones.  The block is first order: ``'d'`` requires ``gradient_penalty=None`` (hinge loss + spectral normalisation
 is the recipe it belongs to), ``'g'`` works with every loss and penalty; on ProGAN / StyleGAN any value but None raises when the
-learner is built; ``cgan`` (ResNet GAN only; None = off, ``'projection'`` the only other value; ``--cgan=none`` on the command
-line) with ``num_classes`` >= 2 makes the pair class-conditional the SNGAN-projection / SAGAN / BigGAN way (conditional.py):
-class-conditional BatchNorm in the generator, a projection critic, on HIP kernels of their own; the inputs keep their widths and
-the learner's steps take the batch's labels (``DeviceImageLoader(labels=...)`` or any loader that yields ``(x, label)``).  It is
-independent of ``class_condition`` / ``use_auxiliary_classifier`` (the reference's own conditioning, which never ran and keeps
-raising), works with every loss, penalty and augmentation and with ``spectral_norm`` / ``self_attention``; any other value, a
-progressive model or ``num_classes`` < 2 raises when the learner is built; ``ortho_reg`` / ``ortho_reg_d`` (ResNet GAN only; 0 =
+learner is built; ``cgan`` (ResNet GAN only; None = off, else ``'projection'``, ``'contra'`` or ``'reacgan'``;
+``--cgan=none`` on the command line) with ``num_classes`` >= 2 makes the pair class-conditional (conditional.py): class-conditional
+BatchNorm in the generator in every mode and, with ``'projection'``, a projection critic - the SNGAN-projection / SAGAN / BigGAN
+way - on HIP kernels of their own; the inputs keep their widths and the learner's steps take the batch's labels
+(``DeviceImageLoader(labels=...)`` or any loader that yields ``(x, label)``).  It is independent of ``class_condition`` /
+``use_auxiliary_classifier`` (the reference's own conditioning, which never ran and keeps raising), works with every loss, penalty
+and augmentation and with ``spectral_norm`` / ``self_attention``; any other value, a progressive model or ``num_classes`` < 2
+raises when the learner is built.  ``'contra'`` (ContraGAN's conditional contrastive loss 2C, Kang & Park 2020) and
+``'reacgan'`` (ReACGAN's data-to-data cross-entropy D2D-CE, Kang et al. 2021) are classifier-based conditional GANs (AC-GAN's
+value ``'acgan'`` is still refused: conditional.py): the critic's score stays unconditional, a head on the critic's feature - an
+embedding of width ``cond_embed`` (int E, default 512, in [1, 1024]) with one proxy per class - carries the loss, and both
+steps add ``cond_lambda`` (float, default 1.0, finite and >= 0; 0 builds the heads and launches nothing) times it: the critic step
+on the real rows, the generator step on the generated rows (csrc/cond_loss.hip; per rank, embeddings are not gathered across
+ranks).  ``cond_temperature`` (float, default 1.0, > 0) divides the cosine similarities of the two contrastive losses;
+``cond_margin_pos`` / ``cond_margin_neg`` (floats, defaults 0.98 / 0.02, the second below the first) are D2D-CE's margins m_p and
+m_n.  The papers train ContraGAN with temperature 1.0 on CIFAR-10 and ReACGAN with 0.5 there and 0.98 / 0.02 margins; these are
+the user's choice and nothing was tuned here.  A value outside these ranges raises when the learner is built and names its field;
+ProGAN / StyleGAN have none of the five fields; ``ortho_reg`` / ``ortho_reg_d`` (ResNet GAN only; 0 =
 off) are the strengths beta of BigGAN's orthogonal regulariser (Brock et al. 2019, eq. 3; ortho_reg.py) on the generator's / the
 critic's Conv2dEx and LinearEx weights: at every generator (critic) update the gradient ``4 beta ((Wm Wm^T) o (1 - I)) Wm`` of
 ``beta |(Wm Wm^T) o (1 - I)|_F^2`` is added to the parameter gradients by batched fp32 matrix-core kernels, after the all-reduce
@@ -63,7 +74,7 @@ number); a negative or non-finite value raises when the learner is built, and Pr
 ``hier_latent`` (bool) / ``shared_embed`` (int E; ResNet GAN only, both off by default) are BigGAN's generator conditioning
 (Brock et al. 2019; hier_latent.py): with ``hier_latent`` the latent is split over the first linear and the residual blocks
 (``chunk = len_latent // (B + 1)``, B = 3 at 32 pixels, 4 at 64; the first linear reads the first ``len_latent - B * chunk``
-entries, so 128 is 28 + 4 x 25 at 64 pixels), with ``shared_embed`` = E > 0 (needs ``cgan='projection'``; BigGAN uses 128) the
+entries, so 128 is 28 + 4 x 25 at 64 pixels), with ``shared_embed`` = E > 0 (needs a ``cgan`` mode; BigGAN uses 128) the
 class is embedded once into ``shared.weight`` (num_classes, E); both norms of every block then take their gain and bias from
 bias-free linears of ``[z_b, e(y)]`` (without labels: self-modulation, Chen et al. 2019), computed for the whole network in one
 launch, and the (num_classes, C) tables are gone.  ``len_latent < B + 1``, a negative value, ``shared_embed`` without ``cgan`` or
@@ -158,7 +169,9 @@ def _spec(model_type):
                  ('use_ewma_gen', bool, False), ('ewma_decay', float, 0.9999), ('ewma_start', int, 0),
                  ('truncation', _float_or_none, None), ('standing_stat_batches', int, 16),
                  ('cr_real', float, 0.), ('cr_fake', float, 0.), ('cr_latent_d', float, 0.), ('cr_latent_g', float, 0.),
-                 ('cr_sigma', float, 0.03), ('cr_shift', _int_or_none, None), ('cr_flip', bool, True)]
+                 ('cr_sigma', float, 0.03), ('cr_shift', _int_or_none, None), ('cr_flip', bool, True),
+                 ('cond_lambda', float, 1.0), ('cond_embed', int, 512), ('cond_temperature', float, 1.0),
+                 ('cond_margin_pos', float, 0.98), ('cond_margin_neg', float, 0.02)]
     else:
         rows += [('batch_size', int, BS),
                  ('bs_dict', dict, {4: BS, 8: BS, 16: BS, 32: BS, 64: BS, 128: BS, 256: BS, 512: BS // 2,

@@ -1,6 +1,6 @@
 """BigGAN's generator conditioning for the ResNet GAN: hierarchical latents ("skip-z") and a shared class embedding.
 
-``config.hier_latent`` (bool) and ``config.shared_embed`` (int E, the embedding width; needs ``cgan='projection'``) - ResNet GAN
+``config.hier_latent`` (bool) and ``config.shared_embed`` (int E, the embedding width; needs a ``cgan`` mode) - ResNet GAN
 only, both off by default - replace the 2018 conditioning of the generator (one (num_classes, C) table per norm, the latent
 entering through the first linear only) by BigGAN's (Brock et al. 2019, section 3 and appendix B):
 
@@ -39,8 +39,9 @@ def validate_config(config):
     if getattr(config, 'model', 'ResNet GAN') != 'ResNet GAN':
         raise ValueError('config.hier_latent / config.shared_embed are ResNet GAN options (the progressive generators have '
                          'their own conditioning)')
-    if embed and getattr(config, 'cgan', None) != 'projection':
-        raise ValueError("config.shared_embed > 0 embeds the class: it needs config.cgan='projection' (and num_classes >= 2)")
+    if embed and getattr(config, 'cgan', None) is None:      # any mode: the generator side is the same in all of them
+        raise ValueError("config.shared_embed > 0 embeds the class: it needs config.cgan='projection' (or another cgan mode; and "
+                         "num_classes >= 2)")
     if hier:
         blocks = num_blocks(getattr(config, 'res_samples', 64))
         if blocks is not None:

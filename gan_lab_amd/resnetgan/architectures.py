@@ -4,8 +4,10 @@ gan_lab/resnetgan/architectures.py:29-224): same class names, constructor argume
 the reference; default off) adds a SAGAN block ``self_attn`` (attention.py) beside the unchanged module tree; ``cgan=True``
 (not in the reference either; default off) with ``num_classes`` = K makes the networks class-conditional (conditional.py): every
 generator BatchNorm carries (K, C) tables and the generator is called as ``g(z, labels)``, the critic gains the projection layer
-``proj`` and is called as ``d(x, labels)``.  With ``cgan`` the reference's meaning of ``num_classes`` (a one-hot concatenated to
-the input) does not apply: the inputs keep their widths.  ``hier_latent=True`` / ``shared_embed=E`` (not in the reference; default
+``proj`` and is called as ``d(x, labels)``; a critic built with ``cgan='acgan'`` / ``'contra'`` / ``'reacgan'`` gains a classifier
+head instead (``cls``, or ``embed`` and ``proxy`` with ``cond_embed`` = E), keeps the unconditional score and hands the feature to
+the caller's loss with ``d(x, labels, return_features=True)``.  With ``cgan`` the reference's meaning of ``num_classes`` (a
+one-hot concatenated to the input) does not apply: the inputs keep their widths.  ``hier_latent=True`` / ``shared_embed=E`` (not in the reference; default
 off; generators only) are BigGAN's conditioning (hier_latent.py): both norms of every block become ``ModulatedBatchNorm2d`` whose
 ``gain`` / ``shift`` linears read the block's chunk of ``z`` and / or the row ``shared.weight[label]`` of one (K, E) embedding, the
 first linear reads only the first chunk, the norm behind the last block is a plain ``BatchNorm2d`` and - with ``shared_embed`` -
@@ -218,28 +220,52 @@ def _cgan_classes(cgan, num_classes):
     return num_classes, 0
 
 
-def _init_projection(critic, cgan, num_classes, nin_feat, equalized_lr):
-    """``cgan=True``: the class embedding ``proj`` of the projection critic - a bias-free LinearEx beside ``linear1``, reading the
-    same feature; built before ``_init_spectral_norm`` so that it gets its u, v like every other layer."""
+def _critic_mode(cgan):
+    """The critic's ``cgan`` argument -> None, 'projection' (also True) or one of the classifier modes."""
+    from ..conditional import HEAD_MODES
+    if not cgan:
+        return None
+    if cgan is True or cgan == 'projection':
+        return 'projection'
+    if cgan in HEAD_MODES:
+        return cgan
+    raise ValueError(f"cgan must be False, True / 'projection', 'acgan', 'contra' or 'reacgan' (got {cgan!r})")
+
+
+def _init_projection(critic, cgan, num_classes, nin_feat, equalized_lr, cond_embed=512):
+    """The critic's conditioning heads, beside ``linear1`` and reading the same feature; built before ``_init_spectral_norm`` so
+    that they get their u, v like every other layer.  ``cgan=True`` / ``'projection'``: the class embedding ``proj`` of the
+    projection critic, a bias-free LinearEx.  ``'acgan'``: the classifier ``cls``.  ``'contra'`` / ``'reacgan'``: ``embed`` and the
+    bias-free ``proxy``, whose (K, E) weight rows are the class proxies - read as a table, never applied as a layer."""
+    critic.cond_mode = mode = _critic_mode(cgan)
     critic.proj = LinearEx(nin_feat=nin_feat, nout_feat=num_classes, include_bias=False, init='Xavier',
-                           equalized_lr=equalized_lr) if cgan else None
+                           equalized_lr=equalized_lr) if mode == 'projection' else None
+    if mode == 'acgan':
+        critic.cls = LinearEx(nin_feat=nin_feat, nout_feat=num_classes, init='Xavier', equalized_lr=equalized_lr)
+    elif mode in ('contra', 'reacgan'):
+        from ..conditional import MAX_EMBED
+        if not isinstance(cond_embed, int) or isinstance(cond_embed, bool) or not 1 <= cond_embed <= MAX_EMBED:
+            raise ValueError(f'cond_embed must be an integer in [1, {MAX_EMBED}] (got {cond_embed!r})')
+        critic.embed = LinearEx(nin_feat=nin_feat, nout_feat=cond_embed, init='Xavier', equalized_lr=equalized_lr)
+        critic.proxy = LinearEx(nin_feat=cond_embed, nout_feat=num_classes, include_bias=False, init='Xavier',
+                                equalized_lr=equalized_lr)
 
 
-def _critic_forward(critic, x, labels):
+def _critic_forward(critic, x, labels, return_features=False):
     _check_spectral_norm(critic)
-    if critic.proj is None and labels is not None:
+    if critic.cond_mode is None and labels is not None:
         raise TypeError(f'{type(critic).__name__} is not class-conditional (cgan=False) and takes no labels')
-    if critic.proj is not None:
+    if critic.cond_mode is not None:
         _need_labels(critic, labels)
     f = critic.features(x)
-    base = critic.linear1(f).view(-1)
-    if critic.proj is None:
-        return base
-    proj = critic.proj
-    weight = proj.linear.weight if proj.weight_override is None else proj.weight_override
-    if proj.scale != 1.0:
-        weight = ops.scale(weight, proj.scale)
-    return ops.class_projection(f, weight, labels, base)
+    out = critic.linear1(f).view(-1)
+    if critic.proj is not None:
+        proj = critic.proj
+        weight = proj.linear.weight if proj.weight_override is None else proj.weight_override
+        if proj.scale != 1.0:
+            weight = ops.scale(weight, proj.scale)
+        out = ops.class_projection(f, weight, labels, out)
+    return (out, f) if return_features else out
 
 
 def _init_spectral_norm(critic, spectral_norm):
@@ -262,7 +288,7 @@ class Discriminator32PixResnet(GAN):
     map, after ``conv1``."""
 
     def __init__(self, fmap=FMAP_D * 2, pooler=None, blur_type=None, nl=None, num_classes=0, equalized_lr=False,
-                 spectral_norm=False, self_attention=False, cgan=False):
+                 spectral_norm=False, self_attention=False, cgan=False, cond_embed=512):
         super().__init__(32)
         cond_classes, num_classes = _cgan_classes(cgan, num_classes)
         from ..utils.custom_layers import AvgPool2x
@@ -283,14 +309,14 @@ class Discriminator32PixResnet(GAN):
         )
         self.linear1 = LinearEx(nin_feat=fmap, nout_feat=1, init='Xavier', equalized_lr=equalized_lr)
         _init_self_attention(self, self_attention, fmap, equalized_lr)
-        _init_projection(self, cgan, cond_classes, fmap, equalized_lr)
+        _init_projection(self, cgan, cond_classes, fmap, equalized_lr, cond_embed)
         _init_spectral_norm(self, spectral_norm)      # after the block exists: its convolutions get u, v too
 
     def features(self, x):
         return _run_with_attention(self, self.resblocks, self.conv1(self.view1(x)), 0)
 
-    def forward(self, x, labels=None):
-        return _critic_forward(self, x, labels)
+    def forward(self, x, labels=None, return_features=False):
+        return _critic_forward(self, x, labels, return_features)
 
 
 class Discriminator64PixResnet(GAN):
@@ -298,7 +324,7 @@ class Discriminator64PixResnet(GAN):
     map (2 * fmap channels), after the first block."""
 
     def __init__(self, fmap=FMAP_D, pooler=None, blur_type=None, nl=None, num_classes=0, equalized_lr=False,
-                 spectral_norm=False, self_attention=False, cgan=False):
+                 spectral_norm=False, self_attention=False, cgan=False, cond_embed=512):
         super().__init__(64)
         cond_classes, num_classes = _cgan_classes(cgan, num_classes)
         from ..utils.custom_layers import AvgPool2x
@@ -320,14 +346,14 @@ class Discriminator64PixResnet(GAN):
         self.linear1 = LinearEx(nin_feat=RES_FEATURE_SPACE ** 2 * 8 * fmap, nout_feat=1, init='Xavier',
                                 equalized_lr=equalized_lr)
         _init_self_attention(self, self_attention, 2 * fmap, equalized_lr)
-        _init_projection(self, cgan, cond_classes, RES_FEATURE_SPACE ** 2 * 8 * fmap, equalized_lr)
+        _init_projection(self, cgan, cond_classes, RES_FEATURE_SPACE ** 2 * 8 * fmap, equalized_lr, cond_embed)
         _init_spectral_norm(self, spectral_norm)      # after the block exists: its convolutions get u, v too
 
     def features(self, x):
         return _run_with_attention(self, self.resblocks, self.conv1(self.view1(x)), 1)
 
-    def forward(self, x, labels=None):
-        return _critic_forward(self, x, labels)
+    def forward(self, x, labels=None, return_features=False):
+        return _critic_forward(self, x, labels, return_features)
 
 
 class DiscriminatorAC32PixResnet(Discriminator32PixResnet):

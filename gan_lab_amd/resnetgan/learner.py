@@ -14,7 +14,11 @@ mean-all-reduced over RCCL (BatchNorm statistics stay per rank, like DDP without
 (spectral_norm.py) and ``loss='hinge'`` is its usual partner; ``config.self_attention`` ('g', 'd', 'gd'; ResNet GAN only) adds
 SAGAN's self-attention block to the generator / critic (attention.py); ``config.cgan='projection'`` (ResNet GAN only, with
 ``config.num_classes`` >= 2) makes the pair class-conditional - conditional BatchNorm in the generator, a projection critic
-(conditional.py) - and ``g_step`` / ``d_step`` then take the batch's labels; ``config.ortho_reg`` / ``config.ortho_reg_d``
+(conditional.py) - and ``g_step`` / ``d_step`` then take the batch's labels; ``config.cgan='contra'`` / ``'reacgan'``
+keep the critic's score unconditional and add ``config.cond_lambda`` times the loss of a classifier head on the critic's feature -
+ContraGAN's 2C, ReACGAN's D2D-CE (csrc/cond_loss.hip) - to the critic step on the real rows and to the
+generator step on the generated rows, per rank, with the unweighted terms in ``last_losses['cond_d']`` / ``['cond_g']``;
+``config.ortho_reg`` / ``config.ortho_reg_d``
 (ResNet GAN only) add the gradient of BigGAN's orthogonal regulariser to the generator's / critic's weight gradients before
 the optimiser step (ortho_reg.py); ``config.hier_latent`` / ``config.shared_embed`` (ResNet GAN only) give the generator BigGAN's
 conditioning - hierarchical latents and a shared class embedding modulating every block norm (hier_latent.py) - without touching
@@ -100,9 +104,12 @@ class GANLearner(object):
             # so there is no behaviour to be in parity with.
             raise NotImplementedError('class_condition / use_auxiliary_classifier: no variant of these options runs in '
                                       'the reference (tests/golden/conditional_probe.json); not provided')
-        # class conditioning of our own (config.cgan; conditional.py): conditional BatchNorm + projection critic, ResNet GAN only
+        # class conditioning of our own (config.cgan; conditional.py): conditional BatchNorm + a projection critic or a critic with
+        # a classifier head and its loss (self._cond: the loss's weight and parameters, None in the other modes), ResNet GAN only
         from .. import conditional
         self.cgan = conditional.validate_config(config)
+        self._cgan_mode = conditional.mode(config) if self.cgan else None
+        self._cond = conditional.validate_loss_config(config)
         # BigGAN's generator conditioning (config.hier_latent / config.shared_embed; hier_latent.py): ResNet GAN only
         from .. import hier_latent
         self._hier_latent, self._shared_embed = hier_latent.validate_config(config)
@@ -187,8 +194,9 @@ class GANLearner(object):
         sn_kw = {'spectral_norm': True} if spectral_norm.validate_config(config) else {}
         if self._attn_d:
             sn_kw['self_attention'] = True
+        cgan_kw_d = dict(cgan_kw, cgan=self._cgan_mode, cond_embed=self._cond['embed']) if self._cond is not None else cgan_kw
         self.disc_model = disc_cls(fmap=fmap_d, pooler=self.disc_model_downsampler, blur_type=c.blur_type,
-                                   nl=self.nl, equalized_lr=c.use_equalized_lr, **sn_kw, **cgan_kw)
+                                   nl=self.nl, equalized_lr=c.use_equalized_lr, **sn_kw, **cgan_kw_d)
         self.gen_model.to(c.dev)
         self.disc_model.to(c.dev)
         from .. import rng
@@ -317,7 +325,7 @@ class GANLearner(object):
         k = self.config.num_classes
         if labels is None:
             if not draw:
-                raise ValueError("config.cgan='projection': d_step needs the labels of the real batch (labels=...)")
+                raise ValueError(f"config.cgan={self._cgan_mode!r}: d_step needs the labels of the real batch (labels=...)")
             from .. import rng
             return rng.randint(n, k, self.config.dev)
         if isinstance(labels, torch.Tensor) and labels.is_cuda:
@@ -333,6 +341,20 @@ class GANLearner(object):
 
     def _disc(self, x, labels):
         return self.disc_model(x, labels) if self.cgan else self.disc_model(x)
+
+    @property
+    def _cond_on(self):
+        """Does a step launch the classifier-based conditioning term (``config.cgan`` in 'contra' / 'reacgan' with
+        ``config.cond_lambda`` > 0)?  With the weight at 0 the heads exist and nothing is launched."""
+        return self._cond is not None and self._cond['weight'] > 0
+
+    def _add_cond_term(self, loss, feat, labels, name):
+        """``loss + cond_lambda * term`` with the term of the critic's classifier head on the feature rows ``feat`` (from the
+        critic pass that produced the scores: the trunk is never run twice) and their labels; per rank, nothing is gathered."""
+        from .. import conditional
+        term = conditional.cond_term(self.disc_model, feat, labels, self._cond)
+        self.last_losses[name] = term.detach()      # unweighted; a device tensor: no host synchronisation
+        return loss + self._cond['weight'] * term
 
     def g_step(self, zb=None, aug_params=None, labels=None, cr_noise=None):
         """resnetgan/learner.py:545-597 (critic parameters frozen by the caller).  ``aug_params``: the DiffAugment rows
@@ -360,9 +382,15 @@ class GANLearner(object):
             fake = self._gen(zb, labels)
         if self.critic_aug is not None:
             fake = self._augment(fake, aug_params)
-        out = self._disc(fake, labels)
+        feat = None
+        if self._cond_on:
+            out, feat = self.disc_model(fake, labels, return_features=True)
+        else:
+            out = self._disc(fake, labels)
         # :573-578 - the minimax generator loss here is -BCE(D(G(z)), 0), like backprop_utils
         loss = self.loss_func_gen(out)
+        if feat is not None:        # the classifier-based conditioning term on the generated rows, with the generator's labels
+            loss = self._add_cond_term(loss, feat, labels, 'cond_g')
         if cr_term is not None:
             loss = loss - self.cr.latent_g * cr_term
             self.last_losses['cr_latent_g'] = cr_term.detach()      # unweighted; a device tensor: no host synchronisation
@@ -559,19 +587,31 @@ class GANLearner(object):
             parts = 2 + len(extra)
             if extra:
                 both = torch.cat([both] + [x for _, _, x in extra])
-            out = self._disc(both, torch.cat((labels,) * parts) if labels is not None else None)
+            f_real = None
+            if self._cond_on:
+                out, feat = self.disc_model(both, torch.cat((labels,) * parts), return_features=True)
+                f_real = feat[n:2 * n]      # the real rows only: generated rows and the consistency terms' rows stay out
+            else:
+                out = self._disc(both, torch.cat((labels,) * parts) if labels is not None else None)
             d_gen, d_real = out[:n], out[n:2 * n]
             d_extra = [out[(2 + i) * n:(3 + i) * n] for i in range(len(extra))]
         else:
             if aug is not None:
                 xgenb, xb = aug(xgenb, aug_params[:n]), aug(xb, aug_params[n:])
-            d_gen, d_real = self._disc(xgenb, labels), self._disc(xb, labels)
+            f_real = None
+            d_gen = self._disc(xgenb, labels)
+            if self._cond_on:
+                d_real, f_real = self.disc_model(xb, labels, return_features=True)
+            else:
+                d_real = self._disc(xb, labels)
             d_extra = [self._disc(x, labels) for _, _, x in extra]
         loss = self.loss_func_disc(d_gen, d_real)
         for (name, weight, _), d_x in zip(extra, d_extra):
             term = ops.cr_msd(d_real if name == 'cr_real' else d_gen, d_x)
             loss = loss + weight * term
             self.last_losses[name] = term.detach()      # unweighted; a device tensor: no host synchronisation
+        if f_real is not None:      # the classifier-based conditioning term on the real rows, with the real labels
+            loss = self._add_cond_term(loss, f_real, labels, 'cond_d')
         self._ada_update(d_real)
         if self.gradient_penalty is not None:
             loss = loss + self.calc_gp(xgenb, xb, eps_interp=eps_interp, labels=labels)
@@ -654,7 +694,7 @@ class GANLearner(object):
                     self.last_losses = dict(itr=itr, loss_d=float(loss_d) if loss_d is not None else None,
                                             loss_g=float(loss_g) if loss_g is not None else None,
                                             res=c.res_samples, batch=self.batch_size,
-                                            **{k: v for k, v in self.last_losses.items() if k.startswith(('ortho_', 'cr_'))})
+                                            **{k: v for k, v in self.last_losses.items() if k.startswith(('ortho_', 'cr_', 'cond_'))})
                     if parallel.rank() == 0:
                         print(('%9s' * 5) % (f'{self.curr_epoch_num}/{self.tot_num_epochs}',
                                              f'{c.res_samples}X{c.res_samples}',
@@ -698,7 +738,8 @@ class GANLearner(object):
         from .. import consistency
         ck = {
             'config': ckpt.saved_config_fields({k: v for k, v in
-                                                consistency.saved_config_fields(sampling.saved_config_fields(vars(self.config))).items()
+                                                conditional.saved_config_fields(consistency.saved_config_fields(
+                                                    sampling.saved_config_fields(vars(self.config)))).items()
                                                 if not k.startswith('_') and
                                                 isinstance(v, (int, float, str, bool, dict, list, tuple, type(None))) and
                                                 not (k in ('self_attention', 'cgan') and v is None) and

@@ -1035,6 +1035,30 @@ int ganlab_moments_accum_f32(const float* rows, long long n, int D, const float*
 int ganlab_kid_rowsums_f32(const float* q, long long M, const float* keys, long long N, int D, float gamma, float coef0,
                            int exclude_diag, double* out, void* stream);
 
+/* ---- classifier-based class conditioning of the ResNet GAN critic: AC-GAN's cross-entropy (Odena et al. 2017), ContraGAN's
+ * conditional contrastive loss 2C (Kang & Park 2020), ReACGAN's data-to-data cross-entropy D2D-CE (Kang et al. 2021)
+ * (config.cgan = 'acgan' | 'contra' | 'reacgan'; csrc/cond_loss.hip; composed in gan_lab_amd/conditional.py).
+ * labels: int32 (N,), clamped into [0, K).  Every loss is the mean over rows; gout is the device scalar cotangent of that mean.  No
+ * atomics, every sum in a fixed order: bitwise reproducible.  Stream-ordered, graph-capturable, nothing is read back by the host.
+ * 1 <= N <= 8192, 2 <= K <= 65536, 1 <= E <= 1024; outside: GANLAB_EUNSUPPORTED.
+ *   class_ce:  z (N, K) logits.  fwd: loss[0] = mean_i (lse_i - z[i, y_i]), lse (N,) saved for the backward; one launch (one
+ *              workgroup).  bwd: dz[i,k] = gout[0]/N (exp(z[i,k] - lse_i) - [k == y_i]); one launch.
+ *   cl:        h (N, E) embeddings, proxy (K, E); both are normalised to unit rows (norm floor 1e-12) inside.  mode 0 = 2C,
+ *              1 = D2D-CE (margin_pos, margin_neg; ignored by 2C); temperature > 0.  fwd: rows (4, N) = the per-row loss, D_i, M_i
+ *              (2C; D2D-CE: u_i) and s_i, loss[0] their mean; two launches.  bwd: dh (N, E), dproxy (K, E), every row written
+ *              (exact zeros for a class absent from the batch); workspace ganlab_cl_bwd_workspace(N, E, K) bytes, 4-byte aligned;
+ *              three launches.  The derivative of a clamp is 0 at its kink. */
+int ganlab_class_ce_fwd_f32(const float* z, const int* labels, float* loss, float* lse, int N, int K, void* stream);
+int ganlab_class_ce_bwd_f32(const float* z, const int* labels, const float* lse, const float* gout, float* dz, int N, int K,
+                            void* stream);
+int ganlab_cl_supported(int N, int E, int K);
+int ganlab_cl_fwd_f32(const float* h, const float* proxy, const int* labels, float* loss, float* rows, int N, int E, int K,
+                      int mode, float temperature, float margin_pos, float margin_neg, void* stream);
+size_t ganlab_cl_bwd_workspace(int N, int E, int K);
+int ganlab_cl_bwd_f32(const float* h, const float* proxy, const int* labels, const float* rows, const float* gout, float* dh,
+                      float* dproxy, int N, int E, int K, int mode, float temperature, float margin_pos, float margin_neg,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
