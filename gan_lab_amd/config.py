@@ -97,7 +97,16 @@ and ``- cr_latent_g * imsd(G(z), G(z'))`` to the generator's, ``z' = z + cr_sigm
 ICR's CIFAR-10 BigGAN setting is 10 / 10 / 5 / 0.5.  The terms are first order in the critic and compose with every loss and
 penalty, ``spectral_norm``, ``self_attention`` and ``cgan``; with all four weights at 0 nothing is built, drawn or launched.  A
 negative or non-finite weight, ``cr_sigma <= 0`` with a latent weight on, ``cr_shift`` outside [0, res_samples), or a positive
-weight together with ``diffaugment`` / ``ada`` raises when the learner is built, and ProGAN / StyleGAN have no such field.
+weight together with ``diffaugment`` / ``ada`` raises when the learner is built, and ProGAN / StyleGAN have no such field;
+``fq_codes`` (ResNet GAN only; int K, 0 = off, else in [1, 4096]) / ``fq_decay`` (float, default 0.8, in [0, 1)) / ``fq_commit``
+(float, default 1.0, finite and >= 0) are the fields of FQ-GAN's feature quantisation of the critic (Zhao et al. 2020;
+quantize.py): K dictionary rows that replace every spatial feature vector of one critic layer by the nearest of them, the decay of
+the moving averages the dictionary follows the features with, and the weight of the commitment term in the critic's loss.  The
+layer is first order, so ``fq_codes > 0`` excludes every ``gradient_penalty`` (hinge loss + spectral normalisation is the recipe).
+FQ-BigGAN uses 2^10 codes, decay 0.8 and weight 1.0; these are the user's choice and nothing was tuned here.  A value outside these
+ranges, or a gradient penalty beside ``fq_codes > 0``, raises ValueError when the learner is built and names its field.  The layer's
+kernels are not in the package yet: a valid ``fq_codes > 0`` is still refused (NotImplementedError, as ``cgan='acgan'`` is) and 0
+builds nothing; ProGAN / StyleGAN have none of the three fields.
 ``--gradient_penalty=none`` on the command line means no penalty (None), as ``make_config(gradient_penalty=None)`` does.
 """
 import argparse
@@ -171,7 +180,8 @@ def _spec(model_type):
                  ('cr_real', float, 0.), ('cr_fake', float, 0.), ('cr_latent_d', float, 0.), ('cr_latent_g', float, 0.),
                  ('cr_sigma', float, 0.03), ('cr_shift', _int_or_none, None), ('cr_flip', bool, True),
                  ('cond_lambda', float, 1.0), ('cond_embed', int, 512), ('cond_temperature', float, 1.0),
-                 ('cond_margin_pos', float, 0.98), ('cond_margin_neg', float, 0.02)]
+                 ('cond_margin_pos', float, 0.98), ('cond_margin_neg', float, 0.02),
+                 ('fq_codes', int, 0), ('fq_decay', float, 0.8), ('fq_commit', float, 1.0)]
     else:
         rows += [('batch_size', int, BS),
                  ('bs_dict', dict, {4: BS, 8: BS, 16: BS, 32: BS, 64: BS, 128: BS, 256: BS, 512: BS // 2,

@@ -143,6 +143,10 @@ class GANLearner(object):
         # consistency regularisation (config.cr_*; consistency.py): None with every weight at 0 - nothing drawn, nothing launched
         from .. import consistency
         self.cr = consistency.validate_config(config)
+        # feature quantisation of the critic (config.fq_*; quantize.py): the fields are checked here; the layer's kernels are not
+        # in the package yet, so a valid fq_codes > 0 is refused and 0 builds nothing
+        from .. import quantize
+        quantize.require_layer(quantize.validate_config(config))
         self.ortho_g = self.ortho_d = None
         self._gradient_penalty = config.gradient_penalty
         self._optimizer = config.optimizer.casefold()
@@ -735,11 +739,12 @@ class GANLearner(object):
         from .. import checkpoint as ckpt
         tcpu = lambda v: None if v is None else v.detach().cpu()  # noqa: E731
         sched_steps = max(self.scheduler_gen._step_count - 1, 0) if (self.sched_bool and self.scheduler_gen) else 0
-        from .. import consistency
+        from .. import consistency, quantize
         ck = {
             'config': ckpt.saved_config_fields({k: v for k, v in
                                                 conditional.saved_config_fields(consistency.saved_config_fields(
-                                                    sampling.saved_config_fields(vars(self.config)))).items()
+                                                    quantize.saved_config_fields(
+                                                        sampling.saved_config_fields(vars(self.config))))).items()
                                                 if not k.startswith('_') and
                                                 isinstance(v, (int, float, str, bool, dict, list, tuple, type(None))) and
                                                 not (k in ('self_attention', 'cgan') and v is None) and
