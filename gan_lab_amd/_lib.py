@@ -340,6 +340,12 @@ SIGNATURES = {
     'ganlab_cl_fwd_f32': (_c_int, [_c_p] * 5 + [_c_int, _c_int, _c_int, _c_int, _c_f, _c_f, _c_f, _c_p]),
     'ganlab_cl_bwd_workspace': (_c_sz, [_c_int, _c_int, _c_int]),
     'ganlab_cl_bwd_f32': (_c_int, [_c_p] * 7 + [_c_int, _c_int, _c_int, _c_int, _c_f, _c_f, _c_f, _c_p, _c_sz, _c_p]),
+    'ganlab_pyramid_mse_workspace': (_c_sz, [_c_int, _c_int, _c_int, _c_int]),
+    'ganlab_pyramid_mse_f32': (_c_int, [_c_p] * 3 + [_c_int] + [_c_p] * 3 + [_c_int, _c_int, _c_int, _c_p, _c_sz, _c_p]),
+    'ganlab_scale_rows_f32': (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_ll, _c_p]),
+    'ganlab_w_moments_workspace': (_c_sz, [_c_int]),
+    'ganlab_w_moments_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_int, _c_p, _c_sz, _c_p]),
+    'ganlab_project_step_f32': (_c_int, [_c_p] * 8 + [_c_int, _c_int, _c_int, _c_int, _c_p, _c_p]),
     'ganlab_step_scalars_size': (_c_int, []),
     'ganlab_set_step_scalars': (_c_int, [_c_p, _c_u64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
 }

@@ -344,6 +344,34 @@ class StyleGenerator(StyleGAN):
                 ops.conv_aff_ok(shape, mod.conv2d.weight, False, mod.padding)
         return ops.conv_aff_ok(shape, mod.conv2d.weight, True, mod.padding)
 
+    def _to_image(self, out):
+        """toRGB behind the last layer, reading a deferred tensor where its kernel can."""
+        if isinstance(out, ops.Deferred) and ops.torgb_mod_ok(out, self.torgb.conv2d.weight):
+            t = self.torgb                    # toRGB is linear: per-sample weights w*s and bias b + w.t (csrc/mod.hip)
+            return ops.torgb_mod(out, t.conv2d.weight, t.conv2d.bias, t.scale, t.lrmul if t.use_lrmul else 1.0)
+        return self.torgb(ops.materialize(out))
+
+    def synthesis(self, ws, noise=None):
+        """The synthesis network alone: the image of given dlatents.  ``ws`` is (N, L, len_dlatent) with ``L =
+        len(self.gen_layers)`` - one dlatent per layer (W+), layer n reads ``ws[:, n]`` - or (N, len_dlatent), used for every layer
+        (W).  The layers run exactly as in ``forward`` (same kernels, same bits for the same dlatents); there is no mapping
+        network, truncation, mixing draw or ``w_ewma`` update.  ``noise``: the per-layer list ``forward`` accepts.  Not available
+        while a resolution fades in."""
+        if self.fade_in_phase:
+            raise ValueError('synthesis: not available while fade_in_phase is set (the image then blends two resolutions; '
+                             'finish the fade-in first)')
+        L = len(self.gen_layers)
+        if not isinstance(ws, torch.Tensor) or ws.dim() not in (2, 3) or ws.shape[-1] != self.len_dlatent or \
+                (ws.dim() == 3 and ws.shape[1] != L):
+            raise ValueError(f'synthesis: ws must be (N, {L}, {self.len_dlatent}) or (N, {self.len_dlatent}) (got '
+                             f'{tuple(getattr(ws, "shape", ()))})')
+        # (L, N, D): every layer reads a contiguous (N, D) slice, and the L gradients come back as one stacked tensor
+        per_layer = ws.transpose(0, 1).contiguous().unbind(0) if ws.dim() == 3 else (ws,) * L
+        out = self.const_input.expand(ws.shape[0], -1, -1, -1)
+        for n, layer in enumerate(self.gen_layers):
+            out = self._layer(n, layer, out, per_layer[n], noise, consumer=self._consumer(n, L))
+        return self._to_image(out)
+
     def _new_w(self, bs, dev):
         z2 = gen_rand_latent_vars(num_samples=bs, length=self.len_latent, distribution=self.latent_distribution,
                                   device=dev)
@@ -395,11 +423,7 @@ class StyleGenerator(StyleGAN):
             out = self._layer(n, layer, out, w, noise, consumer=self._consumer(n, L))
             if self.fade_in_phase and n == L - 3:
                 pre_fade = out
-        if isinstance(out, ops.Deferred) and ops.torgb_mod_ok(out, self.torgb.conv2d.weight):
-            t = self.torgb                    # toRGB is linear: per-sample weights w*s and bias b + w.t (csrc/mod.hip)
-            img = ops.torgb_mod(out, t.conv2d.weight, t.conv2d.bias, t.scale, t.lrmul if t.use_lrmul else 1.0)
-        else:
-            img = self.torgb(ops.materialize(out))
+        img = self._to_image(out)
         if self.fade_in_phase:
             prev = ops.upsample2(self.prev_torgb(pre_fade))
             img = ops.lerp(prev, img, self.alpha)                      # (:481-494)

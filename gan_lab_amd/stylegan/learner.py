@@ -74,6 +74,17 @@ class StyleGANLearner(ProGANLearner):
             if ck.get('w_ewma_lagged') is not None:
                 g.w_ewma = ck['w_ewma_lagged'].to(dev)
 
+    # -- inversion (gan_lab_amd/project.py; the StyleGAN2 projector) ---------------------------------------------------
+    def project(self, targets, steps=1000, space='w', levels=None, weights=None, noise_mode='const', time_average=True,
+                w_avg_samples=10000, seed=0, **schedule):
+        """Project ``targets`` - (N, 3, R, R) in [0, 1] image space at the current resolution - into the generator's latent
+        space, W (``space='w'``) or W+ (``'w+'``): ``gan_lab_amd.project.project`` on this learner, which documents the
+        arguments and the returned ``Projection`` (``ws``, ``images``, ``loss``, ``w_avg``, ``w_std``).  The learner is left
+        exactly as found."""
+        from ..project import project
+        return project(self, targets, steps=steps, space=space, levels=levels, weights=weights, noise_mode=noise_mode,
+                       time_average=time_average, w_avg_samples=w_avg_samples, seed=seed, **schedule)
+
     # -- style-mixing figure (stylegan/learner.py:306-431): the pixel content, without the matplotlib layout ------
     STYLE_MIX_STAGES = (1, 4, 8)    # coarse / middle / fine: generator layer at which source B's w takes over
 

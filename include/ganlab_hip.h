@@ -1059,6 +1059,38 @@ int ganlab_cl_bwd_f32(const float* h, const float* proxy, const int* labels, con
                       float* dproxy, int N, int E, int K, int mode, float temperature, float margin_pos, float margin_neg,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- projection of images into StyleGAN's latent space, W or W+ (csrc/project.hip; composed in
+ * gan_lab_amd/project.py).  No atomics, every sum in a fixed order: bitwise reproducible.  Stream-ordered, nothing is read back by
+ * the host.
+ *   pyramid_mse:  x, t (N, C, R, R) fp32, 16-byte aligned; R a power of two in [4, 1024]; `weights`: `levels` non-negative HOST
+ *                 floats, 1 <= levels <= min(6, log2(R) + 1).  d_0 = x - t, d_{l+1} = the 2x2 mean of d_l (fp32):
+ *                 terms[n, l] = mean_{c,h,w} d_l[n]^2 (squares and sums in fp64, rounded once), loss[n] = sum_l weights[l]
+ *                 terms[n, l] (from the fp64 terms), g = d loss[n] / d x = 2 / (C R^2) sum_l weights[l] up_l(d_l).  Two launches:
+ *                 one workgroup per 32x32 tile of a plane (the plane below 32x32) reads x and t once, writes g once and one fp64
+ *                 partial per (tile, level) into the workspace (ganlab_pyramid_mse_workspace bytes, 8-byte aligned); one
+ *                 workgroup per sample adds them in index order.  Outside the ranges: GANLAB_EUNSUPPORTED.
+ *   scale_rows:   out[n, :] = g[n, :] * s[n] over N rows of `per` floats (per % 4 == 0, 16-byte aligned); out is not g.
+ *   w_moments:    ws (M, D): w_avg[d] = mean_i ws[i, d], w_std[0] = sqrt(sum_{i,d} (ws[i, d] - mean_d)^2 / M) - the StyleGAN2
+ *                 projector's definition; two passes in fp64; workspace ganlab_w_moments_workspace(D) bytes, 8-byte aligned.
+ *   project_step: one launch of one workgroup.  step[0] = k, the device-resident iteration count; hyper = 6 HOST doubles (lr0,
+ *                 initial_noise_factor, lr_rampdown_length, lr_rampup_length, noise_ramp_length, num_steps).  With t = k /
+ *                 num_steps: lr = lr0 (0.5 - 0.5 cos(pi min(1, (1 - t) / rampdown))) min(1, t / rampup); the gradient is
+ *                 grad_ws (N, L, D) itself (w_plus = 1; w_opt, m, v, noise are (N, L, D)) or its sum over L in layer order
+ *                 (w_plus = 0; they are (N, D)); Adam's update number k + 1 (betas 0.9 / 0.999, eps 1e-8, bias-corrected) of
+ *                 w_opt, m, v; step[0] = k + 1; w_in (N, L, D) = w_opt + w_std[0] initial_noise_factor max(0, 1 - t' /
+ *                 noise_ramp)^2 noise at t' = (k + 1) / num_steps, broadcast over L when w_plus = 0.  grad_ws = NULL: no update,
+ *                 step[0] stays, w_in is written at t' = k / num_steps (the first forward's input). */
+#define GANLAB_PYRAMID_MAX_LEVELS 6
+size_t ganlab_pyramid_mse_workspace(int N, int C, int R, int levels);
+int ganlab_pyramid_mse_f32(const float* x, const float* t, const float* weights, int levels, float* g, float* loss, float* terms,
+                           int N, int C, int R, void* workspace, size_t workspace_bytes, void* stream);
+int ganlab_scale_rows_f32(const float* g, const float* s, float* out, int N, long long per, void* stream);
+size_t ganlab_w_moments_workspace(int D);
+int ganlab_w_moments_f32(const float* ws, float* w_avg, float* w_std, long long M, int D, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int ganlab_project_step_f32(float* w_opt, const float* grad_ws, float* m, float* v, int* step, const float* noise,
+                            const float* w_std, float* w_in, int N, int L, int w_plus, int D, const double* hyper, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
