@@ -3,6 +3,7 @@
 Layout (mirrors the reference package `gan_lab/` for the path it replaces):
   csrc/                 hand-written gfx950 HIP kernels + C-ABI (include/ganlab_hip.h)
   _lib.py, ops.py       ctypes binding and double-differentiable autograd ops over the C-ABI
+  _ops/                 the leaf op families behind ops.py (metrics, optimiser passes, augmentation, conditioning, ...)
   utils/                custom_layers / initializer / backprop_utils / latent_utils
   stylegan/, progan/    architectures (+ learners) with the reference's module tree and API
   optim.py, parallel.py fused Adam/EWMA over flat parameter arenas; RCCL data parallelism

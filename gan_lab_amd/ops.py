@@ -1,4 +1,21 @@
-"""Autograd ops over the HIP C-ABI (include/ganlab_hip.h).
+"""Autograd ops over the HIP C-ABI (include/ganlab_hip.h): the convolution and pointwise core, and the facade of the op families.
+
+This file holds the tightly coupled core - the compute-dtype switch, ``Geom``, the packed-weight cache, the ``k_conv_*``
+launchers, the mutually recursive conv Functions, deferred tails and handoffs, the norm, resampling, loss and attention ops - and
+the module state that tests, bench.py and tools rebind (DESIGN.md 4.4a lists the names).  The leaf families, each a launcher layer
+over one or two ``csrc/*.hip`` files, live in ``gan_lab_amd/_ops/`` and are imported below by name, so ``ops.<name>`` is the one
+way in for callers:
+  _ops/core.py       plumbing (``_p``, ``_st``, ``_c``, ...) and the three autograd switches
+  _ops/metrics.py    SWD, PRDC, Frechet moments / KID, MS-SSIM, radial spectrum
+  _ops/optim.py      spectral norm, orthogonal regularisation, Adam, EWMA
+  _ops/augment.py    random draws, DiffAugment, ADA
+  _ops/cond.py       labels, conditional BatchNorm
+  _ops/hier.py       hierarchical latents, modulated BatchNorm, class projection
+  _ops/cr.py         consistency regularisation
+  _ops/cond_loss.py  class cross-entropy, contrastive losses
+  _ops/project.py    latent-space projection
+A function that reads a name which is rebound on this module stays in this file: a rebinding reaches only functions whose
+globals are this module's.  A new family goes into a new ``_ops/`` module, not at the tail of this file.
 
 Layering:
   k_*        thin launchers: torch tensors in (device memory + current stream), kernel call, tensor out.
@@ -24,64 +41,35 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import ACT_LRELU, ACT_NONE, PACK_DGRAD, PACK_FWD, ConvGeom, check
-
-
-# ---------------------------------------------------------------------------------------------- #
-# plumbing
-# ---------------------------------------------------------------------------------------------- #
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-# torch.cuda.current_stream() builds a Python Stream object through several layers of device-index resolution (~10 us;
-# a quarter of the host time of a launch-bound step): ask the C binding for the raw handle of this process's device.
-_RAW_STREAM = getattr(torch._C, '_cuda_getCurrentRawStream', None)
-_GET_DEVICE = getattr(torch._C, '_cuda_getDevice', None)
-
-
-def _st():
-    if _RAW_STREAM is None or _GET_DEVICE is None:
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    return ctypes.c_void_p(_RAW_STREAM(_GET_DEVICE()))      # two C calls (~0.3 us): follows torch.cuda.set_device
-
-
-def _c(t, what='tensor'):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-        raise TypeError(f'gan_lab_amd.ops: {what} must be a float32 tensor on the GPU (got '
-                        f'{type(t).__name__}, {getattr(t, "device", None)}, {getattr(t, "dtype", None)}); '
-                        f'the HIP path has no CPU fallback')
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _inplace(t, what):
-    """``_c`` for an operand that a kernel updates in place through its raw pointer: a non-contiguous view is an error
-    (``.contiguous()`` would update a copy)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-        raise TypeError(f'gan_lab_amd.ops: {what} must be a float32 tensor on the GPU (got '
-                        f'{type(t).__name__}, {getattr(t, "device", None)}, {getattr(t, "dtype", None)}); '
-                        f'the HIP path has no CPU fallback')
-    if not t.is_contiguous():
-        raise ValueError(f'gan_lab_amd.ops: {what} must be contiguous (shape {tuple(t.shape)}, strides {t.stride()}): '
-                         f'the kernel updates it in place')
-    return t
-
-
-def _same_numel(op, named):
-    """The raw-pointer ops walk every operand with the first one's element count."""
-    n, dev = named[0][1].numel(), named[0][1].device
-    for what, t in named[1:]:
-        if t.numel() != n or t.device != dev:
-            raise ValueError(f'gan_lab_amd.ops: {op}: {what} must have the {n} elements of {named[0][0]} on {dev} (got '
-                             f'{t.numel()} on {t.device})')
-
-
-def _gpu_device(device, what):
-    if torch.device(device).type != 'cuda':
-        raise TypeError(f'gan_lab_amd.ops: {what} draws on the GPU (got device {device!r}); the HIP path has no CPU fallback')
-
-
-def _new(shape, like):
-    return torch.empty(shape, dtype=torch.float32, device=like.device)
+from ._ops.core import (  # noqa: F401
+    _p, _RAW_STREAM, _GET_DEVICE, _st, _c, _inplace, _same_numel, _gpu_device, _new, _ct, _aligned16, _nchw, _row_workspace,
+    _INPUT_GRAD_ONLY, input_grad_only, _want_param_grads, _NO_GRAD_TOWARDS, no_grad_towards, _wants_input_grad, _DIRECT, _SINK,
+    _TAKEN, direct_grads_enabled, direct_param_grads, _sink, _take, _sunk)
+from ._ops.metrics import (  # noqa: F401
+    SWD_DESC, _swd_planes, swd_down, swd_band, swd_gather, swd_stats, swd_project, _SWD_WS, _swd_workspace, swd_sort, swd_distance,
+    swd_positions, swd_directions, PRDC_MAX_K, _prdc_rows, _prdc_vector, prdc_norms, prdc_knn, prdc_cross, MOMENTS_MAX_DIM,
+    _accumulator, moments_accum, kid_rowsums, MSSSIM_LEVELS, _msssim_images, msssim_workspace, msssim_level, msssim_finish,
+    SPECTRUM_MIN_RES, SPECTRUM_MAX_RES, SPECTRUM_WINDOWS, _spectrum_size, spectrum_scratch_bytes, _spectrum_alloc,
+    spectrum_workspace, spectrum_scratch, spectrum_feed, spectrum_finish)
+from ._ops.optim import (  # noqa: F401
+    SN_EPS, SnTable, sn_refresh, sn_backward, ortho_plan, OrthoTable, ortho_apply, lerp_rows, _adam_operands, adam_step,
+    adam_step_dev, set_step_scalars, ewma_step, EwmaTable, ewma_many)
+from ._ops.augment import (  # noqa: F401
+    randn, check_truncation, trunc_randn, randn_dev, diffaug_params, diffaug_params_dev, k_diffaug, ADA_ROW, ADA_COUNTERS,
+    ada_params, ada_params_dev, k_ada, ADA_EXT_ROW, ADA_EXT_COUNTERS, ADA_FILTER_TAPS, ADA_FILTER, ADA_NOISE, ADA_CUTOUT,
+    ADA_NEW_GROUPS, AdaDraw, ada_filter_bank, ada_ext_params, ada_ext_params_dev, k_ada_ext, ada_update, _DiffAugment,
+    _DiffAugmentAdjoint, _AdaAugment, _AdaAugmentAdjoint, diff_augment, ada_augment)
+from ._ops.cond import _labels, randint, _bn_batch_stats, _CondBatchNorm, cond_batch_norm  # noqa: F401
+from ._ops.hier import (  # noqa: F401
+    _slot_open, HierTable, _HierModulate, hier_modulate, _ModBatchNorm, _mod_rows, _mod_stats, mod_batch_norm, mod_batch_norm_cols,
+    _proj_dims, _ClassProj, _ClassProjDfeat, _ClassProjDweight, class_projection)
+from ._ops.cr import (  # noqa: F401
+    _cr_table, cr_params, cr_transform, _FirstOrderOnly, _first_order, _CrMsd, _cr_imsd_fwd, _CrImsd, _CrImsdHalves, cr_msd, cr_imsd)
+from ._ops.cond_loss import (  # noqa: F401
+    CL_MODES, CL_MAX_N, CL_MAX_E, CL_MAX_K, _cl_range, _ClassCrossEntropy, _ClassContrastive, class_cross_entropy, class_contrastive)
+from ._ops.project import (  # noqa: F401
+    PYRAMID_MAX_LEVELS, PROJECT_SCHEDULE, pyramid_max_levels, check_pyramid_weights, _PyramidMse, pyramid_mse, w_moments,
+    check_project_schedule, project_step)
 
 
 # ---- compute dtype of the dense 3x3 convolutions ---------------------------------------------------
@@ -499,125 +487,6 @@ def _packed_x3_s2(w, up, scale):
 
 def _packed_x3(w, mode, scale):
     return _packed_x3_any('conv_x3_pack', 'x3', w, mode, scale, 3)
-
-
-# ---- "input gradient only" mode ---------------------------------------------------------------------
-# torch.autograd.grad(D(x), x, create_graph=True) (the gradient-penalty pass) only needs d/dx, but a
-# Python autograd.Function cannot see which of its outputs the engine will keep: without this flag
-# every conv would also run its weight-gradient kernel there and throw the result away.  The flag is
-# a module global (the autograd engine runs backward on its own device thread).
-_INPUT_GRAD_ONLY = [False]
-
-
-class input_grad_only(object):
-    def __enter__(self):
-        self._prev = _INPUT_GRAD_ONLY[0]
-        _INPUT_GRAD_ONLY[0] = True
-
-    def __exit__(self, *exc):
-        _INPUT_GRAD_ONLY[0] = self._prev
-        return False
-
-
-def _want_param_grads():
-    return not _INPUT_GRAD_ONLY[0]
-
-
-# ---- "no gradient towards this leaf" ----------------------------------------------------------------
-# The mirror case: ``loss_d.backward()`` of the D step.  The real batch is a leaf with requires_grad (R1 needs
-# d D/d x with create_graph=True), so the sweep would also produce d loss/d x - one input-gradient kernel of the
-# first layer over the widest tensor of the network - which nobody reads.  ``with ops.no_grad_towards(x):`` makes the
-# first layer's backward skip it (a Python autograd.Function cannot see that the engine will discard an output).
-_NO_GRAD_TOWARDS = [None]
-
-
-class no_grad_towards(object):
-    def __init__(self, leaf):
-        self.ptr = leaf.data_ptr() if leaf is not None else None
-
-    def __enter__(self):
-        self._prev = _NO_GRAD_TOWARDS[0]
-        _NO_GRAD_TOWARDS[0] = self.ptr
-
-    def __exit__(self, *exc):
-        _NO_GRAD_TOWARDS[0] = self._prev
-        return False
-
-
-def _wants_input_grad(ctx, x):
-    return ctx.needs_input_grad[0] and not (_NO_GRAD_TOWARDS[0] is not None and x.grad_fn is None and
-                                            x.data_ptr() == _NO_GRAD_TOWARDS[0])
-
-
-# ---- parameter gradients written straight into the flat arena ---------------------------------------
-# ``loss.backward()`` hands every parameter gradient to an AccumulateGrad node: one ``grad += g`` launch per parameter and
-# use (~250 per StyleGAN step - a fifth of the launches of the launch-bound configurations).  Inside
-# ``with direct_param_grads():`` (the learners' backward sweeps) the gradient kernels of a parameter
-# that lives in a ``ParamArena`` write their result INTO its (zeroed) arena slot when it is the first contribution of this
-# step, and the Function returns None for it; later contributions of the same step (the critic is applied to two batches)
-# take the ordinary accumulating path.  Never active while a differentiable backward is being recorded.
-_DIRECT = [False]
-_SINK, _TAKEN = {}, {}
-
-
-def direct_grads_enabled():
-    """A/B knob GANLAB_DIRECT_GRADS=0.  The mechanism is the same with and without data parallelism: the reducer's
-    post-accumulate hooks fire when a parameter's AccumulateGrad node runs - after EVERY contributing Function, direct or not -
-    and a parameter whose Functions never ran (RgbHandoff) simply leaves its bucket to ``GradReducer.start``; the data-parallel
-    code path on one rank (GANLAB_DIST_WORLD1=1) ends bit-identical to the plain one (tools/dist1_probe.py)."""
-    import os
-    return os.environ.get('GANLAB_DIRECT_GRADS') != '0'
-
-
-class direct_param_grads(object):
-    def __init__(self, enabled=True):
-        self.enabled = bool(enabled)
-
-    def __enter__(self):
-        self._prev = _DIRECT[0]
-        _DIRECT[0] = self.enabled
-        _SINK.clear()
-        _TAKEN.clear()
-
-    def __exit__(self, *exc):
-        _DIRECT[0] = self._prev
-        _SINK.clear()
-        _TAKEN.clear()
-        return False
-
-
-def _sink(name, p):
-    """Offer parameter ``p``'s arena slot to the next launcher that allocates the output called ``name``."""
-    if not _DIRECT[0] or p is None or torch.is_grad_enabled():
-        return
-    base = p._base if p._base is not None else p
-    arena = getattr(base, '_ganlab_arena', None)
-    if arena is None or not base.is_leaf or base.grad is None or base.numel() != p.numel() or \
-            getattr(base, '_ganlab_written', -1) == arena.serial:
-        return
-    _SINK[name] = base
-
-
-def _take(name, shape, like):
-    """Output buffer ``name`` of a launcher: the offered arena slot (marked written for this step) or a fresh tensor."""
-    if _SINK:
-        base = _SINK.pop(name, None)
-        if base is not None:
-            n = 1
-            for v in shape:
-                n *= int(v)
-            if base.grad.numel() == n and base.grad.device == like.device:
-                base._ganlab_written = base._ganlab_arena.serial
-                _TAKEN[name] = True
-                return base.grad.view(shape)
-    return _new(shape, like)
-
-
-def _sunk(name):
-    """After the launcher: did it write the parameter's arena slot (-> the Function returns None for that gradient)?"""
-    if _SINK:
-        _SINK.pop(name, None)
-    return _TAKEN.pop(name, False) if _TAKEN else False
 
 
 # ---- launch observer (measurement only) -------------------------------------------------------------
@@ -1249,16 +1118,6 @@ def k_resample(x, mode, align, hin, win, adjoint):
     return y
 
 
-def _nchw(x):
-    if x.dim() == 2:
-        return x.shape[0], x.shape[1], 1
-    n, c = x.shape[0], x.shape[1]
-    hw = 1
-    for s in x.shape[2:]:
-        hw *= s
-    return n, c, hw
-
-
 def k_bias_act(x, bias, noise, noise_w, bias_scale, act, slope):
     x = _c(x)
     n, c, hw = _nchw(x)
@@ -1335,862 +1194,6 @@ def k_sum(x, scale=1.0, squared=False):
     out = _new((), x)
     check(L.ganlab_sum_f32(_p(x), _p(out), x.numel(), scale, int(squared), _p(ws), ws.numel() * 4, _st()), 'sum')
     return out
-
-
-def randn(shape, seed, offset, device):
-    """Counter-based N(0,1) (Philox4x32-10 + Box-Muller) - replaces torch.randn for latents
-    (utils/latent_utils.py:15) and per-layer noise (stylegan/architectures.py:115-116)."""
-    _gpu_device(device, 'randn')
-    out = torch.empty(shape, dtype=torch.float32, device=device)
-    check(_lib.lib().ganlab_randn_f32(_p(out), out.numel(), int(seed) & (2 ** 64 - 1), int(offset), _st()), 'randn')
-    return out
-
-
-def check_truncation(threshold, what='threshold'):
-    """The truncation threshold of ``trunc_randn`` as a float: finite and > 0, else ValueError."""
-    try:
-        t = float(threshold)
-    except (TypeError, ValueError):
-        raise ValueError(f'{what} must be a finite number > 0 (got {threshold!r})') from None
-    if isinstance(threshold, bool) or not (0.0 < t < float('inf')) or float(np.float32(t)) in (0.0, float('inf')):
-        raise ValueError(f'{what} must be a finite number > 0 (got {threshold!r})')
-    return t
-
-
-def trunc_randn(shape, threshold, seed, offset, device):
-    """Counter-based draws of N(0,1) truncated to [-threshold, threshold] by inverse CDF (csrc/sample.hip): ``randn``'s Philox
-    counters - element i is word i % 4 of counter ``offset + i // 4`` - and its advance of ceil(n / 4), no rejection loop."""
-    t = check_truncation(threshold)
-    out = _c(torch.empty(shape, dtype=torch.float32, device=device), 'trunc_randn output')
-    check(_lib.lib().ganlab_trunc_randn_f32(_p(out), out.numel(), t, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
-                                            _st()), 'trunc_randn')
-    return out
-
-
-def randn_dev(shape, seed, base, delta, device):
-    """``randn`` at stream position ``*base + delta`` (``base``: the step-scalar block of graphs.GraphedStep)."""
-    _gpu_device(device, 'randn_dev')
-    if not isinstance(base, torch.Tensor) or not base.is_cuda:
-        raise TypeError(f'gan_lab_amd.ops: randn_dev base must be the step-scalar block, a tensor on the GPU (got '
-                        f'{type(base).__name__}, {getattr(base, "device", None)}); the HIP path has no CPU fallback')
-    if not base.is_contiguous() or base.numel() * base.element_size() < 8:
-        raise ValueError(f'gan_lab_amd.ops: randn_dev base must be contiguous and hold the 8-byte stream position (got '
-                         f'{base.numel()} x {base.dtype}, strides {base.stride()})')
-    out = torch.empty(shape, dtype=torch.float32, device=device)
-    check(_lib.lib().ganlab_randn_dev_f32(_p(out), out.numel(), int(seed) & (2 ** 64 - 1), _p(base), int(delta), _st()),
-          'randn_dev')
-    return out
-
-
-def diffaug_params(n, h, w, seed, offset, device):
-    """(n, 8) DiffAugment parameter rows (b, s, c, tx, ty, ox, oy, 0) from the Philox stream at ``offset`` (2 counters per row;
-    csrc/augment.hip)."""
-    out = torch.empty((int(n), 8), dtype=torch.float32, device=device)
-    check(_lib.lib().ganlab_diffaug_params_f32(_p(out), int(n), int(h), int(w), int(seed) & (2 ** 64 - 1), int(offset), _st()),
-          'diffaug_params')
-    return out
-
-
-def diffaug_params_dev(n, h, w, seed, base, delta, device):
-    """``diffaug_params`` at stream position ``*base + delta`` (``base``: the step-scalar block of graphs.GraphedStep)."""
-    out = torch.empty((int(n), 8), dtype=torch.float32, device=device)
-    check(_lib.lib().ganlab_diffaug_params_dev_f32(_p(out), int(n), int(h), int(w), int(seed) & (2 ** 64 - 1), _p(base),
-                                                   int(delta), _st()), 'diffaug_params_dev')
-    return out
-
-
-def k_diffaug(x, params, policy, adjoint=False):
-    """DiffAugment of an (N, 3, H, W) batch (``adjoint``: the transpose of its linear part, applied to a cotangent)."""
-    x, params = _c(x, 'diff_augment input'), _c(params, 'diff_augment params')
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[3] % 4 != 0 or tuple(params.shape) != (x.shape[0], 8):
-        raise ValueError(f'diff_augment: needs an (N, 3, H, W) batch with W % 4 == 0 and (N, 8) params, got '
-                         f'{tuple(x.shape)} and {tuple(params.shape)}')
-    n, _, h, w = x.shape
-    L = _lib.lib()
-    nbytes = (L.ganlab_diffaug_bwd_workspace if adjoint else L.ganlab_diffaug_fwd_workspace)(n, h, w, int(policy))
-    ws = torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=x.device)
-    out = torch.empty_like(x)
-    fn = L.ganlab_diffaug_bwd_f32 if adjoint else L.ganlab_diffaug_fwd_f32
-    check(fn(_p(x), _p(params), _p(out), n, h, w, int(policy), _p(ws), ws.numel() * 4, _st()),
-          'diffaug_bwd' if adjoint else 'diffaug_fwd')
-    return out
-
-
-ADA_ROW, ADA_COUNTERS = 32, 8        # GANLAB_ADA_ROW, GANLAB_ADA_COUNTERS (include/ganlab_hip.h)
-
-
-def ada_params(n, h, w, state, policy, seed, offset, device):
-    """(n, 32) ADA parameter rows (M, G, C, gates and raw geometric draws; csrc/ada.hip) from the Philox stream at ``offset``
-    (8 counters per row).  ``state``: the device block whose first float is p; ``policy``: bit mask (``ada.parse_policy``)."""
-    state = _c(state, 'ada_params state')
-    out = torch.empty((int(n), ADA_ROW), dtype=torch.float32, device=device)
-    check(_lib.lib().ganlab_ada_params_f32(_p(out), int(n), int(h), int(w), _p(state), int(policy), int(seed) & (2 ** 64 - 1),
-                                           int(offset), _st()), 'ada_params')
-    return out
-
-
-def ada_params_dev(n, h, w, state, policy, seed, base, delta, device):
-    """``ada_params`` at stream position ``*base + delta`` (``base``: the step-scalar block of graphs.GraphedStep)."""
-    state = _c(state, 'ada_params state')
-    out = torch.empty((int(n), ADA_ROW), dtype=torch.float32, device=device)
-    check(_lib.lib().ganlab_ada_params_dev_f32(_p(out), int(n), int(h), int(w), _p(state), int(policy),
-                                               int(seed) & (2 ** 64 - 1), _p(base), int(delta), _st()), 'ada_params_dev')
-    return out
-
-
-def k_ada(x, params, adjoint=False):
-    """ADA warp + color matrix of an (N, 3, H, W) batch (``adjoint``: the transpose of its linear part, applied to a
-    cotangent)."""
-    x, params = _c(x, 'ada_augment input'), _c(params, 'ada_augment params')
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[3] % 4 != 0 or tuple(params.shape) != (x.shape[0], ADA_ROW):
-        raise ValueError(f'ada_augment: needs an (N, 3, H, W) batch with W % 4 == 0 and (N, {ADA_ROW}) params, got '
-                         f'{tuple(x.shape)} and {tuple(params.shape)}')
-    n, _, h, w = x.shape
-    out = torch.empty_like(x)
-    L = _lib.lib()
-    fn = L.ganlab_ada_bwd_f32 if adjoint else L.ganlab_ada_fwd_f32
-    check(fn(_p(x), _p(params), _p(out), n, h, w, _st()), 'ada_bwd' if adjoint else 'ada_fwd')
-    return out
-
-
-ADA_EXT_ROW, ADA_EXT_COUNTERS, ADA_FILTER_TAPS = 16, 4, 43      # GANLAB_ADA_EXT_ROW, ..._EXT_COUNTERS, ..._FILTER_TAPS
-ADA_FILTER, ADA_NOISE, ADA_CUTOUT = 8, 16, 32       # GANLAB_ADA_FILTER, GANLAB_ADA_NOISE, GANLAB_ADA_CUTOUT
-ADA_NEW_GROUPS = ADA_FILTER | ADA_NOISE | ADA_CUTOUT
-
-
-class AdaDraw(object):
-    """What one ADA draw with a filter, noise or cutout group holds: the (N, 32) ``params`` rows, the (N, 16) ``ext`` rows and the
-    (N, 3, H, W) ``noise`` field (None without the noise group).  Slicing along the batch slices all three, so a learner hands
-    rows [0, B) to one batch and [B, 2B) to the other as it does with a plain tensor of rows."""
-
-    def __init__(self, params, ext, noise=None):
-        self.params, self.ext, self.noise = params, ext, noise
-
-    def __getitem__(self, rows):
-        if not isinstance(rows, slice):
-            raise TypeError('AdaDraw: only slices along the batch are supported')
-        return AdaDraw(self.params[rows], self.ext[rows], None if self.noise is None else self.noise[rows])
-
-    def __len__(self):
-        return self.params.shape[0]
-
-
-def ada_filter_bank():
-    """The library's (4, 43) float64 filter bank (csrc/ada_filter_bank.h), on the host."""
-    out = torch.empty((4, ADA_FILTER_TAPS), dtype=torch.float64)
-    check(_lib.lib().ganlab_ada_filter_bank(ctypes.c_void_p(out.data_ptr())), 'ada_filter_bank')
-    return out
-
-
-def ada_ext_params(n, h, w, state, policy, seed, offset, device):
-    """(n, 16) ``ext`` rows of ADA's filter, noise and cutout groups (csrc/ada_filter.hip) from the Philox stream at ``offset``
-    (4 counters per row): the position right after the main block of the batch, i.e. ``ada_params``' offset + 8 n."""
-    state = _c(state, 'ada_ext_params state')
-    out = torch.empty((int(n), ADA_EXT_ROW), dtype=torch.float32, device=device)
-    check(_lib.lib().ganlab_ada_ext_params_f32(_p(out), int(n), int(h), int(w), _p(state), int(policy),
-                                               int(seed) & (2 ** 64 - 1), int(offset), _st()), 'ada_ext_params')
-    return out
-
-
-def ada_ext_params_dev(n, h, w, state, policy, seed, base, delta, device):
-    """``ada_ext_params`` at stream position ``*base + delta`` (``base``: the step-scalar block of graphs.GraphedStep)."""
-    state = _c(state, 'ada_ext_params state')
-    out = torch.empty((int(n), ADA_EXT_ROW), dtype=torch.float32, device=device)
-    check(_lib.lib().ganlab_ada_ext_params_dev_f32(_p(out), int(n), int(h), int(w), _p(state), int(policy),
-                                                   int(seed) & (2 ** 64 - 1), _p(base), int(delta), _st()),
-          'ada_ext_params_dev')
-    return out
-
-
-def k_ada_ext(x, ext, noise=None, adjoint=False):
-    """cutout(noise(filter(x))) of an (N, 3, H, W) batch under the (N, 16) ``ext`` rows (``adjoint``: F^T (mask o x), the
-    transpose of its linear part, applied to a cotangent; ``noise`` is not read)."""
-    x, ext = _c(x, 'ada_augment input'), _c(ext, 'ada_augment ext')
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[3] % 4 != 0 or x.shape[2] < 2 or \
-            tuple(ext.shape) != (x.shape[0], ADA_EXT_ROW):
-        raise ValueError(f'ada_augment: needs an (N, 3, H, W) batch with H >= 2, W % 4 == 0 and (N, {ADA_EXT_ROW}) ext rows, '
-                         f'got {tuple(x.shape)} and {tuple(ext.shape)}')
-    n, _, h, w = x.shape
-    out = torch.empty_like(x)
-    L = _lib.lib()
-    if adjoint:
-        check(L.ganlab_ada_ext_bwd_f32(_p(x), _p(ext), _p(out), n, h, w, _st()), 'ada_ext_bwd')
-        return out
-    if noise is not None:
-        noise = _c(noise, 'ada_augment noise')
-        if tuple(noise.shape) != tuple(x.shape):
-            raise ValueError(f'ada_augment: the noise field must have the batch\'s shape {tuple(x.shape)}, got '
-                             f'{tuple(noise.shape)}')
-    check(L.ganlab_ada_ext_fwd_f32(_p(x), _p(ext), _p(noise) if noise is not None else None, _p(out), n, h, w, _st()),
-          'ada_ext_fwd')
-    return out
-
-
-def ada_update(state, logits, interval, step_size, target):
-    """The ADA controller (csrc/ada.hip) on the device block ``state`` = (p, acc_sum, acc_n, calls); ``logits`` None only
-    counts the call.  In place, no host read: capturable."""
-    state = _c(state, 'ada_update state')
-    if tuple(state.shape) != (4,):
-        raise ValueError(f'ada_update: state must be 4 floats (p, acc_sum, acc_n, calls), got {tuple(state.shape)}')
-    n = 0
-    if logits is not None:
-        logits = _c(logits, 'ada_update logits').reshape(-1)
-        n = logits.numel()
-    check(_lib.lib().ganlab_ada_update_f32(_p(state), _p(logits) if n else None, n, int(interval), float(step_size),
-                                           float(target), _st()), 'ada_update')
-    return state
-
-
-# ---- sliced Wasserstein distance (csrc/swd.hip; composed in gan_lab_amd/swd.py) ----------------------------------------------
-SWD_DESC = 147                       # GANLAB_SWD_DESC (include/ganlab_hip.h)
-
-
-def _ct(t, dtype, what):
-    """``_c`` for the non-fp32 operands of the SWD kernels (int32 centres, fp64 partials and statistics)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
-        raise TypeError(f'gan_lab_amd.ops: {what} must be a {dtype} tensor on the GPU (got {type(t).__name__}, '
-                        f'{getattr(t, "device", None)}, {getattr(t, "dtype", None)}); the HIP path has no CPU fallback')
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _swd_planes(x, what):
-    x = _c(x, what)
-    if x.dim() < 2 or x.shape[-1] % 2 or x.shape[-2] % 2 or min(x.shape[-2:]) < 4:
-        raise ValueError(f'{what}: needs (..., H, W) planes with even H, W >= 4, got {tuple(x.shape)}')
-    return x
-
-
-def swd_down(x):
-    """Pyramid step down: the 5x5 binomial filter with mirror boundary, every second pixel kept."""
-    x = _swd_planes(x, 'swd_down input')
-    h, w = x.shape[-2:]
-    out = torch.empty(x.shape[:-2] + (h // 2, w // 2), dtype=torch.float32, device=x.device)
-    check(_lib.lib().ganlab_swd_down_f32(_p(x), _p(out), x.numel() // (h * w), h, w, _st()), 'swd_down')
-    return out
-
-
-def swd_band(g0, g1):
-    """Laplacian band ``g0 - up(g1)`` (zero-insert upsample and its filter are never materialised)."""
-    g0, g1 = _swd_planes(g0, 'swd_band fine level'), _c(g1, 'swd_band coarse level')
-    h, w = g0.shape[-2:]
-    if tuple(g1.shape) != tuple(g0.shape[:-2]) + (h // 2, w // 2):
-        raise ValueError(f'swd_band: coarse level must be {tuple(g0.shape[:-2]) + (h // 2, w // 2)}, got {tuple(g1.shape)}')
-    out = torch.empty_like(g0)
-    check(_lib.lib().ganlab_swd_band_f32(_p(g0), _p(g1), _p(out), g0.numel() // (h * w), h, w, _st()), 'swd_band')
-    return out
-
-
-def swd_gather(band, pos, desc, partials):
-    """Descriptor rows of an (N, 3, S, S) level at the (N, n, 2) int32 centres ``pos`` into ``desc`` ((N n, 147) rows of a
-    preallocated set buffer) and the per-image fp64 channel sums into ``partials`` ((N, 6))."""
-    band, pos = _c(band, 'swd_gather level'), _ct(pos, torch.int32, 'swd_gather positions')
-    if band.dim() != 4 or band.shape[1] != 3 or band.shape[2] != band.shape[3] or band.shape[2] < 7 or pos.dim() != 3 or \
-            pos.shape[0] != band.shape[0] or pos.shape[2] != 2:
-        raise ValueError(f'swd_gather: needs an (N, 3, S, S) level with S >= 7 and (N, n, 2) positions, got '
-                         f'{tuple(band.shape)} and {tuple(pos.shape)}')
-    n_img, n = pos.shape[:2]
-    _c(desc, 'swd_gather descriptors'), _ct(partials, torch.float64, 'swd_gather partials')
-    if not desc.is_contiguous() or not partials.is_contiguous() or tuple(desc.shape) != (n_img * n, SWD_DESC) or \
-            tuple(partials.shape) != (n_img, 6):
-        raise ValueError(f'swd_gather: outputs must be contiguous ({n_img * n}, {SWD_DESC}) and ({n_img}, 6), got '
-                         f'{tuple(desc.shape)} and {tuple(partials.shape)}')
-    check(_lib.lib().ganlab_swd_gather_f32(_p(band), _p(pos), _p(desc), _p(partials), n_img, n, band.shape[2], _st()),
-          'swd_gather')
-    return desc
-
-
-def swd_stats(partials, per_image):
-    """(6,) fp64: per-channel mean, then population standard deviation, from the (images, 6) partials of ``swd_gather``
-    (``per_image`` values per channel and image); reduced in a fixed order."""
-    partials = _ct(partials, torch.float64, 'swd_stats partials')
-    if partials.dim() != 2 or partials.shape[1] != 6 or partials.shape[0] < 1:
-        raise ValueError(f'swd_stats: partials must be (images, 6), got {tuple(partials.shape)}')
-    out = torch.empty(6, dtype=torch.float64, device=partials.device)
-    check(_lib.lib().ganlab_swd_stats_f64(_p(partials), partials.shape[0], int(per_image), _p(out), _st()), 'swd_stats')
-    return out
-
-
-def swd_project(desc, dirs, stats, out=None):
-    """(D, M) projections of the normalised descriptors: ``dirs @ ((desc - mean) / std).T`` with the per-channel ``stats`` of
-    ``swd_stats`` applied as the rows are loaded (fp32 MFMA)."""
-    desc, dirs, stats = _c(desc, 'swd_project descriptors'), _c(dirs, 'swd_project directions'), \
-        _ct(stats, torch.float64, 'swd_project statistics')
-    if desc.dim() != 2 or desc.shape[1] != SWD_DESC or dirs.dim() != 2 or dirs.shape[1] != SWD_DESC or stats.numel() != 6:
-        raise ValueError(f'swd_project: needs (M, {SWD_DESC}) descriptors, (D, {SWD_DESC}) directions and 6 statistics, got '
-                         f'{tuple(desc.shape)}, {tuple(dirs.shape)}, {tuple(stats.shape)}')
-    m, d = desc.shape[0], dirs.shape[0]
-    if out is None:
-        out = torch.empty((d, m), dtype=torch.float32, device=desc.device)
-    elif tuple(_c(out, 'swd_project output').shape) != (d, m) or not out.is_contiguous():
-        raise ValueError(f'swd_project: output must be a contiguous ({d}, {m}) tensor, got {tuple(out.shape)}')
-    check(_lib.lib().ganlab_swd_project_f32(_p(desc), _p(dirs), _p(stats), _p(out), m, d, _st()), 'swd_project')
-    return out
-
-
-_SWD_WS = {}
-
-
-def _swd_workspace(nbytes, device):
-    ws = _SWD_WS.get(device)
-    if ws is None or ws.numel() < nbytes:
-        ws = _SWD_WS[device] = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-    return ws
-
-
-def swd_sort(x, out=None):
-    """Each row of a (D, M) buffer sorted ascending (rocPRIM radix sorts inside the library)."""
-    x = _c(x, 'swd_sort input')
-    if x.dim() != 2 or x.numel() == 0:
-        raise ValueError(f'swd_sort: needs a non-empty (D, M) tensor, got {tuple(x.shape)}')
-    if out is None:
-        out = torch.empty_like(x)
-    elif tuple(_c(out, 'swd_sort output').shape) != tuple(x.shape) or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
-        raise ValueError('swd_sort: output must be a contiguous tensor of the input\'s shape that does not alias it')
-    d, m = x.shape
-    L = _lib.lib()
-    nbytes = L.ganlab_swd_sort_workspace(d, m)
-    if nbytes == 0:
-        raise ValueError(f'swd_sort: a ({d}, {m}) buffer is refused (D * M must stay below 2^32 - 1)')
-    ws = _swd_workspace(nbytes, x.device)
-    check(L.ganlab_swd_sort_f32(_p(x), _p(out), d, m, _p(ws), ws.numel(), _st()), 'swd_sort')
-    return out
-
-
-def swd_distance(a, b):
-    """0-d fp64 device tensor: mean |a - b| over two sorted (D, M) buffers (fp64 partials, fixed order)."""
-    a, b = _c(a, 'swd_distance a'), _c(b, 'swd_distance b')
-    if a.dim() != 2 or a.shape != b.shape or a.numel() == 0:
-        raise ValueError(f'swd_distance: needs two equal non-empty (D, M) tensors, got {tuple(a.shape)} and {tuple(b.shape)}')
-    d, m = a.shape
-    L = _lib.lib()
-    ws = torch.empty(L.ganlab_swd_distance_workspace(d, m), dtype=torch.uint8, device=a.device)
-    out = torch.empty(1, dtype=torch.float64, device=a.device)
-    check(L.ganlab_swd_distance_f64(_p(a), _p(b), _p(out), d, m, _p(ws), ws.numel(), _st()), 'swd_distance')
-    return out[0]
-
-
-def swd_positions(n_images, n_per_image, size, seed, offset, device):
-    """(n_images, n_per_image, 2) int32 patch centres uniform in [3, size - 4] from the Philox stream at ``offset``
-    (ceil(n_per_image / 2) counters per image)."""
-    if int(size) < 7 or int(n_images) < 1 or int(n_per_image) < 1:
-        raise ValueError(f'swd_positions: needs size >= 7 and positive counts, got {n_images}, {n_per_image}, {size}')
-    if torch.device(device).type != 'cuda':
-        raise TypeError(f'gan_lab_amd.ops: swd_positions draws on the GPU (got device {device!r}); the HIP path has no CPU '
-                        f'fallback')
-    out = torch.empty((int(n_images), int(n_per_image), 2), dtype=torch.int32, device=device)
-    check(_lib.lib().ganlab_swd_positions_i32(_p(out), int(n_images), int(n_per_image), int(size), int(seed) & (2 ** 64 - 1),
-                                              int(offset), _st()), 'swd_positions')
-    return out
-
-
-def swd_directions(n_dirs, seed, offset, device):
-    """(n_dirs, 147) unit-norm Gaussian directions from the Philox stream at ``offset`` (147 counters per direction)."""
-    if int(n_dirs) < 1:
-        raise ValueError(f'swd_directions: needs a positive count, got {n_dirs}')
-    if torch.device(device).type != 'cuda':
-        raise TypeError(f'gan_lab_amd.ops: swd_directions draws on the GPU (got device {device!r}); the HIP path has no CPU '
-                        f'fallback')
-    out = torch.empty((int(n_dirs), SWD_DESC), dtype=torch.float32, device=device)
-    check(_lib.lib().ganlab_swd_directions_f32(_p(out), int(n_dirs), int(seed) & (2 ** 64 - 1), int(offset), _st()),
-          'swd_directions')
-    return out
-
-
-# ---- k-nearest-neighbour precision / recall / density / coverage (csrc/prdc.hip; composed in gan_lab_amd/prdc.py) --------------
-PRDC_MAX_K = 16                      # GANLAB_PRDC_MAX_K (include/ganlab_hip.h)
-
-
-def _prdc_rows(t, what):
-    t = _c(t, what)
-    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f'{what}: needs a non-empty (rows, width) matrix, got {tuple(t.shape)}')
-    return t
-
-
-def _prdc_vector(t, dtype, n, what):
-    t = _ct(t, dtype, what)
-    if tuple(t.shape) != (n,) or not t.is_contiguous():
-        raise ValueError(f'{what}: must be a contiguous ({n},) tensor, got {tuple(t.shape)}')
-    return t
-
-
-def prdc_norms(rows, out=None):
-    """(N,) squared Euclidean norms of the rows of an (N, D) matrix: fp64 sums in a fixed order, rounded once."""
-    rows = _prdc_rows(rows, 'prdc_norms rows')
-    n, d = rows.shape
-    out = _new((n,), rows) if out is None else _prdc_vector(out, torch.float32, n, 'prdc_norms out')
-    check(_lib.lib().ganlab_prdc_norms_f32(_p(rows), _p(out), n, d, _st()), 'prdc_norms')
-    return out
-
-
-def prdc_knn(rows, k, norms=None, out=None):
-    """(N, k): per row of the (N, D) matrix the ``k`` smallest squared distances to the OTHER rows, ascending - the row itself is
-    excluded by index, a duplicate at another index counts; the last column is the k-NN radius.  ``norms``: ``prdc_norms(rows)``
-    when the caller already has them."""
-    rows = _prdc_rows(rows, 'prdc_knn rows')
-    n, d = rows.shape
-    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= PRDC_MAX_K:
-        raise ValueError(f'prdc_knn: k must be an integer in [1, {PRDC_MAX_K}], got {k!r}')
-    if k >= n:
-        raise ValueError(f'prdc_knn: k must be below the number of rows (k = {k}, rows = {n})')
-    norms = prdc_norms(rows) if norms is None else _prdc_vector(norms, torch.float32, n, 'prdc_knn norms')
-    if out is None:
-        out = _new((n, k), rows)
-    elif tuple(_c(out, 'prdc_knn out').shape) != (n, k) or not out.is_contiguous():
-        raise ValueError(f'prdc_knn: out must be a contiguous ({n}, {k}) tensor, got {tuple(out.shape)}')
-    check(_lib.lib().ganlab_prdc_knn_f32(_p(rows), _p(norms), _p(out), n, d, k, _st()), 'prdc_knn')
-    return out
-
-
-def prdc_cross(queries, keys, radii, radius_of='key', query_norms=None, key_norms=None, out=None):
-    """Queries (M, D) against keys (N, D) under a radius per key (``radius_of='key'``: ``radii`` is (N,)) or per query
-    (``'query'``: (M,)).  Returns per query row (count int32, smallest squared distance fp32, its key index int32): the number of
-    keys with squared distance <= the radius, and the nearest key, the lowest index of a tie.  ``out``: the three tensors."""
-    queries, keys = _prdc_rows(queries, 'prdc_cross queries'), _prdc_rows(keys, 'prdc_cross keys')
-    (m, d), (n, dk) = queries.shape, keys.shape
-    if d != dk:
-        raise ValueError(f'prdc_cross: queries and keys must have one width, got {d} and {dk}')
-    if radius_of not in ('key', 'query'):
-        raise ValueError(f"prdc_cross: radius_of must be 'key' or 'query', got {radius_of!r}")
-    radii = _prdc_vector(radii, torch.float32, n if radius_of == 'key' else m, f'prdc_cross radii (one per {radius_of})')
-    query_norms = prdc_norms(queries) if query_norms is None else \
-        _prdc_vector(query_norms, torch.float32, m, 'prdc_cross query_norms')
-    key_norms = prdc_norms(keys) if key_norms is None else _prdc_vector(key_norms, torch.float32, n, 'prdc_cross key_norms')
-    if out is None:
-        out = (torch.empty((m,), dtype=torch.int32, device=queries.device), _new((m,), queries),
-               torch.empty((m,), dtype=torch.int32, device=queries.device))
-    count = _prdc_vector(out[0], torch.int32, m, 'prdc_cross count')
-    dmin = _prdc_vector(out[1], torch.float32, m, 'prdc_cross smallest distance')
-    imin = _prdc_vector(out[2], torch.int32, m, 'prdc_cross nearest index')
-    check(_lib.lib().ganlab_prdc_cross_f32(_p(queries), _p(query_norms), _p(keys), _p(key_norms), _p(radii),
-                                           1 if radius_of == 'query' else 0, _p(count), _p(dmin), _p(imin), m, n, d, _st()),
-          'prdc_cross')
-    return count, dmin, imin
-
-
-# ---- Frechet moments and KID row sums (csrc/frechet.hip, csrc/kid.hip; composed in gan_lab_amd/frechet.py and kid.py) ------------
-MOMENTS_MAX_DIM = 4096               # ganlab_moments_accum_f32: a (D, D) float64 second-moment matrix of 128 MiB
-
-
-def _accumulator(t, shape, what):
-    """A float64 tensor a kernel adds into through its raw pointer: a non-contiguous view is an error."""
-    if isinstance(t, torch.Tensor) and (tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
-        raise ValueError(f'{what}: must be a contiguous {tuple(shape)} tensor, got {tuple(t.shape)} with strides {t.stride()}')
-    return _ct(t, torch.float64, what)
-
-
-def moments_accum(rows, pivot, sum, gram):
-    """``sum[a] += sum_i (x_ia - c_a)`` and ``gram[a][b] += sum_i (x_ia - c_a)(x_ib - c_b)`` over the rows of an (n, D) fp32
-    matrix, ``c`` the (D,) fp32 ``pivot``; ``sum`` (D,) and ``gram`` (D, D) are float64 and accumulated into (zero them before the
-    first call).  ``gram`` is written in full and stays exactly symmetric.  D <= 4096."""
-    rows = _prdc_rows(rows, 'moments_accum rows')
-    n, d = rows.shape
-    if d > MOMENTS_MAX_DIM:
-        raise ValueError(f'moments_accum: the width must be at most {MOMENTS_MAX_DIM}, got {d}')
-    pivot = _prdc_vector(pivot, torch.float32, d, 'moments_accum pivot')
-    sum = _accumulator(sum, (d,), 'moments_accum sum')
-    gram = _accumulator(gram, (d, d), 'moments_accum gram')
-    check(_lib.lib().ganlab_moments_accum_f32(_p(rows), n, d, _p(pivot), _p(sum), _p(gram), _st()), 'moments_accum')
-    return sum, gram
-
-
-def kid_rowsums(queries, keys, gamma, coef0=1.0, exclude_diag=False, out=None):
-    """(M,) float64: ``out[i] = sum_j (gamma q_i.k_j + coef0)^3`` of the queries (M, D) against the keys (N, D); the dot product
-    and ``gamma dot + coef0`` (one fma) in fp32, the cube and the sum in float64.  ``exclude_diag`` leaves ``j == i`` out by index
-    and needs M == N."""
-    queries, keys = _prdc_rows(queries, 'kid_rowsums queries'), _prdc_rows(keys, 'kid_rowsums keys')
-    (m, d), (n, dk) = queries.shape, keys.shape
-    if d != dk:
-        raise ValueError(f'kid_rowsums: queries and keys must have one width, got {d} and {dk}')
-    if exclude_diag and m != n:
-        raise ValueError(f'kid_rowsums: exclude_diag leaves out the term j == i and needs as many queries as keys, got {m} and {n}')
-    gamma, coef0 = float(gamma), float(coef0)
-    if gamma != gamma or coef0 != coef0:
-        raise ValueError(f'kid_rowsums: gamma and coef0 must be numbers, got {gamma!r} and {coef0!r}')
-    out = torch.empty((m,), dtype=torch.float64, device=queries.device) if out is None else \
-        _prdc_vector(out, torch.float64, m, 'kid_rowsums out')
-    check(_lib.lib().ganlab_kid_rowsums_f32(_p(queries), m, _p(keys), n, d, gamma, coef0, 1 if exclude_diag else 0, _p(out),
-                                            _st()), 'kid_rowsums')
-    return out
-
-
-# ---- multi-scale structural similarity (csrc/msssim.hip; composed in gan_lab_amd/msssim.py) -------------------------------------
-MSSSIM_LEVELS = 5                    # GANLAB_MSSSIM_LEVELS (include/ganlab_hip.h)
-
-
-def _msssim_images(t, side, what):
-    """A (k, 3, side, side) fp32 GPU tensor whose images are contiguous (3, side, side) blocks a fixed number of floats apart:
-    a whole batch, or every second image of one (``x[0::2]``).  Never copied: the kernel takes the stride."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-        raise TypeError(f'gan_lab_amd.ops: {what} must be a float32 tensor on the GPU (got {type(t).__name__}, '
-                        f'{getattr(t, "device", None)}, {getattr(t, "dtype", None)}); the HIP path has no CPU fallback')
-    if t.dim() != 4 or tuple(t.shape[1:]) != (3, side, side) or t.shape[0] < 1 or \
-            tuple(t.stride()[1:]) != (side * side, side, 1) or \
-            (t.shape[0] > 1 and t.stride(0) < 3 * side * side):
-        raise ValueError(f'{what}: needs (k, 3, {side}, {side}) images, each contiguous, got shape {tuple(t.shape)} strides '
-                         f'{tuple(t.stride())}')
-    return t
-
-
-def msssim_workspace(pairs, res, device):
-    """The fp64 per-tile partials of an evaluation of ``pairs`` pairs at ``res`` x ``res`` (all five levels), uninitialised."""
-    if torch.device(device).type != 'cuda':
-        raise TypeError(f'gan_lab_amd.ops: msssim_workspace allocates on the GPU (got device {device!r}); the HIP path has no '
-                        f'CPU fallback')
-    nbytes = _lib.lib().ganlab_msssim_workspace(int(pairs), int(res))
-    if nbytes == 0:
-        raise ValueError(f'msssim_workspace: needs pairs >= 1 and a power-of-two resolution in [16, 16384], got {pairs}, {res}')
-    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
-
-
-def msssim_level(a, b, level, res, c1, c2, workspace, first, pairs, next_a=None, next_b=None):
-    """Level ``level`` (side ``res >> level``) of pairs ``first ..`` of an evaluation of ``pairs`` pairs: their (cs, ssim) tile
-    partials go into ``workspace``, the 2 x 2 means of both images into ``next_a`` / ``next_b`` (None at the last level)."""
-    side = int(res) >> int(level)
-    a, b = _msssim_images(a, side, 'msssim_level a'), _msssim_images(b, side, 'msssim_level b')
-    count = a.shape[0]
-    workspace = _ct(workspace, torch.float64, 'msssim_level workspace')
-    if b.shape[0] != count or (count > 1 and a.stride(0) != b.stride(0)):
-        raise ValueError(f'msssim_level: a and b must hold the same number of images at the same stride, got '
-                         f'{tuple(a.shape)} / {a.stride(0)} and {tuple(b.shape)} / {b.stride(0)}')
-    if (next_a is None) != (next_b is None):
-        raise ValueError('msssim_level: next_a and next_b come together')
-    nstride = 0
-    if next_a is not None:
-        next_a = _msssim_images(next_a, side // 2, 'msssim_level next_a')
-        next_b = _msssim_images(next_b, side // 2, 'msssim_level next_b')
-        if next_a.shape[0] != count or next_b.shape[0] != count or (count > 1 and next_a.stride(0) != next_b.stride(0)):
-            raise ValueError(f'msssim_level: next_a and next_b must hold {count} images at one stride, got '
-                             f'{tuple(next_a.shape)} and {tuple(next_b.shape)}')
-        nstride = next_a.stride(0) if count > 1 else 3 * (side // 2) ** 2
-    stride = a.stride(0) if count > 1 else 3 * side * side
-    check(_lib.lib().ganlab_msssim_level_f32(_p(a), _p(b), stride, _p(next_a), _p(next_b), nstride, int(first), count,
-                                             int(pairs), int(res), int(level), float(c1), float(c2), _p(workspace),
-                                             workspace.numel() * 8, _st()), 'msssim_level')
-
-
-def msssim_finish(workspace, pairs, res, table, values, out):
-    """The evaluation's partials -> ``table`` (pairs, 5, 2) = (CS_i, SSIM_i) clamped at 0, ``values`` (pairs,) = the weighted
-    products, ``out`` (6,) = mean value, mean CS_0..3, mean SSIM_4; all fp64, fixed order."""
-    workspace = _ct(workspace, torch.float64, 'msssim_finish workspace')
-    for t, shape, what in ((table, (pairs, MSSSIM_LEVELS, 2), 'table'), (values, (pairs,), 'values'), (out, (6,), 'out')):
-        if tuple(_ct(t, torch.float64, f'msssim_finish {what}').shape) != shape or not t.is_contiguous():
-            raise ValueError(f'msssim_finish: {what} must be a contiguous {shape} tensor, got {tuple(t.shape)}')
-    check(_lib.lib().ganlab_msssim_finish_f64(_p(workspace), workspace.numel() * 8, int(pairs), int(res), _p(table), _p(values),
-                                              _p(out), _st()), 'msssim_finish')
-    return out
-
-
-# ---- radial power spectrum (csrc/spectrum.hip; composed in gan_lab_amd/spectrum.py) ---------------------------------------------
-SPECTRUM_MIN_RES, SPECTRUM_MAX_RES = 16, 1024        # GANLAB_SPECTRUM_MIN_RES / _MAX_RES (include/ganlab_hip.h)
-SPECTRUM_WINDOWS = {'none': 0, 'hann': 1}            # GANLAB_SPECTRUM_WINDOW_*
-
-
-def _spectrum_size(query, count, res, what):
-    nbytes = query(int(count), int(res))
-    if nbytes == 0:
-        raise ValueError(f'{what}: needs a count >= 1 and a power-of-two resolution in [{SPECTRUM_MIN_RES}, {SPECTRUM_MAX_RES}], '
-                         f'got {count}, {res}')
-    return nbytes
-
-
-def spectrum_scratch_bytes(count, res):
-    """Bytes of scratch a feed of ``count`` images at ``res`` x ``res`` needs (a host call)."""
-    return _spectrum_size(_lib.lib().ganlab_spectrum_scratch, count, res, 'spectrum_scratch_bytes')
-
-
-def _spectrum_alloc(nbytes, device, what):
-    if torch.device(device).type != 'cuda':
-        raise TypeError(f'gan_lab_amd.ops: {what} allocates on the GPU (got device {device!r}); the HIP path has no CPU fallback')
-    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
-
-
-def spectrum_workspace(n_images, res, device):
-    """The (n_images, res / 2 + 1) fp64 per-image profiles of an evaluation, uninitialised."""
-    if torch.device(device).type != 'cuda':
-        raise TypeError(f'gan_lab_amd.ops: spectrum_workspace allocates on the GPU (got device {device!r}); the HIP path has no '
-                        f'CPU fallback')
-    nbytes = _spectrum_size(_lib.lib().ganlab_spectrum_workspace, n_images, res, 'spectrum_workspace')
-    return _spectrum_alloc(nbytes, device, 'spectrum_workspace').view(int(n_images), int(res) // 2 + 1)
-
-
-def spectrum_scratch(count, res, device):
-    """Scratch for feeds of up to ``count`` images: tables, half spectra and per-tile bin sums, uninitialised."""
-    if torch.device(device).type != 'cuda':
-        raise TypeError(f'gan_lab_amd.ops: spectrum_scratch allocates on the GPU (got device {device!r}); the HIP path has no '
-                        f'CPU fallback')
-    return _spectrum_alloc((spectrum_scratch_bytes(count, res) + 7) // 8 * 8, device, 'spectrum_scratch')
-
-
-def spectrum_feed(x, res, window, scratch, workspace, first, n_images):
-    """The profiles of the (k, 3, res, res) fp32 images ``x``, images ``first ..`` of an evaluation of ``n_images``, into their
-    rows of ``workspace``.  ``window``: 'hann' or 'none'."""
-    x = _msssim_images(x, int(res), 'spectrum_feed x')
-    if window not in SPECTRUM_WINDOWS:
-        raise ValueError(f'spectrum_feed: window must be one of {sorted(SPECTRUM_WINDOWS)}, got {window!r}')
-    scratch = _ct(scratch, torch.float64, 'spectrum_feed scratch')
-    workspace = _ct(workspace, torch.float64, 'spectrum_feed workspace')
-    count = x.shape[0]
-    stride = x.stride(0) if count > 1 else 3 * int(res) ** 2
-    check(_lib.lib().ganlab_spectrum_feed_f32(_p(x), stride, int(first), count, int(n_images), int(res), SPECTRUM_WINDOWS[window],
-                                              _p(scratch), scratch.numel() * 8, _p(workspace), workspace.numel() * 8, _st()),
-          'spectrum_feed')
-
-
-def spectrum_finish(workspace_a, workspace_b, n_images, res, out):
-    """``out`` = set a's profile S[0 .. res/2] and its decibels; with ``workspace_b`` also set b's two rows, then the distances
-    'spectrum' and 'hf': 4 (res / 2 + 1) + 2 fp64 values, else 2 (res / 2 + 1)."""
-    workspace_a = _ct(workspace_a, torch.float64, 'spectrum_finish workspace_a')
-    if workspace_b is not None:
-        workspace_b = _ct(workspace_b, torch.float64, 'spectrum_finish workspace_b')
-        if workspace_b.numel() != workspace_a.numel():
-            raise ValueError(f'spectrum_finish: the two workspaces must have one size, got {workspace_a.numel()} and '
-                             f'{workspace_b.numel()}')
-    nb = int(res) // 2 + 1
-    need = 4 * nb + 2 if workspace_b is not None else 2 * nb
-    if _ct(out, torch.float64, 'spectrum_finish out').numel() != need or not out.is_contiguous():
-        raise ValueError(f'spectrum_finish: out must be a contiguous tensor of {need} values, got {tuple(out.shape)}')
-    check(_lib.lib().ganlab_spectrum_finish_f64(_p(workspace_a), _p(workspace_b), workspace_a.numel() * 8, int(n_images), int(res),
-                                                _p(out), out.numel() * 8, _st()), 'spectrum_finish')
-    return out
-
-
-# ---- spectral normalisation: every weight of a critic per launch (csrc/spectral.hip) -----------------------------------
-SN_EPS = 1e-12      # torch.nn.utils.spectral_norm's eps
-
-
-class SnTable(object):
-    """Device-resident job table of ``ganlab_sn_refresh`` / ``ganlab_sn_backward``.  ``layers``: one dict per weight with
-    the float32 GPU tensors ``w`` (the parameter, viewed as (shape[0], -1)), ``w_sn``, ``g_sn``, ``gw`` (same numel), ``u``
-    (shape[0]), ``v`` (numel / shape[0]) and ``sigma`` (1); every one contiguous and 16-byte aligned.  Built and uploaded once
-    (outside any capture), together with the scratch the passes use; keeps the tensors it points at alive."""
-
-    def __init__(self, layers):
-        if not layers:
-            raise ValueError('SnTable: no layers')
-        RC, TC, EB = _lib.SN_ROW_CHUNK, _lib.SN_COL_TILE, _lib.SN_ELEM_BLOCK
-        self.layers = [dict(d) for d in layers]
-        dev = self.layers[0]['w'].device
-        geo, need = [], 0
-        for d in self.layers:
-            w = d['w']
-            R = int(w.shape[0])
-            K = w.numel() // R
-            want = {'w': R * K, 'w_sn': R * K, 'g_sn': R * K, 'gw': R * K, 'u': R, 'v': K, 'sigma': 1}
-            for name, n in want.items():
-                t = d[name]
-                _c(t, f'SnTable {name}')
-                if not t.is_contiguous() or t.numel() != n or t.data_ptr() % 16 or t.device != dev:
-                    raise ValueError(f'SnTable: {name} must be contiguous, 16-byte aligned, on {dev}, with {n} elements '
-                                     f'(got {tuple(t.shape)} at {t.data_ptr():#x} on {t.device})')
-            nrc, nct, neb = (R + RC - 1) // RC, (K + TC - 1) // TC, (R * K + EB - 1) // EB
-            offs = []
-            for n in (nrc * K, R, neb):
-                offs.append(need)
-                need += (n + 3) // 4 * 4
-            geo.append((R, K, nrc * nct, (R + 3) // 4, neb, offs))
-        self.scratch = torch.zeros(need, dtype=torch.float32, device=dev)
-        arr = (_lib.SnJob * len(self.layers))()
-        bt = bs = be = 0
-        base = self.scratch.data_ptr()
-        for j, d, (R, K, nt, ns, ne, offs) in zip(arr, self.layers, geo):
-            j.w, j.w_sn, j.g_sn, j.gw = d['w'].data_ptr(), d['w_sn'].data_ptr(), d['g_sn'].data_ptr(), d['gw'].data_ptr()
-            j.u, j.v, j.sigma = d['u'].data_ptr(), d['v'].data_ptr(), d['sigma'].data_ptr()
-            j.tpart, j.s, j.dpart = base + 4 * offs[0], base + 4 * offs[1], base + 4 * offs[2]
-            j.R, j.K, j.blk_t0, j.blk_s0, j.blk_e0 = R, K, bt, bs, be
-            bt, bs, be = bt + nt, bs + ns, be + ne
-        self.blocks = (bt, bs, be)
-        self.n = len(self.layers)
-        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-
-
-def sn_refresh(table, iterate):
-    """One power iteration (``iterate``) of every layer of ``table``, then sigma = u^T W v and W_sn = W / sigma: 4 launches,
-    2 without the iteration.  The caller reports the rewritten W_sn range (``bump_weight_epoch``)."""
-    bt, bs, be = table.blocks
-    check(_lib.lib().ganlab_sn_refresh(table.table.data_ptr(), table.n, bt, bs, be, 1 if iterate else 0, SN_EPS, _st()),
-          'sn_refresh')
-
-
-def sn_backward(table):
-    """gW += (g_sn - <g_sn, W_sn> u v^T) / sigma for every layer of ``table`` (2 launches)."""
-    check(_lib.lib().ganlab_sn_backward(table.table.data_ptr(), table.n, table.blocks[2], _st()), 'sn_backward')
-
-
-# ---- orthogonal regularisation: every weight of a network per launch (csrc/ortho.hip) ----------------------------------
-def ortho_plan(shapes):
-    """Host-side layout of the job table of ``ganlab_ortho_apply`` for weights of the given (R, K) shapes.  -> (entries,
-    scratch floats, (Gram blocks, apply blocks)); ``entries[i]`` is None for a layer with R == 1 (no off-diagonal element: its
-    penalty and gradient are exactly 0, it is left out) and else a dict with ``form`` (row form when R <= K, else column form:
-    the m x m Gram matrix has m = min(R, K)), ``m``, the float offsets ``s``, ``q`` (None in row form) and ``part`` into the
-    scratch, ``n_part`` and the first block ``blk_g0`` / ``blk_a0`` of either pass.  Pure arithmetic: no GPU, no library."""
-    T, QR = _lib.ORTHO_TILE, _lib.ORTHO_QROWS
-    entries, need, bg, ba = [], 0, 0, 0
-
-    def take(n):
-        nonlocal need
-        o = need
-        need += (n + 3) // 4 * 4
-        return o
-
-    for R, K in shapes:
-        R, K = int(R), int(K)
-        if R < 1 or K < 1:
-            raise ValueError(f'ortho_plan: bad weight shape ({R}, {K})')
-        if R == 1:
-            entries.append(None)
-            continue
-        row = R <= K
-        m = R if row else K
-        tm = (m + T - 1) // T
-        n_part = tm * tm + (0 if row else (R + QR - 1) // QR)
-        e = dict(R=R, K=K, form=_lib.ORTHO_ROW if row else _lib.ORTHO_COL, m=m, s=take(m * m), q=None if row else take(R),
-                 part=take(n_part), n_part=n_part, blk_g0=bg, blk_a0=ba)
-        bg += n_part
-        ba += ((R + T - 1) // T) * ((K + T - 1) // T)
-        entries.append(e)
-    return entries, need, (bg, ba)
-
-
-class OrthoTable(object):
-    """Device-resident job table of ``ganlab_ortho_apply``.  ``layers``: one dict per weight with the float32 GPU tensors ``w``
-    (the parameter, viewed as (shape[0], -1)) and ``gw`` (its gradient slot, same numel), both contiguous and 16-byte aligned.
-    Built and uploaded once (outside any capture), together with the scratch (the m x m Gram matrices, q, the partial sums) and
-    the results: ``penalties`` holds one float per layer (0 for a skipped one) and then the total.  Keeps the tensors it points
-    at alive."""
-
-    def __init__(self, layers):
-        if not layers:
-            raise ValueError('OrthoTable: no layers')
-        self.layers = [dict(d) for d in layers]
-        dev = self.layers[0]['w'].device
-        shapes = []
-        for d in self.layers:
-            w = d['w']
-            R = int(w.shape[0])
-            K = w.numel() // R
-            for name in ('w', 'gw'):
-                t = d[name]
-                _c(t, f'OrthoTable {name}')
-                if not t.is_contiguous() or t.numel() != R * K or t.data_ptr() % 16 or t.device != dev:
-                    raise ValueError(f'OrthoTable: {name} must be contiguous, 16-byte aligned, on {dev}, with {R * K} elements '
-                                     f'(got {tuple(t.shape)} at {t.data_ptr():#x} on {t.device})')
-            shapes.append((R, K))
-        self.plan, need, self.blocks = ortho_plan(shapes)
-        self.scratch = torch.zeros(max(need, 4), dtype=torch.float32, device=dev)
-        self.penalties = torch.zeros(len(self.layers) + 1, dtype=torch.float32, device=dev)
-        live = [(i, d, e) for i, (d, e) in enumerate(zip(self.layers, self.plan)) if e is not None]
-        self.n = len(live)
-        arr = (_lib.OrthoJob * max(self.n, 1))()
-        base, pen = self.scratch.data_ptr(), self.penalties.data_ptr()
-        for j, (i, d, e) in zip(arr, live):
-            j.w, j.gw = d['w'].data_ptr(), d['gw'].data_ptr()
-            j.s, j.part, j.penalty = base + 4 * e['s'], base + 4 * e['part'], pen + 4 * i
-            j.q = base + 4 * e['q'] if e['q'] is not None else None
-            j.R, j.K, j.form, j.n_part, j.blk_g0, j.blk_a0 = e['R'], e['K'], e['form'], e['n_part'], e['blk_g0'], e['blk_a0']
-        self.total = self.penalties[len(self.layers):]      # 1 element: beta * sum over all layers
-        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-
-
-def ortho_apply(table, beta):
-    """gw += 4 beta ((Wm Wm^T) o (1 - I)) Wm for every layer of ``table``, and ``table.penalties`` = beta * sum(M^2) per layer
-    and in total: 3 launches whatever the number of layers (none when every layer was skipped)."""
-    beta = float(beta)
-    if not (0.0 <= beta < float('inf')):
-        raise ValueError(f'ortho_apply: beta must be a finite number >= 0 (got {beta!r})')
-    if table.n == 0:
-        return
-    bg, ba = table.blocks
-    check(_lib.lib().ganlab_ortho_apply(table.table.data_ptr(), table.n, bg, ba, beta, _p(table.total), _st()), 'ortho_apply')
-
-
-def lerp_rows(a, b, t):
-    a, b, t = _c(a), _c(b), _c(t)
-    out = torch.empty_like(a)
-    n = a.shape[0]
-    check(_lib.lib().ganlab_lerp_rows_f32(_p(a), _p(b), _p(t), _p(out), n, a.numel() // n, _st()), 'lerp_rows')
-    return out
-
-
-def _adam_operands(op, p, g, m, v):
-    named = [('p', p), ('g', g), ('m', m), ('v', v)]
-    for what, t in named:
-        _inplace(t, f'{op} {what}')
-    _same_numel(op, named)
-
-
-def adam_step(p, g, m, v, lr, beta1, beta2, eps, wd, bc1, bc2):
-    _adam_operands('adam_step', p, g, m, v)
-    check(_lib.lib().ganlab_adam_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, wd, bc1, bc2,
-                                     _st()), 'adam')
-
-
-def adam_step_dev(p, g, m, v, scalars, beta1, beta2, eps, wd):
-    """``adam_step`` with (lr, 1 - beta1^t, 1 - beta2^t) read from the three floats at ``scalars`` (a device pointer)."""
-    _adam_operands('adam_step_dev', p, g, m, v)
-    if isinstance(scalars, bool) or not isinstance(scalars, int) or scalars <= 0:
-        raise TypeError(f'gan_lab_amd.ops: adam_step_dev scalars must be a device address inside the step-scalar block (got '
-                        f'{scalars!r})')
-    check(_lib.lib().ganlab_adam_dev_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), ctypes.c_void_p(scalars), beta1, beta2, eps,
-                                         wd, _st()), 'adam_dev')
-
-
-def set_step_scalars(block, rng_base, floats):
-    f = [float(v) for v in floats] + [0.0] * (6 - len(floats))
-    check(_lib.lib().ganlab_set_step_scalars(ctypes.c_void_p(block.data_ptr()), int(rng_base) & (2 ** 64 - 1), *f[:6],
-                                             _st()), 'set_step_scalars')
-
-
-def ewma_step(lagged, p, beta):
-    named = [('lagged', lagged), ('p', p)]
-    for what, t in named:
-        _inplace(t, f'ewma_step {what}')
-    _same_numel('ewma_step', named)
-    check(_lib.lib().ganlab_ewma_f32(_p(lagged), _p(p), p.numel(), beta, _st()), 'ewma')
-
-
-class EwmaTable(object):
-    """Device-resident job table of ``ganlab_ewma_many_f32``.  ``pairs``: [(lagged, src)], contiguous float32 GPU tensors of equal
-    size on one device, no two of them overlapping.  Built and uploaded once (outside any capture); keeps the tensors it points
-    at alive."""
-
-    def __init__(self, pairs):
-        self.pairs = [(a, b) for a, b in pairs]
-        if not self.pairs:
-            raise ValueError('EwmaTable: no segments')
-        if len(self.pairs) > 65535:
-            raise ValueError(f'EwmaTable: at most 65535 segments (got {len(self.pairs)})')
-        dev = self.pairs[0][0].device
-        arr = (_lib.EwmaJob * len(self.pairs))()
-        for j, (lagged, src) in zip(arr, self.pairs):
-            for t, what in ((lagged, 'EwmaTable lagged'), (src, 'EwmaTable src')):
-                _c(t, what)
-                if not t.is_contiguous() or t.device != dev:
-                    raise ValueError(f'{what} must be contiguous and on {dev} (got {tuple(t.shape)} on {t.device})')
-            if lagged.numel() != src.numel() or lagged.numel() < 1 or lagged.data_ptr() == src.data_ptr():
-                raise ValueError(f'EwmaTable: a segment needs two distinct tensors of one size >= 1 (got {tuple(lagged.shape)}, '
-                                 f'{tuple(src.shape)})')
-            j.dst, j.src, j.count = lagged.data_ptr(), src.data_ptr(), lagged.numel()
-        self.n = len(self.pairs)
-        self.pointers = self._pointers()
-        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-
-    def _pointers(self):
-        return tuple(t.data_ptr() for pair in self.pairs for t in pair)
-
-    def is_current(self):
-        """Do the tensors still lie where the uploaded table points?"""
-        return self.pointers == self._pointers()
-
-
-def ewma_many(table, decay):
-    """``lagged = decay * lagged + (1 - decay) * src`` for every segment of ``table`` in one launch; ``decay`` = 0 copies."""
-    decay = float(decay)
-    if not (0.0 <= decay < 1.0):
-        raise ValueError(f'ewma_many: decay must lie in [0, 1) (got {decay!r})')
-    if not table.is_current():
-        raise RuntimeError('ewma_many: a tensor of the table moved since it was built; build a new EwmaTable')
-    check(_lib.lib().ganlab_ewma_many_f32(table.table.data_ptr(), table.n, decay, _st()), 'ewma_many')
 
 
 # ---------------------------------------------------------------------------------------------- #
@@ -2813,62 +1816,6 @@ class _Resample(Function):
     def backward(ctx, g):
         mode, align, hin, win, adjoint = ctx.args
         return _Resample.apply(g, mode, align, hin, win, not adjoint), None, None, None, None, None
-
-
-class _DiffAugment(Function):
-    """DiffAugment (csrc/augment.hip): affine in x, so the backward is the adjoint of its linear part."""
-
-    @staticmethod
-    def forward(ctx, x, params, policy):
-        ctx.params, ctx.policy = params, policy
-        return k_diffaug(x, params, policy)
-
-    @staticmethod
-    def backward(ctx, g):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None
-        return _DiffAugmentAdjoint.apply(g, ctx.params, ctx.policy), None, None
-
-
-class _DiffAugmentAdjoint(Function):
-    @staticmethod
-    def forward(ctx, g, params, policy):
-        return k_diffaug(g, params, policy, adjoint=True)
-
-    @staticmethod
-    def backward(ctx, gg):
-        raise NotImplementedError('diff_augment: double backward is not implemented (the penalties differentiate at the '
-                                  'augmented batch, not through the augmentation)')
-
-
-class _AdaAugment(Function):
-    """ADA warp + color matrix (csrc/ada.hip), then with ``ext`` the filter, noise and cutout of csrc/ada_filter.hip: affine in
-    x, so the backward is the adjoint of its linear part."""
-
-    @staticmethod
-    def forward(ctx, x, params, ext=None, noise=None):
-        ctx.params, ctx.ext = params, ext
-        y = k_ada(x, params)
-        return y if ext is None else k_ada_ext(y, ext, noise)
-
-    @staticmethod
-    def backward(ctx, g):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None
-        return _AdaAugmentAdjoint.apply(g, ctx.params, ctx.ext), None, None, None
-
-
-class _AdaAugmentAdjoint(Function):
-    @staticmethod
-    def forward(ctx, g, params, ext=None):
-        if ext is not None:
-            g = k_ada_ext(g, ext, adjoint=True)
-        return k_ada(g, params, adjoint=True)
-
-    @staticmethod
-    def backward(ctx, gg):
-        raise NotImplementedError('ada_augment: double backward is not implemented (the penalties differentiate at the '
-                                  'augmented batch, not through the augmentation)')
 
 
 class _Scale(Function):
@@ -3641,11 +2588,6 @@ def channel_sum(x):
     return _ChanSum.apply(x, None, 1.0)
 
 
-def _row_workspace(rows, length, device):
-    nbytes = _lib.lib().ganlab_ln_rowsums_workspace(rows, length)
-    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-
-
 class _BatchNormTrain(Function):
     """nn.BatchNorm2d in training mode on fused kernels (csrc/norm.hip): batch statistics (2 launches), the C-element
     bookkeeping - rstd, scale, running estimates, batch counter - in one (``bn_finalize``), normalise + affine (1);
@@ -4247,34 +3189,6 @@ def chnorm_penalty(g, gamma, scale):
     return _ChNormPenalty.apply(g, float(gamma), float(scale))
 
 
-def diff_augment(x, params, policy):
-    """DiffAugment (Zhao et al. 2020) of an (N, 3, H, W) fp32 batch on the GPU: ``params`` (N, 8) rows
-    (b, s, c, tx, ty, ox, oy, 0) (``rng.augment_params``), ``policy`` a bit mask (``augment.parse_policy``).  Differentiable
-    once in ``x``."""
-    for t, what in ((x, 'diff_augment input'), (params, 'diff_augment params')):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-            _c(t, what)                 # raises TypeError: there is no CPU path
-    return _DiffAugment.apply(x, params.detach(), int(policy))
-
-
-def ada_augment(x, params, ext=None, noise=None):
-    """ADA (Karras et al. 2020) of an (N, 3, H, W) fp32 batch on the GPU: affine bilinear warp with zero fill, then a 3x4
-    color matrix, per sample from the (N, 32) ``params`` rows (``rng.ada_params`` or ``ada.rows_from_matrices``).  With
-    ``ext`` ((N, 16) rows: ``rng.ada_params`` under a policy with filter, noise or cutout, or ``ada.ext_rows``) the result
-    goes on through the per-sample 43-tap filter, ``sigma * noise`` (``noise``: an (N, 3, H, W) field of standard normals;
-    None adds none, whatever sigma says) and the cutout rectangle; with ``ext`` None nothing further is launched.
-    Differentiable once in ``x``."""
-    for t, what in ((x, 'ada_augment input'), (params, 'ada_augment params')) + \
-            (((ext, 'ada_augment ext'),) if ext is not None else ()) + (((noise, 'ada_augment noise'),) if noise is not None else ()):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-            _c(t, what)                 # raises TypeError: there is no CPU path
-    if ext is None:
-        if noise is not None:
-            raise ValueError('ada_augment: a noise field needs ext rows (their sigma scales it)')
-        return _AdaAugment.apply(x, params.detach())
-    return _AdaAugment.apply(x, params.detach(), ext.detach(), None if noise is None else noise.detach())
-
-
 def layer_tail_deferred(x, bias=None, noise=None, noise_w=None, style=None, bias_scale=1.0, act=None, slope=0.2,
                         blur=False, eps=1e-8):
     """ops.layer_tail without the normalisation pass: returns a ``Deferred`` (see there) for a modulated consumer."""
@@ -4497,854 +3411,3 @@ def gated_residual(x, y, gamma):
     return _GatedResidual.apply(x, y, gamma)
 
 
-# ---------------------------------------------------------------------------------------------- #
-# class conditioning (csrc/cond.hip; conditional.py): conditional BatchNorm, the projection critic's class term
-# ---------------------------------------------------------------------------------------------- #
-def _labels(labels, n, what):
-    """Class labels at the ops boundary: a device tensor of shape (n,), int32 (int64 is converted)."""
-    if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f'gan_lab_amd.ops: {what} labels must be an int32 / int64 tensor on the GPU (got '
-                        f'{type(labels).__name__}, {getattr(labels, "device", None)}, {getattr(labels, "dtype", None)}); '
-                        f'the HIP path has no CPU fallback')
-    if tuple(labels.shape) != (n,):
-        raise ValueError(f'{what}: labels must have shape ({n},), one per sample (got {tuple(labels.shape)})')
-    if labels.dtype != torch.int32:
-        labels = labels.to(torch.int32)
-    return labels if labels.is_contiguous() else labels.contiguous()
-
-
-def randint(n, high, seed, offset, device):
-    """``n`` int32 labels uniform in [0, high) from the Philox stream at (seed, offset); (n + 3) // 4 counters."""
-    out = torch.empty(int(n), dtype=torch.int32, device=device)
-    check(_lib.lib().ganlab_randint_i32(ctypes.c_void_p(out.data_ptr()), int(n), int(high),
-                                        int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), _st()), 'randint')
-    return out
-
-
-def _bn_batch_stats(x, running_mean, running_var, momentum, eps, batches):
-    """The batch statistics of ``x`` and BatchNorm's running-estimate / counter bookkeeping on ``batch_norm``'s own kernels
-    (3 launches), without an affine.  -> fin (4, C): mean, biased variance, rstd, rstd again (no weight to fold in here)."""
-    n, c, hw = _nchw(x)
-    m = n * hw
-    L = _lib.lib()
-    with torch.no_grad():
-        ws = _row_workspace(c, m, x.device)
-        mom = _new((c, 3), x)
-        check(L.ganlab_bn_stats_f32(_p(x), _p(mom), n, c, hw, ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, _st()),
-              'bn_stats')
-        fin = _new((4, c), x)
-        for buf in (running_mean, running_var, batches):
-            assert buf is None or (buf.is_contiguous() and buf.device == x.device)
-        assert batches is None or batches.dtype == torch.int64
-        check(L.ganlab_bn_finalize_f32(_p(mom), None, _p(running_mean) if running_mean is not None else None,
-                                       _p(running_var) if running_var is not None else None,
-                                       ctypes.c_void_p(batches.data_ptr()) if batches is not None else None, _p(fin), c,
-                                       float(eps), float(momentum), m / max(m - 1, 1), _st()), 'bn_finalize')
-    return fin
-
-
-class _CondBatchNorm(Function):
-    """Normalise with the given per-channel ``mean`` / ``rstd`` and apply the affine row of each sample's class (+ the
-    LeakyReLU behind it) in one pass.  ``batch_stats``: mean / rstd are the statistics of ``x`` itself (training mode) and the
-    backward carries their derivative; otherwise (eval mode) they are constants.  First order only, like ``_BatchNormTrain``:
-    the generator is never inside a gradient penalty.  Backward: 3 launches, the table gradients as ordinary tensors."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, labels, mean, rstd, act_slope, batch_stats):
-        n, c, hw = _nchw(x)
-        k = weight.shape[0]
-        y = torch.empty_like(x)
-        check(_lib.lib().ganlab_cbn_apply_f32(_p(x), _p(mean), _p(rstd), _p(weight), _p(bias), _p(labels), _p(y), n, c, hw, k,
-                                              ACT_LRELU if act_slope is not None else ACT_NONE,
-                                              float(act_slope) if act_slope is not None else 1.0, _st()), 'cbn_apply')
-        ctx.save_for_backward(x, weight, labels, mean, rstd, y if act_slope is not None else None)
-        ctx.act_slope, ctx.batch_stats = act_slope, bool(batch_stats)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, weight, labels, mean, rstd, yact = ctx.saved_tensors
-        gy = _c(gy)
-        n, c, hw = _nchw(x)
-        k = weight.shape[0]
-        L = _lib.lib()
-        ws = torch.empty((L.ganlab_cbn_bwd_workspace(n, c) + 7) // 8, dtype=torch.float64, device=x.device)
-        gz = torch.empty_like(gy) if yact is not None else None
-        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        gw, gb, sums = _new((k, c), x), _new((k, c), x), _new((c, 2), x)
-        check(L.ganlab_cbn_bwd_f32(_p(gy), _p(x), _p(mean), _p(rstd), _p(weight), _p(labels), _p(yact), _p(gz), _p(gx), _p(gw),
-                                   _p(gb), _p(sums), n, c, hw, k, int(ctx.batch_stats),
-                                   float(ctx.act_slope) if yact is not None else 1.0, ctypes.c_void_p(ws.data_ptr()),
-                                   ws.numel() * 8, _st()), 'cbn_bwd')
-        want_p = _want_param_grads()
-        return (gx, gw if (want_p and ctx.needs_input_grad[1]) else None, gb if (want_p and ctx.needs_input_grad[2]) else None,
-                None, None, None, None, None)
-
-
-def cond_batch_norm(x, weight, bias, labels, running_mean, running_var, training, momentum=0.1, eps=1e-5, batches=None,
-                    act_slope=None):
-    """Class-conditional BatchNorm: ``batch_norm`` whose affine is row ``labels[n]`` of the (K, C) tables ``weight`` / ``bias``
-    for sample n.  Training mode: batch statistics and the running-estimate / counter bookkeeping on ``batch_norm``'s own
-    kernels (3 launches), then one apply pass; eval mode: the same apply pass with the running statistics."""
-    x, weight, bias = _c(x, 'cond_batch_norm input'), _c(weight, 'cond_batch_norm weight'), _c(bias, 'cond_batch_norm bias')
-    n, c, hw = _nchw(x)
-    labels = _labels(labels, n, 'cond_batch_norm')
-    if weight.dim() != 2 or weight.shape[1] != c or bias.shape != weight.shape:
-        raise ValueError(f'cond_batch_norm: weight / bias must be (num_classes, {c}) tables (got {tuple(weight.shape)}, '
-                         f'{tuple(bias.shape)})')
-    slope = None if act_slope is None else float(act_slope)
-    if not training:
-        mean, rstd = _c(running_mean), torch.rsqrt(running_var + eps)
-        return _CondBatchNorm.apply(x, weight, bias, labels, mean, rstd, slope, False)
-    fin = _bn_batch_stats(x, running_mean, running_var, momentum, eps, batches)
-    return _CondBatchNorm.apply(x, weight, bias, labels, fin[0], fin[2], slope, True)
-
-
-# ---------------------------------------------------------------------------------------------- #
-# hierarchical latents + shared class embedding (csrc/hier.hip; hier_latent.py): the batched modulation, the modulated BatchNorm
-# ---------------------------------------------------------------------------------------------- #
-def _slot_open(p):
-    """May this step's first gradient of parameter ``p`` be written straight into its arena slot (``_sink``'s rule)?"""
-    arena = getattr(p, '_ganlab_arena', None)
-    return _DIRECT[0] and not torch.is_grad_enabled() and arena is not None and p.is_leaf and p.grad is not None and \
-        getattr(p, '_ganlab_written', -1) != arena.serial
-
-
-class HierTable(object):
-    """Device-resident job table of ``ganlab_hier_fwd_f32`` / ``ganlab_hier_bwd_f32``.  ``jobs``: one dict per modulation linear,
-    in column order, with ``w`` (the (C, D) float32 GPU parameter, contiguous), ``z_off`` / ``z_len`` (its chunk of the latent;
-    D = z_len + embed), ``scale`` and ``one`` (1 for a gain, 0 for a shift).  ``shared``: the (num_classes, embed) embedding
-    parameter or None.  Job j owns columns [cols[j], cols[j] + C_j) of the (N, T) buffer.  A weight that lives in an arena
-    (``optim.ParamArena``) gets its gradient written into its arena slot inside ``direct_param_grads``; otherwise, and for every
-    later use in the same step, the gradients come back as ordinary tensors from the table's own buffer.  Built and uploaded
-    once (outside any capture); keeps the tensors it points at alive."""
-
-    def __init__(self, jobs, len_latent, shared=None):
-        if not jobs:
-            raise ValueError('HierTable: no jobs')
-        self.weights = [d['w'] for d in jobs]
-        self.shared = shared
-        dev = self.weights[0].device
-        self.len_latent = int(len_latent)
-        self.embed = int(shared.shape[1]) if shared is not None else 0
-        self.num_classes = int(shared.shape[0]) if shared is not None else 0
-        if shared is not None:
-            _c(shared, 'HierTable shared')
-            if shared.dim() != 2 or not shared.is_contiguous() or shared.device != dev:
-                raise ValueError(f'HierTable: shared must be a contiguous (num_classes, E) tensor on {dev}')
-        self.cols, self.widths, self.own_offsets = [], [], []
-        col = own = bf = bw = 0
-        arr = (_lib.HierJob * len(jobs))()
-        for j, d in zip(arr, jobs):
-            w, z_off, z_len = d['w'], int(d['z_off']), int(d['z_len'])
-            _c(w, 'HierTable w')
-            D = z_len + self.embed
-            if w.dim() != 2 or w.shape[0] < 1 or w.shape[1] != D or D < 1 or not w.is_contiguous() or w.device != dev:
-                raise ValueError(f'HierTable: w must be a contiguous (C, {D}) tensor on {dev} (got {tuple(w.shape)})')
-            if z_len < 0 or z_off < 0 or z_off + z_len > self.len_latent:
-                raise ValueError(f'HierTable: chunk [{z_off}, {z_off + z_len}) leaves the latent [0, {self.len_latent})')
-            C = int(w.shape[0])
-            self.cols.append(col)
-            self.widths.append(C)
-            self.own_offsets.append(own)
-            j.C, j.z_off, j.z_len, j.col, j.scale, j.one = C, z_off, z_len, col, float(d['scale']), float(d['one'])
-            j.blk_f0, j.blk_w0 = bf, bw
-            col += C
-            own += (C * D + 3) // 4 * 4
-            bf += (C + 63) // 64
-            bw += (C * D + 255) // 256
-        self.T, self.blocks = col, (bf, bw)
-        self.gw_own = torch.zeros(own, dtype=torch.float32, device=dev)
-        self.in_arena = all(getattr(w, '_ganlab_arena', None) is not None and w.grad is not None and
-                            w.grad.is_contiguous() for w in self.weights)
-        for j, w, o in zip(arr, self.weights, self.own_offsets):
-            j.w = w.data_ptr()
-            j.gw = w.grad.data_ptr() if self.in_arena else None
-            j.gw_own = self.gw_own.data_ptr() + 4 * o
-        self.n = len(jobs)
-        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        self.pointers = self._pointers()
-        self._grad = {}
-
-    def _pointers(self):
-        ts = self.weights + ([self.shared] if self.shared is not None else [])
-        return tuple(t.data_ptr() for t in ts) + tuple(t.grad.data_ptr() if t.grad is not None else 0 for t in self.weights)
-
-    def is_current(self):
-        """Do the parameters still lie where the uploaded table points?"""
-        return self.pointers == self._pointers()
-
-    def grad_buffer(self, n):
-        """The (n, T) gradient buffer that ``mod_batch_norm`` writes d gain / d shift into and ``hier_modulate``'s backward reads."""
-        g = self._grad.get(n)
-        if g is None:
-            g = self._grad[n] = torch.zeros(n, self.T, dtype=torch.float32, device=self.table.device)
-        return g
-
-
-class _HierModulate(Function):
-    """out (N, T) = every gain (1 + s <W, cond>) and shift (s <W, cond>) of ``table`` in one launch.  Backward (first order, at
-    most 3 launches): the incoming gradient, or - when every consumer wrote its columns into ``table.grad_buffer(N)`` and handed
-    back None - that buffer."""
-
-    @staticmethod
-    def forward(ctx, table, z, shared, labels, *weights):
-        n = z.shape[0]
-        out = _new((n, table.T), z)
-        bf, _ = table.blocks
-        check(_lib.lib().ganlab_hier_fwd_f32(table.table.data_ptr(), table.n, bf, _p(z), _p(shared), _p(labels), _p(out), n,
-                                             table.T, table.len_latent, table.embed, max(table.num_classes, 1), _st()),
-              'hier_fwd')
-        ctx.table = table
-        ctx.save_for_backward(z, shared, labels)
-        ctx.set_materialize_grads(False)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        table = ctx.table
-        z, shared, labels = ctx.saved_tensors
-        n = z.shape[0]
-        g = table.grad_buffer(n) if g is None else _c(g)
-        want_w = _want_param_grads() and any(ctx.needs_input_grad[4:])
-        direct = want_w and table.in_arena and all(_slot_open(w) for w in table.weights)
-        dz = _new(z.shape, z) if ctx.needs_input_grad[1] else None
-        dshared = de = None
-        shared_direct = False
-        if shared is not None and ctx.needs_input_grad[2] and _want_param_grads():
-            de = _new((n, table.embed), z)
-            shared_direct = _slot_open(shared) and shared.grad.is_contiguous()
-            dshared = shared.grad if shared_direct else _new(shared.shape, z)
-        _, bw = table.blocks
-        check(_lib.lib().ganlab_hier_bwd_f32(table.table.data_ptr(), table.n, bw, _p(g), _p(z), _p(shared), _p(labels), _p(dz),
-                                             _p(de), _p(dshared), n, table.T, table.len_latent, table.embed,
-                                             max(table.num_classes, 1), 0 if direct else 1, _st()), 'hier_bwd')
-        if direct:
-            for w in table.weights:
-                w._ganlab_written = w._ganlab_arena.serial
-            gws = [None] * table.n
-        elif want_w:
-            own = table.gw_own.clone()
-            gws = [own[o:o + w.numel()].view(w.shape) if need else None
-                   for o, w, need in zip(table.own_offsets, table.weights, ctx.needs_input_grad[4:])]
-        else:
-            gws = [None] * table.n
-        if shared_direct:
-            shared._ganlab_written = shared._ganlab_arena.serial
-            dshared = None
-        return (None, dz, dshared, None) + tuple(gws)
-
-
-def hier_modulate(table, z, labels=None):
-    """The flat (N, T) modulation buffer of ``table`` (a ``HierTable``) for the latents ``z`` (N, len_latent) and, with a shared
-    embedding, the int32 device ``labels`` (N,): column ``table.cols[j] + c`` holds ``one_j + s_j <W_j[c], cond_j[n]>``.
-    Differentiable once towards ``z``, the embedding and every weight."""
-    z = _c(z, 'hier_modulate z')
-    if z.dim() != 2 or z.shape[1] != table.len_latent or z.shape[0] < 1:
-        raise ValueError(f'hier_modulate: z must be (N, {table.len_latent}) (got {tuple(z.shape)})')
-    if not table.is_current():
-        raise RuntimeError('hier_modulate: the parameters moved since the job table was uploaded; rebuild the table')
-    if table.shared is not None:
-        if labels is None:
-            raise TypeError('hier_modulate: the table has a shared class embedding: labels are required')
-        labels = _labels(labels, z.shape[0], 'hier_modulate')
-    else:
-        labels = None
-    return _HierModulate.apply(table, z, table.shared, labels, *table.weights)
-
-
-class _ModBatchNorm(Function):
-    """Normalise with the given per-channel ``mean`` / ``rstd`` and apply each sample's own gain / shift row (+ the LeakyReLU
-    behind it) in one pass.  The rows are columns [gcol, gcol + C) / [scol, scol + C) of ``gsrc`` / ``ssrc``.  With ``sink`` (the
-    (N, T) gradient buffer of a ``HierTable``) the backward writes d gain / d shift into the same columns of it and returns None
-    towards ``token`` (the modulation buffer these rows were cut from, which keeps its backward behind this one); without, it
-    returns them as tensors.  First order only, like ``_CondBatchNorm``."""
-
-    @staticmethod
-    def forward(ctx, x, gsrc, ssrc, token, gcol, scol, mean, rstd, act_slope, batch_stats, sink):
-        n, c, hw = _nchw(x)
-        y = torch.empty_like(x)
-        gs, ss = gsrc.stride(0), ssrc.stride(0)
-        check(_lib.lib().ganlab_mbn_apply_f32(_p(x), _p(mean), _p(rstd), ctypes.c_void_p(gsrc.data_ptr() + 4 * gcol), gs,
-                                              ctypes.c_void_p(ssrc.data_ptr() + 4 * scol), ss, _p(y), n, c, hw,
-                                              ACT_LRELU if act_slope is not None else ACT_NONE,
-                                              float(act_slope) if act_slope is not None else 1.0, _st()), 'mbn_apply')
-        ctx.save_for_backward(x, gsrc, mean, rstd, y if act_slope is not None else None)
-        ctx.act_slope, ctx.batch_stats, ctx.sink, ctx.cols = act_slope, bool(batch_stats), sink, (gcol, scol)
-        ctx.set_materialize_grads(False)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, gsrc, mean, rstd, yact = ctx.saved_tensors
-        if gy is None:
-            return (None,) * 11
-        gy = _c(gy)
-        n, c, hw = _nchw(x)
-        gcol, scol = ctx.cols
-        L = _lib.lib()
-        ws = torch.empty((L.ganlab_mbn_bwd_workspace(n, c) + 7) // 8, dtype=torch.float64, device=x.device)
-        gz = torch.empty_like(gy) if yact is not None else None
-        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        sums = _new((c, 2), x)
-        sink = ctx.sink
-        dg = ds = None
-        if sink is not None:
-            pg, ps, stride = sink.data_ptr() + 4 * gcol, sink.data_ptr() + 4 * scol, sink.stride(0)
-        elif ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dg, ds = _new((n, c), x), _new((n, c), x)
-            pg, ps, stride = dg.data_ptr(), ds.data_ptr(), c
-        else:
-            pg = ps = None
-            stride = c
-        check(L.ganlab_mbn_bwd_f32(_p(gy), _p(x), _p(mean), _p(rstd), ctypes.c_void_p(gsrc.data_ptr() + 4 * gcol), gsrc.stride(0),
-                                   _p(yact), _p(gz), _p(gx), ctypes.c_void_p(pg) if pg else None,
-                                   ctypes.c_void_p(ps) if ps else None, stride, _p(sums), n, c, hw, int(ctx.batch_stats),
-                                   float(ctx.act_slope) if yact is not None else 1.0, ctypes.c_void_p(ws.data_ptr()),
-                                   ws.numel() * 8, _st()), 'mbn_bwd')
-        return (gx, dg if ctx.needs_input_grad[1] else None, ds if ctx.needs_input_grad[2] else None) + (None,) * 8
-
-
-def _mod_rows(t, n, c, what):
-    _c(t, what)
-    if t.dim() != 2 or tuple(t.shape) != (n, c) or (c > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < c):
-        raise ValueError(f'mod_batch_norm: {what} must be ({n}, {c}) with unit column stride - a contiguous tensor or a column '
-                         f'slice of an (N, T) buffer (got {tuple(t.shape)}, strides {tuple(t.stride())})')
-    return t
-
-
-def _mod_stats(x, running_mean, running_var, training, momentum, eps, batches):
-    if not training:
-        return _c(running_mean), torch.rsqrt(running_var + eps)
-    fin = _bn_batch_stats(x, running_mean, running_var, momentum, eps, batches)
-    return fin[0], fin[2]
-
-
-def mod_batch_norm(x, gain, shift, running_mean, running_var, training, momentum=0.1, eps=1e-5, batches=None,
-                   act_slope=None):
-    """Modulated BatchNorm: ``batch_norm`` whose affine is sample n's own row of the (N, C) tensors ``gain`` / ``shift`` -
-    contiguous, or column slices of one flat (N, T) buffer (row stride T), read where they lie.  Statistics, bookkeeping and
-    eval mode as ``cond_batch_norm``; equal rows reproduce ``batch_norm`` bit for bit.  First order."""
-    x = _c(x, 'mod_batch_norm input')
-    n, c, hw = _nchw(x)
-    gain, shift = _mod_rows(gain, n, c, 'gain'), _mod_rows(shift, n, c, 'shift')
-    slope = None if act_slope is None else float(act_slope)
-    mean, rstd = _mod_stats(x, running_mean, running_var, training, momentum, eps, batches)
-    # a 1-row view may report any row stride: the kernels never step over a row then
-    return _ModBatchNorm.apply(x, gain if n > 1 or gain.stride(0) >= c else gain.contiguous(),
-                               shift if n > 1 or shift.stride(0) >= c else shift.contiguous(), None, 0, 0, mean, rstd, slope,
-                               bool(training), None)
-
-
-def mod_batch_norm_cols(x, mod, flat, sink, gcol, scol, running_mean, running_var, training, momentum=0.1, eps=1e-5,
-                        batches=None, act_slope=None):
-    """``mod_batch_norm`` for the layers of a network: gain / shift are columns [gcol, gcol + C) / [scol, scol + C) of ``flat`` =
-    ``mod.detach()``, ``mod`` the output of ``hier_modulate``; d gain / d shift go straight into the same columns of ``sink`` =
-    ``table.grad_buffer(N)`` (None when ``mod`` carries no gradient) - no per-layer slice, zero-fill or add - and ``mod``'s backward
-    picks them up there."""
-    x = _c(x, 'mod_batch_norm input')
-    n, c, hw = _nchw(x)
-    if flat.dim() != 2 or flat.shape[0] != n or not flat.is_contiguous() or max(gcol, scol) + c > flat.shape[1] or \
-            min(gcol, scol) < 0 or (sink is not None and (sink.shape != flat.shape or not sink.is_contiguous())):
-        raise ValueError(f'mod_batch_norm_cols: columns [{gcol}, +{c}) / [{scol}, +{c}) do not fit the ({n}, T) buffers '
-                         f'(got {tuple(flat.shape)})')
-    slope = None if act_slope is None else float(act_slope)
-    mean, rstd = _mod_stats(x, running_mean, running_var, training, momentum, eps, batches)
-    return _ModBatchNorm.apply(x, flat, flat, mod, int(gcol), int(scol), mean, rstd, slope, bool(training),
-                               sink if mod.requires_grad else None)
-
-
-def _proj_dims(f, weight, what):
-    if f.dim() != 2 or weight.dim() != 2 or f.shape[1] != weight.shape[1]:
-        raise ValueError(f'{what}: features (N, F) and weight (K, F) do not fit (got {tuple(f.shape)}, {tuple(weight.shape)})')
-    return f.shape[0], f.shape[1], weight.shape[0]
-
-
-class _ClassProj(Function):
-    """P(f, W, l, base)[n] = base[n] + <W[l_n], f[n]>.  d/df = G(g, W, l), d/dW = S(g, f, l), d/dbase = g."""
-
-    @staticmethod
-    def forward(ctx, f, weight, labels, base):
-        f, weight = _c(f, 'class_projection features'), _c(weight, 'class_projection weight')
-        n, nf, k = _proj_dims(f, weight, 'class_projection')
-        base = _c(base, 'class_projection base').reshape(n) if base is not None else None
-        out = _new((n,), f)
-        check(_lib.lib().ganlab_proj_fwd_f32(_p(f), _p(weight), _p(labels), _p(base), _p(out), n, nf, k, _st()), 'proj_fwd')
-        ctx.save_for_backward(f, weight, labels)
-        ctx.has_base = base is not None
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        f, weight, labels = ctx.saved_tensors
-        gf = _ClassProjDfeat.apply(g, weight, labels) if ctx.needs_input_grad[0] else None
-        gw = _ClassProjDweight.apply(g, f, labels, weight.shape[0]) if (ctx.needs_input_grad[1] and _want_param_grads()) \
-            else None
-        return gf, gw, None, g if (ctx.has_base and ctx.needs_input_grad[3]) else None
-
-
-class _ClassProjDfeat(Function):
-    """G(g, W, l)[n,j] = g[n] W[l_n,j].  d/dg = P(cot, W, l, 0), d/dW = S(g, cot, l)."""
-
-    @staticmethod
-    def forward(ctx, g, weight, labels):
-        g, weight = _c(g), _c(weight)
-        k, nf = weight.shape
-        n = g.numel()
-        out = _new((n, nf), g)
-        check(_lib.lib().ganlab_proj_dfeat_f32(_p(g), _p(weight), _p(labels), _p(out), n, nf, k, _st()), 'proj_dfeat')
-        ctx.save_for_backward(g, weight, labels)
-        return out
-
-    @staticmethod
-    def backward(ctx, cot):
-        g, weight, labels = ctx.saved_tensors
-        gg = _ClassProj.apply(cot, weight, labels, None).view(g.shape) if ctx.needs_input_grad[0] else None
-        gw = _ClassProjDweight.apply(g, cot, labels, weight.shape[0]) if (ctx.needs_input_grad[1] and _want_param_grads()) \
-            else None
-        return gg, gw, None
-
-
-class _ClassProjDweight(Function):
-    """S(g, f, l)[k,j] = sum_{n: l_n = k} g[n] f[n,j].  d/dg = P(f, cot, l, 0), d/df = G(g, cot, l)."""
-
-    @staticmethod
-    def forward(ctx, g, f, labels, k):
-        g, f = _c(g), _c(f)
-        n, nf = f.shape
-        out = _new((k, nf), f)
-        check(_lib.lib().ganlab_proj_dweight_f32(_p(g), _p(f), _p(labels), _p(out), n, nf, k, _st()), 'proj_dweight')
-        ctx.save_for_backward(g, f, labels)
-        return out
-
-    @staticmethod
-    def backward(ctx, cot):
-        g, f, labels = ctx.saved_tensors
-        gg = _ClassProj.apply(f, cot, labels, None).view(g.shape) if ctx.needs_input_grad[0] else None
-        gf = _ClassProjDfeat.apply(g, cot, labels) if ctx.needs_input_grad[1] else None
-        return gg, gf, None, None
-
-
-def class_projection(f, weight, labels, base=None):
-    """The projection critic's output (Miyato & Koyama 2018): ``base[n] + <weight[labels[n]], f[n]>`` for features (N, F), a
-    (K, F) class embedding and the unconditional score ``base`` (N,) (None: 0).  Any order of differentiation."""
-    if not isinstance(f, torch.Tensor) or f.dim() != 2:
-        raise ValueError('class_projection: features must be an (N, F) tensor')
-    return _ClassProj.apply(f, weight, _labels(labels, f.shape[0], 'class_projection'), base)
-
-
-# ---------------------------------------------------------------------------------------------- #
-# consistency regularisation (csrc/cr.hip; consistency.py): the bCR image transform, the two mean squared differences
-# ---------------------------------------------------------------------------------------------- #
-def _cr_table(params, n, what):
-    """A transform table at the ops boundary: a contiguous (n, 4) int32 device tensor."""
-    if not isinstance(params, torch.Tensor) or not params.is_cuda or params.dtype != torch.int32:
-        raise TypeError(f'gan_lab_amd.ops: {what} params must be an int32 tensor on the GPU (got {type(params).__name__}, '
-                        f'{getattr(params, "device", None)}, {getattr(params, "dtype", None)}); the HIP path has no CPU fallback')
-    if tuple(params.shape) != (n, 4):
-        raise ValueError(f'{what}: params must have shape ({n}, 4), one (flip, dx, dy, 0) row per image (got '
-                         f'{tuple(params.shape)})')
-    return params if params.is_contiguous() else params.contiguous()
-
-
-def cr_params(n, shift, flip, seed, offset, device, base=None):
-    """(n, 4) int32 rows (flip, dx, dy, 0) of ``cr_transform`` from the Philox stream at ``offset`` (+ ``*base``: the step-scalar
-    block of graphs.GraphedStep), one counter per row: flip in {0, 1} (0 when ``flip`` is False), dx, dy uniform in
-    [-shift, shift]."""
-    _gpu_device(device, 'cr_params')
-    n, shift = int(n), int(shift)
-    if n < 1 or shift < 0:
-        raise ValueError(f'cr_params: needs n >= 1 and shift >= 0 (got {n}, {shift})')
-    out = torch.empty((n, 4), dtype=torch.int32, device=device)
-    check(_lib.lib().ganlab_cr_params_i32(ctypes.c_void_p(out.data_ptr()), n, shift, int(bool(flip)), int(seed) & (2 ** 64 - 1),
-                                          int(offset) & (2 ** 64 - 1), _p(base), _st()), 'cr_params')
-    return out
-
-
-def cr_transform(x, params):
-    """The bCR image transform: ``y[n,c,i,j] = x[n,c,i-dy, f(j-dx)]`` per row (flip, dx, dy, 0) of the (N, 4) int32 ``params``, f
-    the horizontal mirror when flip is set, zero where the source leaves the image.  Bit-exact; no gradient (every transformed
-    input of the critic step is detached)."""
-    x = _c(x, 'cr_transform input')
-    if x.dim() != 4:
-        raise ValueError(f'cr_transform: needs an (N, C, H, W) batch (got {tuple(x.shape)})')
-    if x.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError('cr_transform has no adjoint: detach its input (consistency regularisation transforms detached '
-                           'batches only)')
-    n, c, h, w = x.shape
-    params = _cr_table(params, n, 'cr_transform')
-    y = torch.empty_like(x)
-    check(_lib.lib().ganlab_cr_transform_f32(_p(x), ctypes.c_void_p(params.data_ptr()), _p(y), n, c, h, w, _st()),
-          'cr_transform')
-    return y
-
-
-class _FirstOrderOnly(Function):
-    """The gradients a first-order-only backward computed, tied to the op's inputs so that differentiating them - a second
-    differentiation of the op - raises by the op's name instead of returning a silently wrong (or missing) second derivative."""
-
-    @staticmethod
-    def forward(ctx, name, n_inputs, *tensors):
-        ctx.name = name
-        return tuple(t.view_as(t) for t in tensors[n_inputs:])
-
-    @staticmethod
-    def backward(ctx, *gg):
-        raise RuntimeError(f'gan_lab_amd.ops.{ctx.name} is first order only: its backward was asked to differentiate twice (no '
-                           f'double backward is provided; keep it out of create_graph=True penalties)')
-
-
-def _first_order(name, inputs, grads):
-    """``grads`` as they are, or - while autograd is recording the backward (create_graph=True) - guarded by ``_FirstOrderOnly``."""
-    if not torch.is_grad_enabled():
-        return grads
-    return _FirstOrderOnly.apply(name, len(inputs), *inputs, *grads)
-
-
-class _CrMsd(Function):
-    """mean_n (a_n - b_n)^2 of two score vectors -> 0-dim tensor; first order only."""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        out = _new((), a)
-        check(_lib.lib().ganlab_cr_msd_fwd_f32(_p(a), _p(b), _p(out), a.numel(), _st()), 'cr_msd_fwd')
-        ctx.save_for_backward(a, b)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        a, b = ctx.saved_tensors
-        ga, gb = torch.empty_like(a), torch.empty_like(b)
-        g1 = _c(gout.detach()).reshape(1)
-        check(_lib.lib().ganlab_cr_msd_bwd_f32(_p(a), _p(b), _p(g1), _p(ga), _p(gb), a.numel(), _st()), 'cr_msd_bwd')
-        return _first_order('cr_msd', (a, b, gout), (ga, gb))
-
-
-def _cr_imsd_fwd(a, b, n):
-    L = _lib.lib()
-    ws = torch.empty((L.ganlab_cr_imsd_workspace(n) + 7) // 8, dtype=torch.float64, device=a.device)
-    out = _new((), a)
-    check(L.ganlab_cr_imsd_fwd_f32(_p(a), _p(b), _p(out), n, _p(ws), ws.numel() * 8, _st()), 'cr_imsd_fwd')
-    return out
-
-
-class _CrImsd(Function):
-    """Mean over every element of (a - b)^2 for two image batches -> 0-dim tensor; first order only."""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        ctx.save_for_backward(a, b)
-        return _cr_imsd_fwd(a, b, a.numel())
-
-    @staticmethod
-    def backward(ctx, gout):
-        a, b = ctx.saved_tensors
-        ga, gb = torch.empty_like(a), torch.empty_like(b)
-        g1 = _c(gout.detach()).reshape(1)
-        check(_lib.lib().ganlab_cr_imsd_bwd_f32(_p(a), _p(b), _p(g1), _p(ga), _p(gb), a.numel(), _st()), 'cr_imsd_bwd')
-        return _first_order('cr_imsd', (a, b, gout), (ga, gb))
-
-
-class _CrImsdHalves(Function):
-    """``_CrImsd`` of the two halves of one contiguous (2N, ...) tensor: the backward writes both gradients into the halves of ONE
-    gradient tensor, so the producer's backward starts from a single (2N, ...) cotangent."""
-
-    @staticmethod
-    def forward(ctx, both):
-        ctx.save_for_backward(both)
-        half = both.numel() // 2
-        flat = both.view(-1)
-        return _cr_imsd_fwd(flat[:half], flat[half:], half)
-
-    @staticmethod
-    def backward(ctx, gout):
-        both, = ctx.saved_tensors
-        half = both.numel() // 2
-        flat, g = both.detach().view(-1), torch.empty_like(both)
-        gflat = g.view(-1)
-        g1 = _c(gout.detach()).reshape(1)
-        check(_lib.lib().ganlab_cr_imsd_bwd_f32(_p(flat[:half]), _p(flat[half:]), _p(g1), _p(gflat[:half]), _p(gflat[half:]), half,
-                                                _st()), 'cr_imsd_bwd')
-        return _first_order('cr_imsd', (both, gout), (g,))[0]
-
-
-def cr_msd(a, b):
-    """Mean over the batch of the squared difference of two critic score vectors, (N,) or (N, 1): fp32 differences squared in
-    fp32, summed in fp64 in a fixed order (bitwise reproducible).  Differentiable ONCE in both; a second differentiation raises."""
-    a, b = _c(a, 'cr_msd a'), _c(b, 'cr_msd b')
-    for t in (a, b):
-        if not (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 1)) or t.numel() < 1:
-            raise ValueError(f'cr_msd: scores must be (N,) or (N, 1) with N >= 1 (got {tuple(a.shape)} and {tuple(b.shape)})')
-    if a.numel() != b.numel() or a.device != b.device:
-        raise ValueError(f'cr_msd: the two score vectors differ ({tuple(a.shape)} on {a.device}, {tuple(b.shape)} on {b.device})')
-    return _CrMsd.apply(a, b)
-
-
-def cr_imsd(a, b=None):
-    """Mean over all N*C*H*W elements of the squared difference of two equal-shaped image batches (fp64 partials per workgroup,
-    summed in a fixed order: bitwise reproducible).  ``b=None``: ``a`` is one contiguous (2N, ...) tensor and its two halves are
-    compared - the gradient then is ONE (2N, ...) tensor written in a single launch.  Differentiable ONCE; a second
-    differentiation raises."""
-    if b is None:
-        a = _c(a, 'cr_imsd input')
-        if a.dim() < 1 or a.shape[0] < 2 or a.shape[0] % 2:
-            raise ValueError(f'cr_imsd: one tensor must hold two halves along its first axis (got {tuple(a.shape)})')
-        return _CrImsdHalves.apply(a)
-    a, b = _c(a, 'cr_imsd a'), _c(b, 'cr_imsd b')
-    if a.shape != b.shape or a.device != b.device or a.numel() < 1:
-        raise ValueError(f'cr_imsd: the two batches differ ({tuple(a.shape)} on {a.device}, {tuple(b.shape)} on {b.device})')
-    return _CrImsd.apply(a, b)
-
-
-# ---------------------------------------------------------------------------------------------- #
-# classifier-based class conditioning (csrc/cond_loss.hip; conditional.py): AC-GAN's cross-entropy, ContraGAN's 2C, ReACGAN's D2D-CE
-# ---------------------------------------------------------------------------------------------- #
-CL_MODES = {'2c': 0, 'd2d': 1}
-CL_MAX_N, CL_MAX_E, CL_MAX_K = 8192, 1024, 65536
-
-
-def _cl_range(what, n, k, e=None):
-    if not 1 <= n <= CL_MAX_N or not 2 <= k <= CL_MAX_K or (e is not None and not 1 <= e <= CL_MAX_E):
-        raise ValueError(f'{what}: supported are 1 <= N <= {CL_MAX_N}, 2 <= K <= {CL_MAX_K}' +
-                         (f', 1 <= E <= {CL_MAX_E} (got N = {n}, E = {e}, K = {k})' if e is not None else f' (got N = {n}, K = {k})'))
-
-
-class _ClassCrossEntropy(Function):
-    """mean_i (LSE_k z_ik - z[i, y_i]) -> 0-dim tensor; first order only."""
-
-    @staticmethod
-    def forward(ctx, z, labels):
-        n, k = z.shape
-        out, lse = _new((), z), _new((n,), z)
-        check(_lib.lib().ganlab_class_ce_fwd_f32(_p(z), _p(labels), _p(out), _p(lse), n, k, _st()), 'class_ce_fwd')
-        ctx.save_for_backward(z, labels, lse)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        z, labels, lse = ctx.saved_tensors
-        n, k = z.shape
-        dz = torch.empty_like(z)
-        g1 = _c(gout.detach()).reshape(1)
-        check(_lib.lib().ganlab_class_ce_bwd_f32(_p(z), _p(labels), _p(lse), _p(g1), _p(dz), n, k, _st()), 'class_ce_bwd')
-        return _first_order('class_cross_entropy', (z, gout), (dz,))[0], None
-
-
-class _ClassContrastive(Function):
-    """The 2C / D2D-CE mean over rows -> (0-dim loss, (4, N) rows = l, D, M, s); first order only."""
-
-    @staticmethod
-    def forward(ctx, h, proxy, labels, mode, tau, mp, mn):
-        n, e = h.shape
-        k = proxy.shape[0]
-        out, rows = _new((), h), _new((4, n), h)
-        check(_lib.lib().ganlab_cl_fwd_f32(_p(h), _p(proxy), _p(labels), _p(out), _p(rows), n, e, k, mode, tau, mp, mn, _st()),
-              'cl_fwd')
-        ctx.save_for_backward(h, proxy, labels, rows)
-        ctx.params = (mode, tau, mp, mn)
-        ctx.mark_non_differentiable(rows)
-        return out, rows
-
-    @staticmethod
-    def backward(ctx, gout, _grows):
-        h, proxy, labels, rows = ctx.saved_tensors
-        n, e = h.shape
-        k = proxy.shape[0]
-        L = _lib.lib()
-        dh, dp = torch.empty_like(h), torch.empty_like(proxy)
-        ws = _new(((L.ganlab_cl_bwd_workspace(n, e, k) + 3) // 4,), h)
-        g1 = _c(gout.detach()).reshape(1)
-        check(L.ganlab_cl_bwd_f32(_p(h), _p(proxy), _p(labels), _p(rows), _p(g1), _p(dh), _p(dp), n, e, k, *ctx.params, _p(ws),
-                                  ws.numel() * 4, _st()), 'cl_bwd')
-        dh, dp = _first_order('class_contrastive', (h, proxy, gout), (dh, dp))
-        return dh, dp if _want_param_grads() else None, None, None, None, None, None
-
-
-def class_cross_entropy(logits, labels):
-    """AC-GAN's auxiliary classification loss (Odena et al. 2017): the mean over the N rows of ``logsumexp(logits[i]) -
-    logits[i, labels[i]]`` for (N, K) logits, as a 0-dim device tensor; one launch forward, one backward, a fixed summation order
-    (bitwise reproducible).  Differentiable ONCE; a second differentiation raises."""
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
-        raise ValueError('class_cross_entropy: logits must be an (N, K) tensor')
-    z = _c(logits, 'class_cross_entropy logits')
-    _cl_range('class_cross_entropy', z.shape[0], z.shape[1])
-    return _ClassCrossEntropy.apply(z, _labels(labels, z.shape[0], 'class_cross_entropy'))
-
-
-def class_contrastive(h, proxy_weight, labels, mode='2c', temperature=1.0, margin_pos=0.98, margin_neg=0.02, return_rows=False):
-    """ContraGAN's conditional contrastive loss (``mode='2c'``; Kang & Park 2020) or ReACGAN's data-to-data cross-entropy
-    (``mode='d2d'``; Kang et al. 2021) of (N, E) embeddings ``h`` and the (K, E) class proxies ``proxy_weight``, both normalised
-    to unit rows inside: the mean over rows as a 0-dim device tensor (csrc/cond_loss.hip: the N x N similarities are formed tile
-    by tile on the exact-fp32 MFMA and never stored; 2 launches forward, 3 backward, bitwise reproducible).  The margins are
-    D2D-CE's.  ``return_rows``: also the (N,) per-row losses (detached).  Differentiable ONCE in ``h`` and ``proxy_weight``."""
-    if not isinstance(h, torch.Tensor) or h.dim() != 2 or not isinstance(proxy_weight, torch.Tensor) or proxy_weight.dim() != 2 \
-            or h.shape[1] != proxy_weight.shape[1]:
-        raise ValueError(f'class_contrastive: embeddings (N, E) and proxies (K, E) do not fit (got '
-                         f'{tuple(getattr(h, "shape", ()))}, {tuple(getattr(proxy_weight, "shape", ()))})')
-    if mode not in CL_MODES:
-        raise ValueError(f"class_contrastive: mode must be '2c' or 'd2d' (got {mode!r})")
-    tau, mp, mn = float(temperature), float(margin_pos), float(margin_neg)
-    if not (tau > 0 and np.isfinite(tau) and np.isfinite(mp) and np.isfinite(mn)):
-        raise ValueError(f'class_contrastive: needs a finite temperature > 0 and finite margins (got {tau}, {mp}, {mn})')
-    h, proxy_weight = _c(h, 'class_contrastive embeddings'), _c(proxy_weight, 'class_contrastive proxies')
-    _cl_range('class_contrastive', h.shape[0], proxy_weight.shape[0], h.shape[1])
-    loss, rows = _ClassContrastive.apply(h, proxy_weight, _labels(labels, h.shape[0], 'class_contrastive'), CL_MODES[mode], tau,
-                                         mp, mn)
-    return (loss, rows[0]) if return_rows else loss
-
-
-# ---------------------------------------------------------------------------------------------- #
-# projection into StyleGAN's latent space (csrc/project.hip; project.py): the multi-scale reconstruction loss, the moments of W,
-# the latent update
-# ---------------------------------------------------------------------------------------------- #
-PYRAMID_MAX_LEVELS = 6                               # GANLAB_PYRAMID_MAX_LEVELS (include/ganlab_hip.h)
-PROJECT_SCHEDULE = {'lr0': 0.1, 'initial_noise_factor': 0.05, 'lr_rampdown_length': 0.25, 'lr_rampup_length': 0.05,
-                    'noise_ramp_length': 0.75}       # the StyleGAN2 projector's defaults
-
-
-def pyramid_max_levels(res):
-    """Levels ``pyramid_mse`` allows at resolution ``res``: min(6, log2(res) + 1); ValueError unless ``res`` is a power of two in
-    [4, 1024]."""
-    if isinstance(res, bool) or not isinstance(res, (int, np.integer)) or not 4 <= res <= 1024 or res & (res - 1):
-        raise ValueError(f'pyramid_mse: the resolution must be a power of two in [4, 1024] (got {res!r})')
-    return min(PYRAMID_MAX_LEVELS, int(res).bit_length())
-
-
-def check_pyramid_weights(weights, res, what='weights'):
-    """``weights`` of ``pyramid_mse`` at resolution ``res`` as a tuple of floats: 1 to ``pyramid_max_levels(res)`` finite
-    non-negative numbers, else a ValueError that names ``what``."""
-    top = pyramid_max_levels(res)
-    try:
-        w = tuple(float(v) for v in weights)
-    except (TypeError, ValueError):
-        raise ValueError(f'{what} must be a sequence of non-negative numbers (got {weights!r})') from None
-    if not 1 <= len(w) <= top:
-        raise ValueError(f'{what} must hold 1 to {top} values at {res}x{res}, one per pyramid level (got {len(w)})')
-    if any(isinstance(v, bool) for v in weights) or not all(0.0 <= v <= 3.0e38 for v in w):
-        raise ValueError(f'{what} must be finite and non-negative (got {weights!r})')
-    return w
-
-
-def _aligned16(t):
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
-class _PyramidMse(Function):
-    """(loss (N,), terms (N, Lv)) of x against t; the gradient in x is formed by the forward's launch and saved.  First order only,
-    no gradient for t."""
-
-    @staticmethod
-    def forward(ctx, x, t, weights):
-        L = _lib.lib()
-        n, c, r, _ = x.shape
-        lv = len(weights)
-        ws = torch.empty((L.ganlab_pyramid_mse_workspace(n, c, r, lv) + 7) // 8, dtype=torch.float64, device=x.device)
-        g, loss, terms = torch.empty_like(x), _new((n,), x), _new((n, lv), x)
-        host_w = (ctypes.c_float * lv)(*weights)
-        check(L.ganlab_pyramid_mse_f32(_p(x), _p(t), ctypes.cast(host_w, ctypes.c_void_p), lv, _p(g), _p(loss), _p(terms), n, c, r,
-                                       _p(ws), ws.numel() * 8, _st()), 'pyramid_mse')
-        ctx.save_for_backward(x, g)
-        ctx.mark_non_differentiable(terms)
-        return loss, terms
-
-    @staticmethod
-    def backward(ctx, gloss, _gterms):
-        x, g = ctx.saved_tensors
-        s = _c(gloss.detach(), 'pyramid_mse cotangent')
-        gx = torch.empty_like(g)
-        check(_lib.lib().ganlab_scale_rows_f32(_p(g), _p(s), _p(gx), g.shape[0], g[0].numel(), _st()), 'pyramid_mse_bwd')
-        return _first_order('pyramid_mse', (x, gloss), (gx,))[0], None, None
-
-
-def pyramid_mse(x, t, weights):
-    """Multi-scale mean squared error of two (N, C, R, R) batches, R a power of two in [4, 1024]: with ``d_0 = x - t`` and
-    ``d_{l+1}`` the 2x2 mean of ``d_l``, ``loss[n] = sum_l weights[l] * mean_{c,h,w} d_l[n]^2`` over ``len(weights)`` levels (at
-    most ``pyramid_max_levels(R)``).  Returns ``(loss (N,), terms (N, Lv))``, ``terms[n, l]`` the unweighted level means
-    (detached).  One launch reads x and t once, forms every level inside 32x32 tiles in LDS, sums the squares in fp64 and writes
-    the gradient; a second adds the per-tile partials in a fixed order (csrc/project.hip; no atomics, bitwise reproducible).
-    Differentiable ONCE in ``x`` (a second differentiation raises), not in ``t``."""
-    x, t = _c(x, 'pyramid_mse x'), _c(t, 'pyramid_mse t')
-    if x.dim() != 4 or x.shape[2] != x.shape[3] or x.shape != t.shape or x.device != t.device or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f'pyramid_mse: needs two equal (N, C, R, R) batches (got {tuple(x.shape)} on {x.device}, '
-                         f'{tuple(t.shape)} on {t.device})')
-    if t.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError('pyramid_mse has no gradient for its target: detach it')
-    weights = check_pyramid_weights(weights, int(x.shape[2]), 'pyramid_mse: weights')
-    return _PyramidMse.apply(_aligned16(x), _aligned16(t), weights)
-
-
-def w_moments(ws):
-    """``(w_avg (D,), w_std 0-dim)`` of (M, D) dlatent rows as the StyleGAN2 projector defines them: the column means and
-    ``sqrt(sum (w - w_avg)^2 / M)`` over all entries; two passes, fp64, a fixed summation order; device tensors, no gradient."""
-    ws = _c(ws, 'w_moments rows').detach()
-    if ws.dim() != 2 or ws.shape[0] < 1 or ws.shape[1] < 1:
-        raise ValueError(f'w_moments: needs (M, D) rows with M, D >= 1 (got {tuple(ws.shape)})')
-    L = _lib.lib()
-    m, d = ws.shape
-    work = torch.empty((L.ganlab_w_moments_workspace(d) + 7) // 8, dtype=torch.float64, device=ws.device)
-    w_avg, w_std = _new((d,), ws), _new((), ws)
-    check(L.ganlab_w_moments_f32(_p(ws), _p(w_avg), _p(w_std), m, d, _p(work), work.numel() * 8, _st()), 'w_moments')
-    return w_avg, w_std
-
-
-def check_project_schedule(num_steps, schedule, what='project_step'):
-    """The six doubles ``project_step`` takes - (lr0, initial_noise_factor, lr_rampdown_length, lr_rampup_length,
-    noise_ramp_length, num_steps) - from ``num_steps`` and a dict over ``PROJECT_SCHEDULE``'s keys (missing: the default).
-    ValueError naming the key: an unknown one, lr0 or initial_noise_factor not finite and >= 0, a length outside (0, 1]."""
-    unknown = sorted(set(schedule) - set(PROJECT_SCHEDULE))
-    if unknown:
-        raise ValueError(f'{what}: unknown schedule value {unknown[0]!r} (known: {", ".join(PROJECT_SCHEDULE)})')
-    if isinstance(num_steps, bool) or not isinstance(num_steps, (int, np.integer)) or not 1 <= num_steps < 2 ** 31:
-        raise ValueError(f'{what}: steps must be an integer >= 1 (got {num_steps!r})')
-    out = []
-    for key, default in PROJECT_SCHEDULE.items():
-        raw = schedule.get(key, default)
-        try:
-            val = float(raw)
-        except (TypeError, ValueError):
-            val = float('nan')
-        lo_ok = val >= 0.0 if key in ('lr0', 'initial_noise_factor') else 0.0 < val <= 1.0
-        if isinstance(raw, bool) or not (lo_ok and val < float('inf')):
-            rng_txt = 'finite and >= 0' if key in ('lr0', 'initial_noise_factor') else 'in (0, 1]'
-            raise ValueError(f'{what}: {key} must be {rng_txt} (got {raw!r})')
-        out.append(val)
-    return tuple(out) + (float(num_steps),)
-
-
-def project_step(w_opt, grad_ws, m, v, step, noise, w_std, w_in, hyper):
-    """One update of the projected dlatents in ONE launch (csrc/project.hip).  ``step``: 1-element int32 device tensor, the
-    iteration count k.  W+ space: ``w_opt``, ``m``, ``v``, ``noise`` are (N, L, D) like ``grad_ws`` and ``w_in``; W space: they
-    are (N, D), the gradient is ``grad_ws`` summed over L in layer order and ``w_in`` is broadcast over L.  Adam's update k + 1
-    (betas 0.9 / 0.999, eps 1e-8, bias-corrected) with the learning rate of the StyleGAN2 projector's schedule at
-    ``t = k / num_steps``, then ``step = k + 1`` and ``w_in = w_opt + scale((k + 1) / num_steps) * noise`` - the next forward's
-    input.  ``grad_ws=None``: no update, ``w_in`` at the current count (the first forward's input).  ``hyper``:
-    ``check_project_schedule``'s tuple.  Everything is updated in place; nothing is read back by the host."""
-    w_in = _inplace(w_in, 'project_step w_in')
-    if w_in.dim() != 3:
-        raise ValueError(f'project_step: w_in must be (N, L, D) (got {tuple(w_in.shape)})')
-    n, l, d = w_in.shape
-    if w_opt.dim() not in (2, 3) or tuple(w_opt.shape) not in ((n, d), (n, l, d)):
-        raise ValueError(f'project_step: w_opt must be ({n}, {d}) (W) or ({n}, {l}, {d}) (W+) (got {tuple(w_opt.shape)})')
-    w_plus = w_opt.dim() == 3
-    for name, t in (('w_opt', w_opt), ('m', m), ('v', v), ('noise', noise)):
-        _inplace(t, f'project_step {name}')
-        if t.shape != w_opt.shape:
-            raise ValueError(f'project_step: {name} must have the shape of w_opt, {tuple(w_opt.shape)} (got {tuple(t.shape)})')
-    if grad_ws is not None:
-        grad_ws = _c(grad_ws, 'project_step grad_ws')
-        if grad_ws.shape != w_in.shape:
-            raise ValueError(f'project_step: grad_ws must be {tuple(w_in.shape)} (got {tuple(grad_ws.shape)})')
-    if not isinstance(step, torch.Tensor) or not step.is_cuda or step.dtype != torch.int32 or step.numel() != 1:
-        raise TypeError('gan_lab_amd.ops: project_step step must be a 1-element int32 tensor on the GPU; the HIP path has no CPU '
-                        'fallback')
-    w_std = _c(w_std, 'project_step w_std')
-    if w_std.numel() != 1 or len(hyper) != 6:
-        raise ValueError('project_step: w_std must hold one value and hyper six (check_project_schedule)')
-    host_h = (ctypes.c_double * 6)(*[float(h) for h in hyper])
-    check(_lib.lib().ganlab_project_step_f32(_p(w_opt), _p(grad_ws), _p(m), _p(v), ctypes.c_void_p(step.data_ptr()), _p(noise),
-                                             _p(w_std), _p(w_in), n, l, int(w_plus), d, ctypes.cast(host_h, ctypes.c_void_p),
-                                             _st()), 'project_step')
-    return w_in

@@ -2,6 +2,7 @@
 against the exact-fp32 MFMA kernels of the same entry points, at the accuracy bar of the fp32 kernels (TOL of test_gpu_ops).
 The reference computes F.conv2d in fp32 (utils/custom_layers.py:202-211); the bar that the split products are 'fp32' is the
 rms distance to float64, which must not exceed ATen's own (tools/x3_bench.py; here: <= 1.1 x the exact kernels')."""
+import contextlib
 import ctypes
 
 import pytest
@@ -20,6 +21,16 @@ def ops():
     from gan_lab_amd import ops as _ops, _lib
     _lib.lib()
     return _ops
+
+
+@contextlib.contextmanager
+def x3_at_any_size(ops):
+    """The split-product kernels on these small cases too: no minimum tile count for the launch."""
+    old_min, ops._X3_MIN_TILES = ops._X3_MIN_TILES, 1
+    try:
+        yield
+    finally:
+        ops._X3_MIN_TILES = old_min
 
 
 def rms_rel(a, ref):
@@ -48,8 +59,7 @@ def test_x3_forward_and_input_gradient(ops, case):
     gy = torch.randn(n, co, h, w, generator=g)
     geom = ops.Geom(n, ci, h, w, co, 3, 1)
     scale = 1.0 / (3 * ci ** 0.5)
-    old_min, ops._X3_MIN_TILES = ops._X3_MIN_TILES, 1
-    try:
+    with x3_at_any_size(ops):
         assert ops.x3_ok(geom) and ops.x3_ok(geom, True)
         y3 = ops.k_conv_fwd(x.cuda(), wt.cuda(), b.cuda(), geom, scale, 0.5, ops.ACT_LRELU, 0.2)
         assert 'conv_x3_fwd_kernel' in launched(ops)
@@ -62,8 +72,6 @@ def test_x3_forward_and_input_gradient(ops, case):
             gx1 = ops.k_conv_dgrad(gy.cuda(), wt.cuda(), geom, scale)
         finally:
             ops.set_x3(prev)
-    finally:
-        ops._X3_MIN_TILES = old_min
     yd = F.leaky_relu(F.conv2d(x.double(), wt.double() * scale, None, padding=1) + 0.5 * b.double().view(1, -1, 1, 1), 0.2)
     xd = x.double().requires_grad_(True)
     gxd, = torch.autograd.grad(F.conv2d(xd, wt.double() * scale, padding=1), xd, gy.double())
@@ -83,12 +91,9 @@ def test_x3_masked_input_gradient(ops):
     wt = torch.randn(co, ci, 3, 3, generator=g)
     gy = torch.randn(n, co, h, w, generator=g)
     geom = ops.Geom(n, ci, h, w, co, 3, 1)
-    old_min, ops._X3_MIN_TILES = ops._X3_MIN_TILES, 1
-    try:
+    with x3_at_any_size(ops):
         gx3 = ops.k_conv_dgrad_mask(gy.cuda(), wt.cuda(), x.cuda(), geom, 0.03, 0.2)
         assert 'conv_x3_fwd_kernel' in launched(ops)
-    finally:
-        ops._X3_MIN_TILES = old_min
     xd = torch.zeros(n, ci, h, w, dtype=torch.float64, requires_grad=True)
     gxd, = torch.autograd.grad(F.conv2d(xd, wt.double() * 0.03, padding=1), xd, gy.double())
     gxd = gxd * torch.where(x > 0, 1.0, 0.2).double()
@@ -111,8 +116,7 @@ def test_x3_affine_on_load_and_tail(ops, noise):
     scale, eps = 0.02, 1e-8
     bd = a.double() * s_.double().view(n, ci, 1, 1) + t_.double().view(n, ci, 1, 1)
     conv = F.conv2d(bd, wt.double() * scale, None, padding=1)
-    old_min, ops._X3_MIN_TILES = ops._X3_MIN_TILES, 1
-    try:
+    with x3_at_any_size(ops):
         y = ops.k_conv_fwd_aff(a.cuda(), s_.cuda(), t_.cuda(), wt.cuda(), geom, scale)
         assert 'conv_x3_fwd_kernel' in launched(ops)
         assert_close(y.cpu(), conv, TOL, 'x3 affine-on-load forward vs float64')
@@ -129,8 +133,6 @@ def test_x3_affine_on_load_and_tail(ops, noise):
         nzc, nwc = (nz.cuda(), nw.cuda()) if noise else (None, None)
         _lib.check(L.ganlab_conv_fwd_aff_tail_x3(p(ac), p(wp), p(sc), p(tc), p(bc), p(nzc), p(nwc), p(yt), p(mean), p(rstd),
                                                  geom.ref(), 0.7, ops.ACT_LRELU, 0.2, eps, p(ws), ws.numel() * 8, None), 'tail')
-    finally:
-        ops._X3_MIN_TILES = old_min
     pre = conv + 0.7 * b.double().view(1, -1, 1, 1)
     if noise:
         pre = pre + nw.double().view(1, -1, 1, 1) * nz.double()
@@ -149,11 +151,8 @@ def test_x3_padding_stays_zero_under_the_affine(ops):
     s_, t_ = torch.ones(n, ci), torch.ones(n, ci)
     wt = torch.ones(co, ci, 3, 3)
     geom = ops.Geom(n, ci, h, w, co, 3, 1)
-    old_min, ops._X3_MIN_TILES = ops._X3_MIN_TILES, 1
-    try:
+    with x3_at_any_size(ops):
         y = ops.k_conv_fwd_aff(a.cuda(), s_.cuda(), t_.cuda(), wt.cuda(), geom, 1.0).cpu()
-    finally:
-        ops._X3_MIN_TILES = old_min
     assert y[0, 0, 8, 8].item() == 9 * ci and y[0, 0, 0, 0].item() == 4 * ci and y[0, 0, 0, 5].item() == 6 * ci
 
 
@@ -227,8 +226,7 @@ def test_x3_up_layer_forward(ops, case):
     geom = ops.Geom(n, ci, hl, wl, co, 3, 1, up=1)
     scale = 1.0 / (3 * ci ** 0.5)
     assert geom.s2
-    old_min, ops._X3_MIN_TILES = ops._X3_MIN_TILES, 1
-    try:
+    with x3_at_any_size(ops):
         assert ops.x3_s2_ok(geom)
         y3 = ops.k_conv_fwd(x.cuda(), wt.cuda(), b.cuda(), geom, scale, 0.5, ops.ACT_LRELU, 0.2)
         assert 'conv_x3_up_kernel' in launched(ops)
@@ -240,8 +238,6 @@ def test_x3_up_layer_forward(ops, case):
             assert 'conv_x3_up_kernel' not in launched(ops)
         finally:
             ops.set_x3(prev)
-    finally:
-        ops._X3_MIN_TILES = old_min
     up = F.interpolate(x.double(), scale_factor=2, mode='nearest')
     yd = F.leaky_relu(F.conv2d(up, wt.double() * scale, None, padding=1) + 0.5 * b.double().view(1, -1, 1, 1), 0.2)
     bd = x.double() * s_.double().view(n, ci, 1, 1) + t_.double().view(n, ci, 1, 1)
@@ -262,8 +258,7 @@ def test_x3_pooled_layer_input_gradient(ops, case):
     geom = ops.Geom(n, cin, 2 * hl, 2 * wl, cout, 3, 1, pool=1)
     scale = 1.0 / (3 * cin ** 0.5)
     assert geom.s2
-    old_min, ops._X3_MIN_TILES = ops._X3_MIN_TILES, 1
-    try:
+    with x3_at_any_size(ops):
         assert ops.x3_s2_ok(geom, True)
         gx3 = ops.k_conv_dgrad(gy.cuda(), wt.cuda(), geom, scale)
         assert 'conv_x3_up_kernel' in launched(ops)
@@ -273,8 +268,6 @@ def test_x3_pooled_layer_input_gradient(ops, case):
             assert 'conv_x3_up_kernel' not in launched(ops)
         finally:
             ops.set_x3(prev)
-    finally:
-        ops._X3_MIN_TILES = old_min
     xd = torch.zeros(n, cin, 2 * hl, 2 * wl, dtype=torch.float64, requires_grad=True)
     gxd, = torch.autograd.grad(F.avg_pool2d(F.conv2d(xd, wt.double() * scale, padding=1), 2), xd, gy.double())
     assert_close(gx3.cpu(), gxd, TOL, 'x3 pooled layer input gradient vs float64')
@@ -377,8 +370,7 @@ def test_x3_pooled_layer_forward(ops, case):
     b = torch.randn(co, generator=g)
     geom = ops.Geom(n, ci, 2 * hl, 2 * wl, co, 3, 1, pool=1)
     scale = 1.0 / (3 * ci ** 0.5)
-    old_min, ops._X3_MIN_TILES = ops._X3_MIN_TILES, 1
-    try:
+    with x3_at_any_size(ops):
         assert ops.x3_s2_down_ok(geom)
         y3 = ops.k_conv_fwd(x.cuda(), wt.cuda(), b.cuda(), geom, scale, 0.5, ops.ACT_LRELU, 0.2)
         assert 'conv_x3_down_kernel' in launched(ops)
@@ -388,8 +380,6 @@ def test_x3_pooled_layer_forward(ops, case):
             assert 'conv_x3_down_kernel' not in launched(ops)
         finally:
             ops.set_x3(prev)
-    finally:
-        ops._X3_MIN_TILES = old_min
     yd = F.leaky_relu(F.avg_pool2d(F.conv2d(x.double(), wt.double() * scale, None, padding=1), 2) + 0.5 * b.double().view(1, -1, 1, 1), 0.2)
     assert_close(y3.cpu(), yd, TOL, 'x3 pooled layer forward vs float64')
     assert_close(y3.cpu(), y1.cpu(), TOL, 'x3 pooled layer forward vs exact-fp32 kernel')
@@ -405,8 +395,7 @@ def test_x3_up_layer_input_gradient(ops, case):
     gy = torch.randn(n, cout, 2 * hl, 2 * wl, generator=g)
     geom = ops.Geom(n, cin, hl, wl, cout, 3, 1, up=1)
     scale = 1.0 / (3 * cin ** 0.5)
-    old_min, ops._X3_MIN_TILES = ops._X3_MIN_TILES, 1
-    try:
+    with x3_at_any_size(ops):
         assert ops.x3_s2_down_ok(geom, True)
         gx3 = ops.k_conv_dgrad(gy.cuda(), wt.cuda(), geom, scale)
         assert 'conv_x3_down_kernel' in launched(ops)
@@ -415,8 +404,6 @@ def test_x3_up_layer_input_gradient(ops, case):
             gx1 = ops.k_conv_dgrad(gy.cuda(), wt.cuda(), geom, scale)
         finally:
             ops.set_x3(prev)
-    finally:
-        ops._X3_MIN_TILES = old_min
     xd = torch.zeros(n, cin, hl, wl, dtype=torch.float64, requires_grad=True)
     gxd, = torch.autograd.grad(F.conv2d(F.interpolate(xd, scale_factor=2, mode='nearest'), wt.double() * scale, padding=1), xd, gy.double())
     assert_close(gx3.cpu(), gxd, TOL, 'x3 up layer input gradient vs float64')
