@@ -19,6 +19,7 @@ SO_PATH = os.path.join(CSRC, os.path.basename(os.environ.get('GANLAB_HIP_LIB', '
 
 _c_int, _c_ll, _c_f, _c_p, _c_sz, _c_u64 = (ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p,
                                              ctypes.c_size_t, ctypes.c_uint64)
+_c_d = ctypes.c_double
 
 ACT_NONE, ACT_LRELU = 0, 1
 PACK_FWD, PACK_DGRAD = 0, 1
@@ -348,6 +349,10 @@ SIGNATURES = {
     'ganlab_project_step_f32': (_c_int, [_c_p] * 8 + [_c_int, _c_int, _c_int, _c_int, _c_p, _c_p]),
     'ganlab_step_scalars_size': (_c_int, []),
     'ganlab_set_step_scalars': (_c_int, [_c_p, _c_u64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
+    'ganlab_ppl_endpoints_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_int, _c_d, _c_int, _c_int, _c_u64, _c_u64, _c_p]),
+    'ganlab_row_sqdist_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_ll, _c_p]),
+    'ganlab_trimmed_mean_workspace': (_c_sz, [_c_ll]),
+    'ganlab_trimmed_mean_f32': (_c_int, [_c_p, _c_ll, _c_d, _c_d, _c_p, _c_p, _c_sz, _c_p]),
 }
 
 _LIB = None

@@ -1,7 +1,7 @@
 """Launchers of the validation metrics.  No autograd: metrics run under ``torch.no_grad``.
 
-Drives csrc/swd.hip, csrc/prdc.hip, csrc/frechet.hip, csrc/kid.hip, csrc/msssim.hip and csrc/spectrum.hip; composed in
-gan_lab_amd/swd.py, prdc.py, frechet.py, kid.py, msssim.py and spectrum.py.  Re-exported by ``gan_lab_amd.ops``."""
+Drives csrc/swd.hip, csrc/prdc.hip, csrc/frechet.hip, csrc/kid.hip, csrc/ppl.hip, csrc/msssim.hip and csrc/spectrum.hip; composed
+in gan_lab_amd/swd.py, prdc.py, frechet.py, kid.py, ppl.py, msssim.py and spectrum.py.  Re-exported by ``gan_lab_amd.ops``."""
 import torch
 
 from .. import _lib
@@ -272,6 +272,87 @@ def kid_rowsums(queries, keys, gamma, coef0=1.0, exclude_diag=False, out=None):
     check(_lib.lib().ganlab_kid_rowsums_f32(_p(queries), m, _p(keys), n, d, gamma, coef0, 1 if exclude_diag else 0, _p(out),
                                             _st()), 'kid_rowsums')
     return out
+
+
+# ---- perceptual path length (csrc/ppl.hip; composed in gan_lab_amd/ppl.py) -----------------------------------------------------
+PPL_MAX_DIM = 4096                   # GANLAB_PPL_MAX_DIM (include/ganlab_hip.h)
+PPL_MODES = {'lerp': 0, 'slerp': 1}                  # GANLAB_PPL_LERP / _SLERP
+PPL_SAMPLINGS = {'full': 0, 'end': 1}                # GANLAB_PPL_FULL / _END
+PPL_RECORD = ('mean', 'lo', 'hi', 'kept', 'nonfinite')
+
+
+def check_ppl_epsilon(epsilon, what='ppl_endpoints: epsilon'):
+    """``epsilon`` as a float: finite, positive and below 1, else a ValueError that names ``what``."""
+    try:
+        eps = float(epsilon)
+    except (TypeError, ValueError):
+        eps = float('nan')
+    if isinstance(epsilon, bool) or not 0.0 < eps < 1.0:
+        raise ValueError(f'{what} must be a finite number in (0, 1) (got {epsilon!r})')
+    return eps
+
+
+def ppl_endpoints(a, b, epsilon, mode, sampling='full', seed=0, offset=0):
+    """``(t (N,), out (2, N, D))`` from the (N, D) rows ``a`` and ``b``: ``out[0]`` the point of the path from a to b at ``t``,
+    ``out[1]`` at ``t + epsilon``, one launch.  ``sampling`` 'full': ``t[n]`` uniform in [0, 1), one Philox counter per row from
+    ``offset`` under the key ``seed`` (a short draw is the prefix of a long one); 'end': t = 0.  ``mode`` 'lerp': ``a + (b - a) t``
+    (formed in double, rounded once); 'slerp': StyleGAN's spherical interpolation of the normalised rows, rescaled to norm
+    sqrt(D); parallel, antipodal or zero rows give ``a / |a| sqrt(D)`` at both ends.  D <= 4096."""
+    a, b = _prdc_rows(a, 'ppl_endpoints a'), _prdc_rows(b, 'ppl_endpoints b')
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError(f'ppl_endpoints: a and b must be equal (N, D) matrices on one device, got {tuple(a.shape)} on {a.device} '
+                         f'and {tuple(b.shape)} on {b.device}')
+    n, d = a.shape
+    if d > PPL_MAX_DIM:
+        raise ValueError(f'ppl_endpoints: the width of a and b must be at most {PPL_MAX_DIM}, got {d}')
+    if mode not in PPL_MODES:
+        raise ValueError(f"ppl_endpoints: mode must be 'lerp' or 'slerp', got {mode!r}")
+    if sampling not in PPL_SAMPLINGS:
+        raise ValueError(f"ppl_endpoints: sampling must be 'full' or 'end', got {sampling!r}")
+    eps = check_ppl_epsilon(epsilon)
+    if isinstance(offset, bool) or not isinstance(offset, int) or offset < 0:
+        raise ValueError(f'ppl_endpoints: offset must be a non-negative integer, got {offset!r}')
+    t, out = _new((n,), a), _new((2, n, d), a)
+    check(_lib.lib().ganlab_ppl_endpoints_f32(_p(a), _p(b), _p(t), _p(out), n, d, eps, PPL_MODES[mode], PPL_SAMPLINGS[sampling],
+                                              int(seed) & (2 ** 64 - 1), offset, _st()), 'ppl_endpoints')
+    return t, out
+
+
+def row_sqdist(x, y, out=None):
+    """(N,) squared Euclidean distances between the rows of two (N, D) matrices (two tensors, or the halves of one (2N, D)
+    tensor): differences, squares and sums in float64, rounded once."""
+    x, y = _prdc_rows(x, 'row_sqdist x'), _prdc_rows(y, 'row_sqdist y')
+    if x.shape != y.shape or x.device != y.device:
+        raise ValueError(f'row_sqdist: x and y must be equal (N, D) matrices on one device, got {tuple(x.shape)} on {x.device} '
+                         f'and {tuple(y.shape)} on {y.device}')
+    n, d = x.shape
+    out = _new((n,), x) if out is None else _prdc_vector(out, torch.float32, n, 'row_sqdist out')
+    check(_lib.lib().ganlab_row_sqdist_f32(_p(x), _p(y), _p(out), n, d, _st()), 'row_sqdist')
+    return out
+
+
+def trimmed_mean(v, q_lo=0.01, q_hi=0.99):
+    """(5,) float64 device record ``PPL_RECORD`` = (mean, lo, hi, kept, nonfinite) of the (n,) values ``v``: ``lo`` / ``hi`` are
+    numpy.percentile's 'lower' at quantile ``q_lo`` / 'higher' at ``q_hi`` (sorted on the device), ``kept`` the number of values
+    with lo <= v <= hi, ``mean`` their float64 mean.  A NaN or an infinity among the values: ``nonfinite`` counts them and
+    mean, lo and hi are NaN."""
+    v = _c(v, 'trimmed_mean values')
+    if v.dim() != 1 or v.numel() < 1:
+        raise ValueError(f'trimmed_mean: values must be a non-empty (n,) vector, got {tuple(v.shape)}')
+    try:
+        q_lo, q_hi = float(q_lo), float(q_hi)
+    except (TypeError, ValueError):
+        q_lo = q_hi = float('nan')
+    if not 0.0 <= q_lo <= q_hi <= 1.0:
+        raise ValueError(f'trimmed_mean: q_lo and q_hi must satisfy 0 <= q_lo <= q_hi <= 1, got {q_lo!r} and {q_hi!r}')
+    L = _lib.lib()
+    nbytes = L.ganlab_trimmed_mean_workspace(v.numel())
+    if nbytes == 0:
+        raise ValueError(f'trimmed_mean: {v.numel()} values are refused (the count must stay below 2^31)')
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=v.device)
+    record = torch.empty(len(PPL_RECORD), dtype=torch.float64, device=v.device)
+    check(L.ganlab_trimmed_mean_f32(_p(v), v.numel(), q_lo, q_hi, _p(record), _p(ws), ws.numel(), _st()), 'trimmed_mean')
+    return record
 
 
 # ---- multi-scale structural similarity (csrc/msssim.hip; composed in gan_lab_amd/msssim.py) -------------------------------------

@@ -107,6 +107,18 @@ FQ-BigGAN uses 2^10 codes, decay 0.8 and weight 1.0; these are the user's choice
 ranges, or a gradient penalty beside ``fq_codes > 0``, raises ValueError when the learner is built and names its field.  The layer's
 kernels are not in the package yet: a valid ``fq_codes > 0`` is still refused (NotImplementedError, as ``cgan='acgan'`` is) and 0
 builds nothing; ProGAN / StyleGAN have none of the three fields.
+``'ppl'`` as an entry of ``gen_metrics`` (ProGAN and StyleGAN): the perceptual path length of ppl.py - the StyleGAN paper's measure
+of how smooth the latent space is - of the generator the other metrics score: the mean squared image change per squared latent step
+along interpolation paths between ``ppl_samples`` (default 1024, >= 2) pairs of latents, after the distances outside the 1st .. 99th
+percentile are dropped.  ``ppl_space`` (``--ppl_space=none`` on the command line) is ``'z'`` (spherical paths between latents),
+``'w'`` (straight paths in StyleGAN's W; refused on ProGAN, which has none) or None: ``'w'`` for StyleGAN, ``'z'`` for ProGAN.
+``ppl_sampling`` is ``'full'`` (the step is taken at a uniformly drawn point of the path) or ``'end'`` (at its start);
+``ppl_epsilon`` (default 1e-4, finite, in (0, 1)) the step; ``ppl_seed`` (an integer in [0, 2**63)) fixes the latents, the points
+and the per-layer noise, so two evaluations of one generator agree bit for bit.  The image distance is ``ops.pyramid_mse`` over
+every level the resolution allows, not LPIPS (no pretrained network ships here): compare a run with itself, not with published
+numbers.  The metric needs no validation reals and is not available while a resolution fades in (its line then says so).  A
+value outside these ranges, or ``'ppl'`` among ``disc_metrics``, raises ValueError when the learner is built and names its field;
+the ResNet GAN has none of the five fields.
 ``--gradient_penalty=none`` on the command line means no penalty (None), as ``make_config(gradient_penalty=None)`` does.
 """
 import argparse
@@ -192,7 +204,9 @@ def _spec(model_type):
                  ('bit_exact_resampling', bool, False), ('eps_drift', float, .001), ('len_latent', int, 512),
                  ('nonlinearity', str.casefold, 'leaky relu'), ('leakiness', float, .2),
                  ('use_equalized_lr', bool, True), ('normalize_z', bool, True), ('mbstd_group_size', int, 4),
-                 ('use_ewma_gen', bool, True)]
+                 ('use_ewma_gen', bool, True),
+                 ('ppl_samples', int, 1024), ('ppl_space', _str_or_none, None), ('ppl_sampling', str.casefold, 'full'),
+                 ('ppl_epsilon', float, 1e-4), ('ppl_seed', int, 0)]
         if model_type == 'ProGAN':
             rows += [('num_main_iters', int, (NIMG_TRANSITION // BS) * 20),
                      ('lr_fctr_dict', dict, {4: 1., 8: 1., 16: 1., 32: 1., 64: 1., 128: 1., 256: 1., 512: 1.,

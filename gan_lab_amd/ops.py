@@ -6,7 +6,7 @@ the module state that tests, bench.py and tools rebind (DESIGN.md 4.4a lists the
 over one or two ``csrc/*.hip`` files, live in ``gan_lab_amd/_ops/`` and are imported below by name, so ``ops.<name>`` is the one
 way in for callers:
   _ops/core.py       plumbing (``_p``, ``_st``, ``_c``, ...) and the three autograd switches
-  _ops/metrics.py    SWD, PRDC, Frechet moments / KID, MS-SSIM, radial spectrum
+  _ops/metrics.py    SWD, PRDC, Frechet moments / KID, path length, MS-SSIM, radial spectrum
   _ops/optim.py      spectral norm, orthogonal regularisation, Adam, EWMA
   _ops/augment.py    random draws, DiffAugment, ADA
   _ops/cond.py       labels, conditional BatchNorm
@@ -48,7 +48,8 @@ from ._ops.core import (  # noqa: F401
 from ._ops.metrics import (  # noqa: F401
     SWD_DESC, _swd_planes, swd_down, swd_band, swd_gather, swd_stats, swd_project, _SWD_WS, _swd_workspace, swd_sort, swd_distance,
     swd_positions, swd_directions, PRDC_MAX_K, _prdc_rows, _prdc_vector, prdc_norms, prdc_knn, prdc_cross, MOMENTS_MAX_DIM,
-    _accumulator, moments_accum, kid_rowsums, MSSSIM_LEVELS, _msssim_images, msssim_workspace, msssim_level, msssim_finish,
+    _accumulator, moments_accum, kid_rowsums, PPL_MAX_DIM, PPL_MODES, PPL_SAMPLINGS, PPL_RECORD, check_ppl_epsilon, ppl_endpoints,
+    row_sqdist, trimmed_mean, MSSSIM_LEVELS, _msssim_images, msssim_workspace, msssim_level, msssim_finish,
     SPECTRUM_MIN_RES, SPECTRUM_MAX_RES, SPECTRUM_WINDOWS, _spectrum_size, spectrum_scratch_bytes, _spectrum_alloc,
     spectrum_workspace, spectrum_scratch, spectrum_feed, spectrum_finish)
 from ._ops.optim import (  # noqa: F401

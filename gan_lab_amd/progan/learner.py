@@ -22,7 +22,7 @@ import warnings
 import torch
 from torch import nn
 
-from .. import frechet, kid, msssim, ops, parallel, prdc, rng, spectrum, swd
+from .. import frechet, kid, msssim, ops, parallel, ppl, prdc, rng, spectrum, swd
 from .._int import LearnerConfigCopy
 from ..optim import EwmaTracker, ParamArena
 from ..resnetgan.learner import GANLearner
@@ -86,6 +86,7 @@ class ProGANLearner(GANLearner):
 
     def _init_progressive(self, config, learner_name):
         """Common constructor body of ProGANLearner / StyleGANLearner (progan/learner.py:104-206)."""
+        ppl.validate_config(config)      # the path length's options ('ppl' in config.gen_metrics; ppl.py), used by compute_metrics
         self.config = LearnerConfigCopy(config, learner_name, self._nonredefinable, REDEFINABLE_FROM_LEARNER_ATTRS)
         self._is_data_configed = False
         self._update_data_config(raise_exception=False)
@@ -591,6 +592,10 @@ class ProGANLearner(GANLearner):
                                  f"validation reals and cannot be listed among the critic's metrics (config.disc_metrics)")
             if want and valid_dl is None:
                 raise ValueError(f"'{name}' needs the validation reals: pass valid_dl (train(train_dl, valid_dl, z_valid_dl))")
+        want_ppl = 'ppl' in metrics
+        if want_ppl and metrics_type != 'generator':
+            raise ValueError("'ppl' is a generator metric: it measures the generator's latent space and cannot be listed among "
+                             "the critic's metrics (config.disc_metrics)")
         if want_grid and (self.ds_mean is None or self.data_config is None):
             self._update_data_config(raise_exception=True)
         self.disc_model.eval()
@@ -609,7 +614,7 @@ class ProGANLearner(GANLearner):
                 self._grid_fill = 0
             self._img_grid_constructed = False
             table = {m: torch.zeros(self.batch_size, n_batches, device=c.dev) for m in metrics
-                     if m not in ('swd', 'msssim', 'spectrum', 'prdc', 'fd', 'kid')}
+                     if m not in ('swd', 'msssim', 'spectrum', 'prdc', 'fd', 'kid', 'ppl')}
             swd_eval, swd_left = self._swd_begin(n_z, valid_dl) if want_swd else (None, 0)
             ms_fake, ms_real, ms_fake_left, ms_real_left = self._msssim_begin(n_z, valid_dl) if want_ms else (None, None, 0, 0)
             sp_fake, sp_real, sp_left = self._spectrum_begin(n_z, valid_dl) if want_sp else (None, None, 0)
@@ -715,6 +720,9 @@ class ProGANLearner(GANLearner):
             if want_kid:
                 vals['kid'] = kid_eval.result()
                 swd_lines = swd_lines + [('kid', vals['kid']['kid'])]
+            if want_ppl:
+                vals['ppl'], ppl_lines = self._ppl_evaluate()
+                swd_lines = swd_lines + ppl_lines
         finally:
             self.gen_model.train()
             self.disc_model.train()
@@ -722,7 +730,7 @@ class ProGANLearner(GANLearner):
         names = metrics + [name for name, _ in swd_lines]
         width = '%-' + str(max(len(m) for m in names) + 3) + 's'
         return ['    ' + (width % (m + ':')) + '%.4g' % vals[m] + '\n' for m in metrics
-                if m not in ('image grid', 'swd', 'msssim', 'spectrum', 'prdc', 'fd', 'kid')] + \
+                if m not in ('image grid', 'swd', 'msssim', 'spectrum', 'prdc', 'fd', 'kid', 'ppl')] + \
             ['    ' + (width % (name + ':')) + (v if isinstance(v, str) else '%.4g' % v) + '\n' for name, v in swd_lines]
 
     def _swd_begin(self, n_z, valid_dl):
@@ -756,6 +764,19 @@ class ProGANLearner(GANLearner):
             return self.gen_model_lagged(zb)
         finally:
             rng._STATE['offset'] = offset
+
+    def _ppl_evaluate(self):
+        """(the dict kept in last_metrics, [(line name, value)]): ``ppl.generator_path_length`` of the generator this method
+        scores - the time-averaged one when ``use_ewma_gen`` is on - over ``config.ppl_samples`` pairs in batches of the current
+        batch size.  It needs no validation data and leaves the training stream where it was."""
+        c = self.config
+        samples, space, sampling, epsilon, seed = ppl.validate_config(c)
+        if self.gen_model.fade_in_phase:
+            return {'ppl': float('nan'), 'space': space}, \
+                [('ppl', 'nan (not available while a resolution fades in: the image then blends two resolutions)')]
+        out = ppl.generator_path_length(self, samples, space, sampling=sampling, epsilon=epsilon, batch=self.batch_size, seed=seed)
+        out['space'] = space
+        return out, [('ppl', out['ppl'])]
 
     def _swd_finish(self, swd_eval):
         """(the dict kept in last_metrics, [(line name, value)])."""

@@ -1091,6 +1091,42 @@ int ganlab_w_moments_f32(const float* ws, float* w_avg, float* w_std, long long 
 int ganlab_project_step_f32(float* w_opt, const float* grad_ws, float* m, float* v, int* step, const float* noise,
                             const float* w_std, float* w_in, int N, int L, int w_plus, int D, const double* hyper, void* stream);
 
+/* ---- perceptual path length (csrc/ppl.hip; composed in gan_lab_amd/ppl.py).  No atomics, every sum in a fixed
+ * order: bitwise reproducible.  Stream-ordered; the host reads nothing back.  Every argument is checked before any launch.
+ *   ppl_endpoints: a, b (N, D) fp32 -> t (N,) and out (2, N, D): out[0] the point of the path from a to b at t, out[1] the point at
+ *                  t + eps (eps a double in (0, 1); the sum is formed in double).  One launch, one workgroup per row;
+ *                  1 <= D <= GANLAB_PPL_MAX_DIM, 1 <= N < 2^31.
+ *                  sampling FULL: t[n] = (w >> 8) 2^-24 in [0, 1), w = word 0 of Philox4x32-10 on the counter (offset + n, 0, 0, 0)
+ *                  (low, high 32 bits of offset + n first) under the key (low, high 32 bits of seed) - one counter per row, so
+ *                  the draw of N rows is the prefix of any longer one from the same seed and offset.  sampling END: t = 0.
+ *                  mode LERP:  a + (b - a) t per entry, in double from the fp32 operands, rounded once.
+ *                  mode SLERP: ah = a / |a|, bh = b / |b|, d = clamp(<ah, bh>, -1, 1), c = bh - d ah, ch = c / |c|;
+ *                  r = ah cos(t acos d) + ch sin(t acos d); out = r sqrt(D / |r|^2) (StyleGAN's slerp of normalised latents,
+ *                  rescaled to the radius sqrt(D) of a normal latent).  Entries, |a|^2, |b|^2, <ah, bh>, |c|^2 and |r|^2 are
+ *                  fp32 (fixed-order sums over the row's workgroup); acos, the angle, its sine and cosine and the final scale are
+ *                  formed in double from those and rounded once.  Where |c|^2 < 2^-30 (parallel or antipodal rows), |a| = 0 or
+ *                  |b| = 0, both points are ah sqrt(D), with ah = a where |a| = 0.  Finite for finite rows.
+ *   row_sqdist:    out[n] = sum_j (x[n, j] - y[n, j])^2 over N rows of D floats: differences, squares and the sum in double,
+ *                  rounded once to fp32.  x and y may be the two halves of one (2N, D) buffer.  D >= 1, 1 <= N < 2^31.
+ *   trimmed_mean:  v (n,) fp32, 1 <= n < 2^31 -> record of 5 doubles (mean, lo, hi, kept, nonfinite).  The values are sorted
+ *                  (rocPRIM radix sort into the workspace, ganlab_trimmed_mean_workspace(n) bytes; 0 = n refused);
+ *                  lo = sorted[floor((n - 1) q_lo)], hi = sorted[ceil((n - 1) q_hi)], the products in double, rounded once
+ *                  (numpy.percentile's 'lower' / 'higher'), 0 <= q_lo <= q_hi <= 1; kept = the number of
+ *                  values with lo <= v <= hi (ties at either bound all count); mean = their fp64 sum over kept, the sum taken
+ *                  over the sorted array in a fixed order.  With any NaN or infinity among the values: nonfinite = their number,
+ *                  mean = lo = hi = NaN, kept = 0. */
+#define GANLAB_PPL_MAX_DIM 4096
+#define GANLAB_PPL_LERP 0
+#define GANLAB_PPL_SLERP 1
+#define GANLAB_PPL_FULL 0
+#define GANLAB_PPL_END 1
+int ganlab_ppl_endpoints_f32(const float* a, const float* b, float* t, float* out, long long N, int D, double eps, int mode,
+                             int sampling, uint64_t seed, uint64_t offset, void* stream);
+int ganlab_row_sqdist_f32(const float* x, const float* y, float* out, long long N, long long D, void* stream);
+size_t ganlab_trimmed_mean_workspace(long long n);
+int ganlab_trimmed_mean_f32(const float* v, long long n, double q_lo, double q_hi, double* record, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
