@@ -3,9 +3,9 @@ switches with their state (input-gradient-only mode, "no gradient towards this l
 flat arena of ``optim.ParamArena``).
 
 Drives no kernel file of its own except the row-workspace size query of csrc/norm.hip.  ``gan_lab_amd.ops`` re-exports every name
-here.  Tests rebind ``ops._take`` and ``ops.direct_param_grads``: both are defined here, but ``_take`` is called
-only by functions of ``ops.py``, which read it as a global of that module, and the learners reach the context manager as
-``ops.direct_param_grads``."""
+here.  A test rebinds ``ops.direct_param_grads``: it is defined here, and the learners reach the context manager
+as ``ops.direct_param_grads``.  How many outputs went into an arena slot is counted here (``arena_takes``), whichever module the
+launcher that calls ``_take`` lives in."""
 import ctypes
 import os
 
@@ -156,6 +156,7 @@ def _wants_input_grad(ctx, x):
 # take the ordinary accumulating path.  Never active while a differentiable backward is being recorded.
 _DIRECT = [False]
 _SINK, _TAKEN = {}, {}
+_TAKE_HITS = [0]        # outputs that went into an arena slot, ever: the tests read the difference over a step
 
 
 def direct_grads_enabled():
@@ -207,8 +208,14 @@ def _take(name, shape, like):
             if base.grad.numel() == n and base.grad.device == like.device:
                 base._ganlab_written = base._ganlab_arena.serial
                 _TAKEN[name] = True
+                _TAKE_HITS[0] += 1
                 return base.grad.view(shape)
     return _new(shape, like)
+
+
+def arena_takes():
+    """How many ``_take`` calls have returned an arena slot so far (monotonic)."""
+    return _TAKE_HITS[0]
 
 
 def _sunk(name):

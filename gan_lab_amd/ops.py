@@ -1,11 +1,17 @@
-"""Autograd ops over the HIP C-ABI (include/ganlab_hip.h): the convolution and pointwise core, and the facade of the op families.
+"""Autograd ops over the HIP C-ABI (include/ganlab_hip.h): convolution dispatch with its fused tails, and the facade of the op
+families.
 
-This file holds the tightly coupled core - the compute-dtype switch, ``Geom``, the packed-weight cache, the ``k_conv_*``
-launchers, the mutually recursive conv Functions, deferred tails and handoffs, the norm, resampling, loss and attention ops - and
-the module state that tests, bench.py and tools rebind (DESIGN.md 4.4a lists the names).  The leaf families, each a launcher layer
-over one or two ``csrc/*.hip`` files, live in ``gan_lab_amd/_ops/`` and are imported below by name, so ``ops.<name>`` is the one
-way in for callers:
+This file holds one subject, the tightly coupled conv core - the packed-weight cache, the split-product gates, the ``k_conv_*``
+launchers, the mask-bits and fused-blur launchers, the mutually recursive conv Functions, handoffs, InstanceNorm, deferred tails
+and modulated convs - and the module state that tests, bench.py and tools rebind (DESIGN.md 4.4a lists the names).  The leaf
+families, each a launcher layer over one or two ``csrc/*.hip`` files, live in ``gan_lab_amd/_ops/`` and are imported below by
+name, so ``ops.<name>`` is the one way in for callers:
   _ops/core.py       plumbing (``_p``, ``_st``, ``_c``, ...) and the three autograd switches
+  _ops/geom.py       compute-dtype switch, ``Geom``, launch observer
+  _ops/pointwise.py  blur, up / pool / resample, bias_act and act_bwd launchers, channel sums, axpby, tanh, mul, per-channel affine
+  _ops/norm.py       BatchNorm (training), LayerNorm, their composed cross-checks
+  _ops/loss.py       minibatch stddev, scalar reductions, BCE / hinge / channel-norm penalty
+  _ops/attention.py  attention, 2x2 max pool, gated residual
   _ops/metrics.py    SWD, PRDC, Frechet moments / KID, path length, MS-SSIM, radial spectrum
   _ops/optim.py      spectral norm, orthogonal regularisation, Adam, EWMA
   _ops/augment.py    random draws, DiffAugment, ADA
@@ -33,7 +39,7 @@ All ops require contiguous fp32 CUDA(HIP) tensors and raise otherwise - there is
 import ctypes
 import os
 
-import numpy as np
+import numpy as np  # noqa: F401  (part of the module's surface: tests/golden/ops_surface.txt)
 
 import torch
 from torch.autograd import Function
@@ -44,7 +50,24 @@ from ._lib import ACT_LRELU, ACT_NONE, PACK_DGRAD, PACK_FWD, ConvGeom, check
 from ._ops.core import (  # noqa: F401
     _p, _RAW_STREAM, _GET_DEVICE, _st, _c, _inplace, _same_numel, _gpu_device, _new, _ct, _aligned16, _nchw, _row_workspace,
     _INPUT_GRAD_ONLY, input_grad_only, _want_param_grads, _NO_GRAD_TOWARDS, no_grad_towards, _wants_input_grad, _DIRECT, _SINK,
-    _TAKEN, direct_grads_enabled, direct_param_grads, _sink, _take, _sunk)
+    _TAKEN, _TAKE_HITS, direct_grads_enabled, direct_param_grads, _sink, _take, arena_takes, _sunk)
+from ._ops.geom import (  # noqa: F401
+    _COMPUTE, set_compute_dtype, get_compute_dtype, compute_dtype, Geom, pool_fusable, _OBSERVER, set_launch_observer, conv_flops,
+    _note)
+from ._ops.pointwise import (  # noqa: F401
+    k_blur, decode_u8, k_up2, k_pool2, RESAMPLE_MODES, _RESAMPLE_TABLES, resample_matrix, _taps, _resample_tables, k_resample,
+    k_bias_act, k_act_bwd, k_act_bwd_bias, k_channel_sum, k_axpby, k_scale_dev, k_sum, _ActBwd, _ActBwdBias, _ChanSum,
+    _GroupBroadcast, _Blur, _Pool2, _Up2, _Resample, _Scale, _Axpby, _PixelNorm, _ChanAffine, _Mul, _Tanh, _TanhBwd, chan_affine,
+    mul, tanh, channel_sum, blur, avg_pool2, upsample2, resample, lerp, scale, add, global_avg_pool, pixelnorm, group_broadcast)
+from ._ops.norm import (  # noqa: F401
+    _BatchNormTrain, batch_norm_composed, _ln_rowsums, _ln_project, _LayerNorm, _LayerNormBwd, layer_norm, layer_norm_composed)
+from ._ops.loss import (  # noqa: F401
+    _MbstdStat, _MbstdBwd, _Sum, _BceMean, _HingeMean, _HingeBwd, _ChNormPenalty, mbstd_stat, sum_all, sumsq_all, bce_logits_mean,
+    hinge_mean, chnorm_penalty)
+from ._ops.attention import (  # noqa: F401
+    _ATTN_SECOND_ORDER, _attn_dims, attention_ok, k_attn_fwd, k_attn_bwd, _Attention, _AttentionBwd, _pool_dims, k_maxpool2x2,
+    k_maxpool2x2_bwd, _MaxPool2x2, _MaxPool2x2Bwd, k_gated_residual, k_dot, _GatedResidual, _GatedResidualBwd, attention,
+    max_pool2x2, gated_residual)
 from ._ops.metrics import (  # noqa: F401
     SWD_DESC, _swd_planes, swd_down, swd_band, swd_gather, swd_stats, swd_project, _SWD_WS, _swd_workspace, swd_sort, swd_distance,
     swd_positions, swd_directions, PRDC_MAX_K, _prdc_rows, _prdc_vector, prdc_norms, prdc_knn, prdc_cross, MOMENTS_MAX_DIM,
@@ -71,118 +94,6 @@ from ._ops.cond_loss import (  # noqa: F401
 from ._ops.project import (  # noqa: F401
     PYRAMID_MAX_LEVELS, PROJECT_SCHEDULE, pyramid_max_levels, check_pyramid_weights, _PyramidMse, pyramid_mse, w_moments,
     check_project_schedule, project_step)
-
-
-# ---- compute dtype of the dense 3x3 convolutions ---------------------------------------------------
-# 'f32' (default): exact fp32 MFMA, the reference's arithmetic.  'bf16': BASELINE config #2 "bf16 compute /
-# fp32 master" - eligible 3x3 layers multiply bf16-rounded operands on v_mfma_f32_16x16x32_bf16 with fp32
-# accumulation (csrc/conv_bf16.hip); tensors in HBM, parameters, optimiser state and every other kernel stay fp32.
-_COMPUTE = ['f32']
-
-
-def set_compute_dtype(name):
-    if name not in ('f32', 'bf16'):
-        raise ValueError("compute dtype must be 'f32' or 'bf16'")
-    _COMPUTE[0] = name
-
-
-def get_compute_dtype():
-    return _COMPUTE[0]
-
-
-class compute_dtype(object):
-    """with ops.compute_dtype('bf16'): ... - graphs BUILT inside keep their kernels for the backward."""
-
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        self._prev = _COMPUTE[0]
-        set_compute_dtype(self.name)
-
-    def __exit__(self, *exc):
-        _COMPUTE[0] = self._prev
-        return False
-
-
-class Geom:
-    """Static description of one convolution (mirrors ganlab_conv_geom) + derived output size.
-    ``up``: nearest 2x upsample folded in front; ``pool``: 2x2 average pool folded behind (stride-2
-    fused kernels, csrc/conv_s2.hip).  ``s2`` tells whether the stride-2 fast path applies."""
-    __slots__ = ('N', 'Cin', 'Hin', 'Win', 'Cout', 'ks', 'pad', 'up', 'pool', 'Ho', 'Wo', 's2', '_c', 'bf', 'bf_fused')
-
-    _CACHE = {}
-
-    def __new__(cls, N, Cin, Hin, Win, Cout, ks, pad, up=0, pool=0):
-        # a training step builds the same few dozen geometries again and again; each costs two ctypes structures and
-        # two library queries, so they are interned (instances are immutable after construction).  An instance enters
-        # the cache only once its construction has SUCCEEDED: a rejected geometry raises on every attempt.
-        key = (int(N), int(Cin), int(Hin), int(Win), int(Cout), int(ks), int(pad), int(bool(up)), int(bool(pool)),
-               _COMPUTE[0])
-        g = cls._CACHE.get(key)
-        if g is None:
-            g = object.__new__(cls)
-            g._c = None
-            g._build(*key[:9])
-            if len(cls._CACHE) > 4096:
-                cls._CACHE.clear()
-            cls._CACHE[key] = g
-        return g
-
-    def __init__(self, N, Cin, Hin, Win, Cout, ks, pad, up=0, pool=0):
-        pass            # built (and validated) in __new__
-
-    def _build(self, N, Cin, Hin, Win, Cout, ks, pad, up, pool):
-        if ks not in (1, 3):
-            raise ValueError('conv kernels support ks in {1, 3}; a 4x4 valid conv runs as a linear')
-        self.N, self.Cin, self.Hin, self.Win, self.Cout, self.ks, self.pad, self.up, self.pool = \
-            int(N), int(Cin), int(Hin), int(Win), int(Cout), int(ks), int(pad), int(bool(up)), int(bool(pool))
-        hv, wv = (2 * Hin, 2 * Win) if up else (Hin, Win)
-        self.Ho, self.Wo = hv + 2 * pad - ks + 1, wv + 2 * pad - ks + 1
-        if self.pool:
-            self.Ho, self.Wo = self.Ho // 2, self.Wo // 2
-        cg = ConvGeom(self.N, self.Cin, self.Hin, self.Win, self.Cout, self.ks, self.pad, self.up, self.pool)
-        # bf16 compute mode (decided HERE, so a backward that runs outside the `compute_dtype` block still uses the
-        # kernels its forward used).  ``bf``: the plain geometry at the resolution of the taps (what the weight-gradient
-        # kernels take, on a materialised upsample of x or of the pooled layer's gy); ``bf_fused``: this geometry with
-        # its up / pool flag - the forward and input-gradient kernels fold the resampling in
-        self.bf = self.bf_fused = None
-        if _COMPUTE[0] == 'bf16':
-            v = ConvGeom(self.N, self.Cin, hv, wv, self.Cout, self.ks, self.pad, 0, 0)
-            if _lib.lib().ganlab_conv_bf16_supported(ctypes.byref(v)):
-                self.bf = v
-                if (self.up or self.pool) and _lib.lib().ganlab_conv_bf16_supported(ctypes.byref(cg)):
-                    self.bf_fused = cg
-                elif self.pool:
-                    self.bf = None
-        self.s2 = bool(self.bf is None and (self.up or self.pool) and
-                       _lib.lib().ganlab_conv_s2_supported(ctypes.byref(cg)))
-        if self.pool and not self.s2 and self.bf_fused is None:
-            raise ValueError('pool=1 geometry is not supported by the stride-2 kernels; compose conv + pool')
-        self._c = cg
-
-    def ref(self):
-        return ctypes.byref(self._c)
-
-    @property
-    def in_shape(self):
-        return (self.N, self.Cin, self.Hin, self.Win)
-
-    @property
-    def out_shape(self):
-        return (self.N, self.Cout, self.Ho, self.Wo)
-
-
-def pool_fusable(N, Cin, Hin, Win, Cout, ks, pad):
-    """Whether conv(ks, pad) followed by AvgPool2d(2) can run as ONE stride-2 kernel."""
-    if ks != 3 or pad != 1:
-        return False
-    if _COMPUTE[0] == 'bf16':
-        v = ConvGeom(int(N), int(Cin), int(Hin), int(Win), int(Cout), 3, 1, 0, 1)
-        if _lib.lib().ganlab_conv_bf16_supported(ctypes.byref(v)):
-            return True         # the bf16 kernel sums the 2 x 2 outputs in its epilogue
-    c = ConvGeom(int(N), int(Cin), int(Hin), int(Win), int(Cout), 3, 1, 0, 1)
-    return bool(_lib.lib().ganlab_conv_s2_supported(ctypes.byref(c)))
 
 
 # ---- packed-weight cache ------------------------------------------------------------------------
@@ -488,34 +399,6 @@ def _packed_x3_s2(w, up, scale):
 
 def _packed_x3(w, mode, scale):
     return _packed_x3_any('conv_x3_pack', 'x3', w, mode, scale, 3)
-
-
-# ---- launch observer (measurement only) -------------------------------------------------------------
-# bench.py / tools/step_layers.py count the convolution FLOPs the step actually EXECUTES (stride-2 fused layers run
-# 16 low-resolution taps instead of 4 x 9, the shared D(real) forward and the skipped weight gradients never launch)
-# by registering a callable here; every conv launcher reports (kind, Geom) to it.  None = no overhead.
-_OBSERVER = [None]
-
-
-def set_launch_observer(fn):
-    prev = _OBSERVER[0]
-    _OBSERVER[0] = fn
-    return prev
-
-
-def conv_flops(g):
-    """FLOPs one pass (forward, input gradient or weight gradient) over geometry ``g`` executes in this library."""
-    if g.s2:
-        lo_h, lo_w = (g.Hin, g.Win) if g.up else (g.Ho, g.Wo)
-        return 2.0 * 16 * g.Cin * g.Cout * lo_h * lo_w * g.N
-    if g.bf is not None:       # bf16 layers run all 9 taps at the taps' resolution, also with a folded upsample / pool
-        return 2.0 * g.ks * g.ks * g.Cin * g.Cout * g.bf.Hin * g.bf.Win * g.N
-    return 2.0 * g.ks * g.ks * g.Cin * g.Cout * g.Ho * g.Wo * g.N
-
-
-def _note(kind, g):
-    if _OBSERVER[0] is not None:
-        _OBSERVER[0](kind, g)
 
 
 # ---------------------------------------------------------------------------------------------- #
@@ -859,14 +742,6 @@ def k_conv_wgrad(gy, x, g, scale):
     return gw
 
 
-def k_blur(x):
-    x = _c(x)
-    n, c, h, w = x.shape
-    y = torch.empty_like(x)
-    check(_lib.lib().ganlab_blur3x3_f32(_p(x), _p(y), n * c, h, w, _st()), 'blur3x3')
-    return y
-
-
 _MASK_BITS = [None]
 
 
@@ -900,29 +775,6 @@ def k_blur_bits(x):
 
 def _is_bits(y):
     return y.dtype == torch.int32
-
-
-def decode_u8(images_u8_nhwc, res, mean, std, flip=None):
-    """Real-image input path on the device: (N,Hs,Ws,C) uint8 -> box-downsample by the
-    power-of-two factor Hs/res (bit-exact with PIL's BOX resize) -> (N,C,res,res) fp32 ``(v/255 - mean)/std``
-    (data_config.py:307-341).  ``flip``: optional (N,) uint8/bool mask, horizontal mirror per image."""
-    x = images_u8_nhwc
-    if not x.is_cuda or x.dtype != torch.uint8 or x.dim() != 4:
-        raise TypeError('decode_u8 needs a (N,H,W,C) uint8 tensor on the GPU')
-    x = x.contiguous()
-    n, hs, ws, c = x.shape
-    if hs % res or ws % res or hs // res != ws // res:
-        raise ValueError(f'cannot box-resize {hs}x{ws} to {res}x{res}')
-    mean = torch.as_tensor(mean, dtype=torch.float32, device=x.device).contiguous()
-    std = torch.as_tensor(std, dtype=torch.float32, device=x.device).contiguous()
-    assert mean.numel() == c and std.numel() == c
-    if flip is not None:
-        flip = flip.to(device=x.device, dtype=torch.uint8).contiguous()
-        assert flip.numel() == n
-    out = torch.empty((n, c, res, res), dtype=torch.float32, device=x.device)
-    check(_lib.lib().ganlab_u8_box_decode_f32(x.data_ptr(), _p(out), n, hs, ws, c, hs // res, _p(mean), _p(std),
-                                              flip.data_ptr() if flip is not None else None, _st()), 'u8_box_decode')
-    return out
 
 
 def blur_fusable(x):
@@ -1026,175 +878,6 @@ def k_act_bwd_blur(g, y, noise, slope, bias_scale, want_gb, want_gnw):
                                              _p(gnw), n, c, h, w, slope, bias_scale, _p(ws),
                                              ws.numel() * 4 if ws is not None else 0, _st()), 'act_bwd_blur')
     return out, gb, gnw
-
-
-def k_up2(x, scale=1.0):
-    x = _c(x)
-    n, c, h, w = x.shape
-    y = _new((n, c, 2 * h, 2 * w), x)
-    check(_lib.lib().ganlab_up2_f32(_p(x), _p(y), n * c, h, w, scale, _st()), 'up2')
-    return y
-
-
-def k_pool2(x, scale=0.25):
-    x = _c(x)
-    n, c, h, w = x.shape
-    assert h % 2 == 0 and w % 2 == 0
-    y = _new((n, c, h // 2, w // 2), x)
-    check(_lib.lib().ganlab_pool2_f32(_p(x), _p(y), n * c, h // 2, w // 2, scale, _st()), 'pool2')
-    return y
-
-
-# ---- table-driven resamplers: nn.Upsample(mode='bilinear'), NearestPool2d, BilinearPool2d (custom_layers.py:59-75) ---
-RESAMPLE_MODES = ('bilinear_up', 'bilinear_down', 'nearest_down')
-_RESAMPLE_TABLES = {}
-
-
-def resample_matrix(mode, align_corners, n_in):
-    """1-D interpolation matrix (n_out x n_in, float64 entries that are float32 numbers) of ``F.interpolate`` at scale
-    2 / 0.5, with ATen's source-index arithmetic in float32: align_corners -> src = dst * (n_in-1)/(n_out-1); else
-    src = (dst + .5) / scale - .5 clamped at 0 (bilinear), floor(dst / scale) (nearest)."""
-    if mode not in RESAMPLE_MODES:
-        raise ValueError(f'resampler mode {mode!r}: one of {RESAMPLE_MODES}')
-    f32 = np.float32
-    n_out = 2 * n_in if mode == 'bilinear_up' else n_in // 2
-    if n_out < 1 or (mode != 'bilinear_up' and n_in % 2):
-        raise ValueError(f'{mode}: size {n_in} has no 0.5x / 2x counterpart')
-    m = np.zeros((n_out, n_in), np.float64)
-    inv = f32(0.5) if mode == 'bilinear_up' else f32(2.0)
-    for o in range(n_out):
-        if mode == 'nearest_down':
-            m[o, min(int(np.floor(f32(o) * inv)), n_in - 1)] = 1.0
-            continue
-        if align_corners:
-            r = f32(n_in - 1) / f32(n_out - 1) if n_out > 1 else f32(0)
-            src = r * f32(o)
-        else:
-            src = max(inv * (f32(o) + f32(0.5)) - f32(0.5), f32(0))
-        i0 = min(int(src), n_in - 1)
-        i1 = i0 + (1 if i0 < n_in - 1 else 0)
-        l1 = f32(src) - f32(i0)
-        m[o, i0] += float(f32(1) - l1)
-        m[o, i1] += float(l1)
-    return m
-
-
-def _taps(m):
-    nz = [np.nonzero(row)[0] for row in m]
-    t = max(1, max(len(v) for v in nz))
-    if t > 6:
-        raise ValueError(f'resampler needs {t} taps per output (the kernel holds 6)')
-    idx, w = np.zeros((m.shape[0], t), np.int32), np.zeros((m.shape[0], t), np.float32)
-    for o, v in enumerate(nz):
-        idx[o, :len(v)] = v
-        w[o, :len(v)] = m[o, v]
-    return idx, w, t
-
-
-def _resample_tables(mode, align, n_in, adjoint, device):
-    key = (mode, bool(align), int(n_in), bool(adjoint), str(device))
-    tab = _RESAMPLE_TABLES.get(key)
-    if tab is None:
-        m = resample_matrix(mode, align, n_in)
-        idx, w, t = _taps(m.T if adjoint else m)
-        tab = (torch.from_numpy(idx).to(device), torch.from_numpy(w).to(device), t, idx.shape[0])
-        _RESAMPLE_TABLES[key] = tab
-    return tab
-
-
-def k_resample(x, mode, align, hin, win, adjoint):
-    """``adjoint=False``: (N, C, hin, win) -> the resampled map; ``True``: a map of the resampled size -> (N, C, hin, win)
-    through the transposed interpolation matrices (the layer's backward; its own backward is the forward again)."""
-    x = _c(x)
-    n, c, h, w = x.shape
-    iy, wy, ty, ho = _resample_tables(mode, align, hin, adjoint, x.device)
-    ix, wx, tx, wo = _resample_tables(mode, align, win, adjoint, x.device)
-    exp_h = hin if not adjoint else (2 * hin if mode == 'bilinear_up' else hin // 2)
-    exp_w = win if not adjoint else (2 * win if mode == 'bilinear_up' else win // 2)
-    if (h, w) != (exp_h, exp_w):
-        raise ValueError(f'resample {mode} (adjoint={adjoint}): input {h}x{w}, expected {exp_h}x{exp_w}')
-    y = _new((n, c, ho, wo), x)
-    check(_lib.lib().ganlab_resample2d_f32(_p(x), _p(y), _p(iy), _p(wy), _p(ix), _p(wx), n * c, h, w, ho, wo, ty, tx,
-                                           _st()), 'resample2d')
-    return y
-
-
-def k_bias_act(x, bias, noise, noise_w, bias_scale, act, slope):
-    x = _c(x)
-    n, c, hw = _nchw(x)
-    y = torch.empty_like(x)
-    bias = _c(bias) if bias is not None else None
-    noise = _c(noise) if noise is not None else None
-    noise_w = _c(noise_w) if noise_w is not None else None
-    if noise is not None:
-        assert noise.numel() == n * hw and noise_w.numel() == c
-    check(_lib.lib().ganlab_bias_act_f32(_p(x), _p(bias), _p(noise), _p(noise_w), _p(y), n, c, hw, bias_scale, act,
-                                         slope, _st()), 'bias_act')
-    return y
-
-
-def k_act_bwd(gy, y, slope):
-    gy, y = _c(gy), _c(y)
-    assert gy.shape == y.shape
-    gz = torch.empty_like(gy)
-    check(_lib.lib().ganlab_act_bwd_f32(_p(gy), _p(y), _p(gz), gy.numel(), slope, _st()), 'act_bwd')
-    return gz
-
-
-def k_act_bwd_bias(gy, y, slope, scale):
-    gy, y = _c(gy), _c(y)
-    assert gy.shape == y.shape
-    n, c, hw = _nchw(gy)
-    L = _lib.lib()
-    ws = torch.empty((L.ganlab_channel_sum_workspace(n, c, hw) + 3) // 4, dtype=torch.float32, device=gy.device)
-    gz, gb = torch.empty_like(gy), _take('gb', (c,), gy)
-    check(L.ganlab_act_bwd_bias_f32(_p(gy), _p(y), _p(gz), _p(gb), n, c, hw, slope, scale, _p(ws), ws.numel() * 4,
-                                    _st()), 'act_bwd_bias')
-    return gz, gb
-
-
-def k_channel_sum(a, b=None, scale=1.0, sink=None):
-    a = _c(a)
-    n, c, hw = _nchw(a)
-    L = _lib.lib()
-    nbytes = L.ganlab_channel_sum_workspace(n, c, hw)
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=a.device)
-    out = _take(sink, (c,), a) if sink is not None else _new((c,), a)
-    b = _c(b) if b is not None else None
-    check(L.ganlab_channel_sum_f32(_p(a), _p(b), _p(out), n, c, hw, scale, _p(ws), ws.numel() * 4, _st()),
-          'channel_sum')
-    return out
-
-
-def k_axpby(x, y, a, b, out=None):
-    """a*x + b*y; ``out`` may be ``y`` itself (running averages updated in place: a captured step must write the buffer
-    the next replay reads)."""
-    x = _c(x)
-    y = _c(y) if y is not None else None
-    if y is not None:
-        assert x.shape == y.shape
-    if out is None:
-        out = torch.empty_like(x)
-    assert out.is_contiguous() and out.shape == x.shape
-    check(_lib.lib().ganlab_axpby_f32(_p(x), _p(y), _p(out), x.numel(), a, b, _st()), 'axpby')
-    return out
-
-
-def k_scale_dev(x, gout, a, shape=None):
-    gout = _c(gout)
-    x = _c(x) if x is not None else None
-    out = torch.empty_like(x) if x is not None else _new(shape, gout)
-    check(_lib.lib().ganlab_scale_dev_f32(_p(x), _p(gout), _p(out), out.numel(), a, _st()), 'scale_dev')
-    return out
-
-
-def k_sum(x, scale=1.0, squared=False):
-    x = _c(x)
-    L = _lib.lib()
-    ws = torch.empty((L.ganlab_sum_workspace(x.numel()) + 3) // 4, dtype=torch.float32, device=x.device)
-    out = _new((), x)
-    check(L.ganlab_sum_f32(_p(x), _p(out), x.numel(), scale, int(squared), _p(ws), ws.numel() * 4, _st()), 'sum')
-    return out
 
 
 # ---------------------------------------------------------------------------------------------- #
@@ -1445,43 +1128,6 @@ class _ConvDgradBlurAct(Function):
         return d_gy, d_w, None, None, None, None, None, None
 
 
-class _ActBwd(Function):
-    """gz = gy * lrelu'(y) from the saved OUTPUT y (sign(y) == sign(pre-activation))."""
-
-    @staticmethod
-    def forward(ctx, gy, y, slope):
-        ctx.save_for_backward(y)
-        ctx.slope = slope
-        return k_act_bwd(gy, y, slope)
-
-    @staticmethod
-    def backward(ctx, gg):
-        y, = ctx.saved_tensors
-        return _ActBwd.apply(gg, y, ctx.slope), None, None
-
-
-class _ActBwdBias(Function):
-    """(gz, gb) = (gy * lrelu'(y), bias_scale * sum_{n,hw} gz) in one pass over the tensors."""
-
-    @staticmethod
-    def forward(ctx, gy, y, slope, bias_scale):
-        ctx.save_for_backward(y)
-        ctx.slope, ctx.bias_scale = slope, bias_scale
-        gz, gb = k_act_bwd_bias(gy, y, slope, bias_scale)
-        return gz, gb
-
-    @staticmethod
-    def backward(ctx, ggz, ggb):
-        y, = ctx.saved_tensors
-        g = ggz
-        if ggb is not None:
-            shape = y.shape
-            view = [1, shape[1]] + [1] * (len(shape) - 2)
-            b = _Scale.apply(ggb.view(view).expand(shape), ctx.bias_scale)
-            g = b if g is None else _Axpby.apply(g, b, 1.0, 1.0)
-        return (_ActBwd.apply(g, y, ctx.slope) if g is not None else None), None, None, None
-
-
 class _BlurActBwd(Function):
     """(out, gb) = (lrelu'(y) * blur(g), bias_scale * sum_{n,hw} out): the backward of  conv+bias+LeakyReLU
     -> blur  in one pass.  Linear in g; its adjoint is _ActBwdBlur."""
@@ -1564,41 +1210,6 @@ class _BlurBiasAct(Function):
             want_nw = False
         return (gx if ctx.needs_input_grad[0] else None), (gb.view(ctx.bias_shape) if want_b else None), None, \
             (gnw.view(ctx.nw_shape) if want_nw else None), None, None, None, None
-
-
-class _ChanSum(Function):
-    """(N,C,...) -> (C,) sum, optionally weighted by a (N,1,...) map (noise-weight gradient)."""
-
-    @staticmethod
-    def forward(ctx, a, b, scale, sink=None):
-        ctx.shape, ctx.scale = a.shape, scale
-        ctx.has_b = b is not None
-        return k_channel_sum(a, b, scale, sink)
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.has_b:
-            raise NotImplementedError('double backward through the noise-weighted channel sum')
-        shape = ctx.shape
-        view = [1, shape[1]] + [1] * (len(shape) - 2)
-        return _Scale.apply(g.view(view).expand(shape), ctx.scale), None, None, None
-
-
-class _GroupBroadcast(Function):
-    """(G,) -> (G*gs, 1, h, w): every sample of group g gets stat[g] on its whole plane (the minibatch-stddev feature map,
-    custom_layers.py:135-139).  Its adjoint is a per-group sum: a channel-sum launch instead of the ATen reduction that
-    autograd derives for ``expand``; the pair is closed under differentiation (R1 differentiates through it)."""
-
-    @staticmethod
-    def forward(ctx, stat, gs, h, w):
-        ctx.dims = (stat.shape[0], gs, h, w)
-        G = stat.shape[0]
-        return stat.view(G, 1, 1, 1, 1).expand(G, gs, 1, h, w).reshape(G * gs, 1, h, w)
-
-    @staticmethod
-    def backward(ctx, g):
-        G, gs, h, w = ctx.dims
-        return _ChanSum.apply(g.reshape(1, G, gs * h * w), None, 1.0), None, None, None
 
 
 class _ConvBiasAct(Function):
@@ -1770,79 +1381,6 @@ class _BiasAct(Function):
                 gnw = None
         return (gz if ctx.needs_input_grad[0] else None), (gb.view(ctx.bias_shape) if gb is not None else None), \
             None, gnw, None, None, None, None
-
-
-class _Blur(Function):
-    @staticmethod
-    def forward(ctx, x):
-        return k_blur(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _Blur.apply(g)  # symmetric taps + zero padding -> self-adjoint
-
-
-class _Pool2(Function):
-    @staticmethod
-    def forward(ctx, x, scale):
-        ctx.scale = scale
-        return k_pool2(x, scale)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _Up2.apply(g, ctx.scale), None
-
-
-class _Up2(Function):
-    @staticmethod
-    def forward(ctx, x, scale):
-        ctx.scale = scale
-        return k_up2(x, scale)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _Pool2.apply(g, ctx.scale), None
-
-
-class _Resample(Function):
-    """Linear map x -> M_y x M_x^T; backward is the adjoint gather, whose backward is the forward (R1 reaches the critic's
-    pooler through a double backward)."""
-
-    @staticmethod
-    def forward(ctx, x, mode, align, hin, win, adjoint):
-        ctx.args = (mode, align, hin, win, adjoint)
-        return k_resample(x, mode, align, hin, win, adjoint)
-
-    @staticmethod
-    def backward(ctx, g):
-        mode, align, hin, win, adjoint = ctx.args
-        return _Resample.apply(g, mode, align, hin, win, not adjoint), None, None, None, None, None
-
-
-class _Scale(Function):
-    @staticmethod
-    def forward(ctx, x, a):
-        ctx.a = a
-        return k_axpby(x, None, a, 0.0)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _Scale.apply(g, ctx.a), None
-
-
-class _Axpby(Function):
-    """out = a*x + b*y (fade-in blends, progan/architectures.py:163-167, :311-315)."""
-
-    @staticmethod
-    def forward(ctx, x, y, a, b):
-        ctx.a, ctx.b = a, b
-        return k_axpby(x, y, a, b)
-
-    @staticmethod
-    def backward(ctx, g):
-        gx = _Scale.apply(g, ctx.a) if ctx.needs_input_grad[0] else None
-        gy = _Scale.apply(g, ctx.b) if ctx.needs_input_grad[1] else None
-        return gx, gy, None, None
 
 
 # ---------------------------------------------------------------------------------------------- #
@@ -2467,523 +2005,6 @@ class _ToRGBMod(Function):
         return ga, None, None, gw, gb, None, None, None
 
 
-class _PixelNorm(Function):
-    @staticmethod
-    def forward(ctx, x, eps):
-        x = _c(x)
-        n, c, hw = _nchw(x)
-        y = torch.empty_like(x)
-        check(_lib.lib().ganlab_pixelnorm_fwd_f32(_p(x), _p(y), n, c, hw, eps, _st()), 'pixelnorm_fwd')
-        ctx.save_for_backward(x)
-        ctx.eps = eps
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, = ctx.saved_tensors
-        gy = _c(gy)
-        n, c, hw = _nchw(x)
-        gx = torch.empty_like(x)
-        check(_lib.lib().ganlab_pixelnorm_bwd_f32(_p(gy), _p(x), _p(gx), n, c, hw, ctx.eps, _st()), 'pixelnorm_bwd')
-        return gx, None
-
-
-# ---------------------------------------------------------------------------------------------- #
-# BatchNorm / LayerNorm building blocks (ResNet GAN path): every piece is closed under differentiation,
-# so torch.autograd composes first and second derivatives (WGAN-GP through LayerNorm) from HIP kernels.
-# ---------------------------------------------------------------------------------------------- #
-class _ChanAffine(Function):
-    """y[n,c,...] = x[n,c,...] * scale[c] + shift[c]  (scale / shift may be None)."""
-
-    @staticmethod
-    def forward(ctx, x, scale, shift):
-        x = _c(x)
-        n, c, hw = _nchw(x)
-        sc = _c(scale) if scale is not None else None
-        sh = _c(shift) if shift is not None else None
-        y = torch.empty_like(x)
-        check(_lib.lib().ganlab_chan_affine_f32(_p(x), _p(sc), _p(sh), _p(y), n, c, hw, _st()), 'chan_affine')
-        ctx.save_for_backward(x, sc)
-        ctx.has = (scale is not None, shift is not None)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        x, sc = ctx.saved_tensors
-        gx = _ChanAffine.apply(g, sc, None) if ctx.needs_input_grad[0] else None
-        gs = _ChanSum.apply(_Mul.apply(g, x), None, 1.0) if (ctx.has[0] and ctx.needs_input_grad[1]) else None
-        gt = _ChanSum.apply(g, None, 1.0) if (ctx.has[1] and ctx.needs_input_grad[2]) else None
-        return gx, gs, gt
-
-
-class _Mul(Function):
-    @staticmethod
-    def forward(ctx, a, b):
-        a, b = _c(a), _c(b)
-        assert a.shape == b.shape
-        out = torch.empty_like(a)
-        check(_lib.lib().ganlab_mul_f32(_p(a), _p(b), _p(out), a.numel(), _st()), 'mul')
-        ctx.save_for_backward(a, b)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        a, b = ctx.saved_tensors
-        return (_Mul.apply(g, b) if ctx.needs_input_grad[0] else None,
-                _Mul.apply(g, a) if ctx.needs_input_grad[1] else None)
-
-
-class _Tanh(Function):
-    """nn.Tanh: the ResNet generators' output layer, and the hidden activation of ``--nonlinearity tanh``
-    (config.py:208,254; resnetgan/learner.py:180-181).  The backward is a Function of its own so that a gradient penalty
-    differentiates through it (a critic with tanh activations under WGAN-GP / R1)."""
-    @staticmethod
-    def forward(ctx, x):
-        x = _c(x)
-        y = torch.empty_like(x)
-        check(_lib.lib().ganlab_tanh_fwd_f32(_p(x), _p(y), x.numel(), _st()), 'tanh_fwd')
-        ctx.save_for_backward(y)
-        ctx.set_materialize_grads(False)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        if g is None:
-            return None
-        y, = ctx.saved_tensors
-        return _TanhBwd.apply(g, y)
-
-
-class _TanhBwd(Function):
-    """gx = g * (1 - y^2), y = tanh(x): linear in g, and d gx / d y = -2 g y (the second order of tanh)."""
-    @staticmethod
-    def forward(ctx, g, y):
-        g, y = _c(g), _c(y)
-        gx = torch.empty_like(g)
-        check(_lib.lib().ganlab_tanh_bwd_f32(_p(g), _p(y), _p(gx), g.numel(), _st()), 'tanh_bwd')
-        ctx.save_for_backward(g, y)
-        return gx
-
-    @staticmethod
-    def backward(ctx, go):
-        g, y = ctx.saved_tensors
-        gg = _TanhBwd.apply(go, y) if ctx.needs_input_grad[0] else None
-        gy = scale(mul(mul(go, g), y), -2.0) if ctx.needs_input_grad[1] else None
-        return gg, gy
-
-
-def chan_affine(x, scale=None, shift=None):
-    return _ChanAffine.apply(x, scale, shift)
-
-
-def mul(a, b):
-    return _Mul.apply(a, b)
-
-
-def tanh(x):
-    return _Tanh.apply(x)
-
-
-def channel_sum(x):
-    return _ChanSum.apply(x, None, 1.0)
-
-
-class _BatchNormTrain(Function):
-    """nn.BatchNorm2d in training mode on fused kernels (csrc/norm.hip): batch statistics (2 launches), the C-element
-    bookkeeping - rstd, scale, running estimates, batch counter - in one (``bn_finalize``), normalise + affine (1);
-    backward sums = the parameter gradients (2) and the input gradient (1).  First order only - the generator is never
-    inside a gradient penalty.  Returns (y, batch mean, biased batch variance)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, eps, running_mean, running_var, momentum, batches, act_slope):
-        x = _c(x)
-        n, c, hw = _nchw(x)
-        m = n * hw
-        L = _lib.lib()
-        ws = _row_workspace(c, m, x.device)
-        mom = _new((c, 3), x)
-        check(L.ganlab_bn_stats_f32(_p(x), _p(mom), n, c, hw, ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, _st()),
-              'bn_stats')
-        fin = _new((4, c), x)                                # mean, var, rstd, scale = rstd * weight
-        for buf in (running_mean, running_var, batches):
-            assert buf is None or (buf.is_contiguous() and buf.device == x.device)
-        assert batches is None or batches.dtype == torch.int64
-        check(L.ganlab_bn_finalize_f32(_p(mom), _p(_c(weight)) if weight is not None else None,
-                                       _p(running_mean) if running_mean is not None else None,
-                                       _p(running_var) if running_var is not None else None,
-                                       ctypes.c_void_p(batches.data_ptr()) if batches is not None else None, _p(fin), c,
-                                       float(eps), float(momentum), m / max(m - 1, 1), _st()), 'bn_finalize')
-        mean, var, rstd, scale = fin[0], fin[1], fin[2], fin[3]
-        y = torch.empty_like(x)
-        # act_slope: the LeakyReLU / ReLU behind the normalisation (resnetgan/resblocks.py:48-49) applied by the same pass;
-        # its backward is applied by bn_bwd_sums as it loads the gradient (sign(y) = sign of the pre-activation)
-        check(L.ganlab_bn_apply_f32(_p(x), _p(mean), _p(scale), _p(_c(bias)) if bias is not None else None, _p(y), n, c,
-                                    hw, ACT_LRELU if act_slope is not None else ACT_NONE,
-                                    float(act_slope) if act_slope is not None else 1.0, _st()), 'bn_apply')
-        ctx.save_for_backward(x, mean, rstd, scale, y if act_slope is not None else None)
-        ctx.act_slope = act_slope
-        ctx.has_weight, ctx.has_bias = weight is not None, bias is not None
-        ctx.mark_non_differentiable(mean, var)
-        return y, mean, var
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy, _gm, _gv):
-        x, mean, rstd, scale, yact = ctx.saved_tensors
-        gy = _c(gy)
-        n, c, hw = _nchw(x)
-        L = _lib.lib()
-        ws = _row_workspace(c, n * hw, x.device)
-        sums = _new((c, 3), x)
-        gz = torch.empty_like(gy) if yact is not None else None      # gy * lrelu'(y), written by the sums pass
-        check(L.ganlab_bn_bwd_sums_f32(_p(gy), _p(x), _p(mean), _p(rstd), _p(sums), n, c, hw,
-                                       ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, _p(yact), _p(gz),
-                                       float(ctx.act_slope) if yact is not None else 1.0, _st()), 'bn_bwd_sums')
-        if gz is not None:
-            gy = gz
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            check(L.ganlab_bn_bwd_apply_f32(_p(gy), _p(x), _p(mean), _p(rstd), _p(sums), _p(scale), _p(gx), n, c, hw,
-                                            _st()), 'bn_bwd_apply')
-        want_p = _want_param_grads()
-        gw = sums[:, 1] if (ctx.has_weight and want_p and ctx.needs_input_grad[1]) else None
-        gb = sums[:, 0] if (ctx.has_bias and want_p and ctx.needs_input_grad[2]) else None
-        return gx, gw, gb, None, None, None, None, None, None
-
-
-def batch_norm(x, weight, bias, running_mean, running_var, training, momentum=0.1, eps=1e-5, batches=None,
-               act_slope=None):
-    """nn.BatchNorm2d semantics (biased variance for the normalisation, unbiased for the running estimate): fused
-    kernels in training mode (``batches``: the module's ``num_batches_tracked``, counted by the same launch that moves the
-    running estimates), one per-channel affine with the running statistics in eval mode."""
-    if training:
-        return _BatchNormTrain.apply(x, weight, bias, float(eps), running_mean, running_var, float(momentum), batches,
-                                     act_slope)[0]
-    xc = chan_affine(x, None, -running_mean)          # centred, like the training path
-    rstd = torch.rsqrt(running_var + eps)
-    y = chan_affine(xc, rstd * weight if weight is not None else rstd, bias)
-    return y if act_slope is None else bias_act(y, act='lrelu', slope=act_slope)
-
-
-def batch_norm_composed(x, weight, bias, eps=1e-5):
-    """Training-mode BatchNorm composed from channel sums / per-channel affines / products (any order of
-    differentiation through autograd): the cross-check of the fused kernels in the tests."""
-    n, c, hw = _nchw(x)
-    m = n * hw
-    mean = channel_sum(x) / m
-    xc = chan_affine(x, None, -mean)
-    var = channel_sum(mul(xc, xc)) / m
-    rstd = torch.rsqrt(var + eps)
-    return chan_affine(xc, rstd * weight if weight is not None else rstd, bias)
-
-
-def _ln_rowsums(a, wa, x, mean, rstd, n, m, b2=None, w2=None, yact=None, gz=None, slope=1.0):
-    """[N][3] row sums (see ganlab_ln_rowsums_f32): sum a*wa, sum a*wa*xhat, sum a*b2*w2; with ``yact`` a is first multiplied
-    by lrelu'(yact) and that product is also written to ``gz``."""
-    L = _lib.lib()
-    nbytes = L.ganlab_ln_rowsums_workspace(n, m)
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
-    out = _new((n, 3), x)
-    check(L.ganlab_ln_rowsums_f32(_p(a), _p(wa), _p(x), _p(mean), _p(rstd), _p(b2), _p(w2), _p(out), n, m,
-                                  ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, _p(yact), _p(gz), float(slope), _st()),
-          'ln_rowsums')
-    return out
-
-
-def _ln_project(a, wa, x, mean, rstd, sums, wo, n, m):
-    """wo * P_x(a * wa) with P_x(g) = rstd * (g - mean(g) - xhat * mean(g * xhat)) per row."""
-    out = torch.empty_like(x)
-    check(_lib.lib().ganlab_ln_project_f32(_p(a), _p(wa), _p(x), _p(mean), _p(rstd), _p(sums), _p(wo), _p(out), n, m,
-                                           _st()), 'ln_project')
-    return out
-
-
-class _LayerNorm(Function):
-    """nn.LayerNorm(x.shape[1:]) with elementwise affine on fused kernels (csrc/norm.hip): 2 launches forward,
-    4 backward, 7 for the backward of the backward (WGAN-GP through the critic)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, eps, act_slope):
-        x = _c(x)
-        n = x.shape[0]
-        m = x.numel() // n
-        w = _c(weight).reshape(m) if weight is not None else None
-        b = _c(bias).reshape(m) if bias is not None else None
-        L = _lib.lib()
-        mean, rstd = _new((n,), x), _new((n,), x)
-        nbytes = L.ganlab_row_stats_workspace(n, m)
-        ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
-        check(L.ganlab_row_stats_f32(_p(x), _p(mean), _p(rstd), n, m, eps, _p(ws), ws.numel() * 8, _st()), 'ln_stats')
-        y = torch.empty_like(x)
-        # act_slope: the LeakyReLU / ReLU behind the normalisation (resnetgan/resblocks.py:48-49) in the same pass; the
-        # backward applies its derivative while loading the gradient for the row sums (sign(y) = sign of the pre-activation)
-        check(L.ganlab_ln_affine_fwd_f32(_p(x), _p(mean), _p(rstd), _p(w), _p(b), _p(y), n, m,
-                                         ACT_LRELU if act_slope is not None else ACT_NONE,
-                                         float(act_slope) if act_slope is not None else 1.0, _st()), 'ln_affine_fwd')
-        # the weight INPUT is saved: the double backward reaches the parameter
-        ctx.save_for_backward(x, weight, mean, rstd, y if act_slope is not None else None)
-        ctx.act_slope = act_slope
-        ctx.wshape = weight.shape if weight is not None else None
-        ctx.has_bias = bias is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, weight, mean, rstd, yact = ctx.saved_tensors
-        w = weight.reshape(-1) if weight is not None else None      # tracked under create_graph
-        want_p = _want_param_grads() and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        gx, gw, gb = _LayerNormBwd.apply(gy, x, w, mean, rstd, want_p, yact, ctx.act_slope)
-        if gw is not None and ctx.wshape is not None:
-            gw = gw.reshape(ctx.wshape)
-            gb = gb.reshape(ctx.wshape) if ctx.has_bias else None
-        else:
-            gw = gb = None
-        return gx, gw, gb if ctx.has_bias else None, None, None
-
-
-class _LayerNormBwd(Function):
-    """(gy, x, w) -> (gx, gw, gb); its own backward is the analytic double backward for a cotangent of gx (the
-    gradient-penalty pass never keeps gw / gb: ops.input_grad_only).  With ``yact`` (the output of a LayerNorm fused with
-    its LeakyReLU) gy is the gradient BEHIND the activation: gz = gy * lrelu'(yact) is formed by the row-sums pass and takes
-    gy's place everywhere below; lrelu'' = 0, so the double backward only gains the same mask on its d/d gy."""
-
-    @staticmethod
-    def forward(ctx, gy, x, w, mean, rstd, want_param_grads, yact=None, act_slope=None):
-        gy = _c(gy)
-        w = _c(w) if w is not None else None
-        n = x.shape[0]
-        m = x.numel() // n
-        L = _lib.lib()
-        if yact is not None:
-            gz = torch.empty_like(gy)
-            sums = _ln_rowsums(gy, w, x, mean, rstd, n, m, yact=yact, gz=gz, slope=act_slope)
-            gy = gz
-        else:
-            sums = _ln_rowsums(gy, w, x, mean, rstd, n, m)             # a = mean(ghat), beta = mean(ghat * xhat)
-        gw = gb = None
-        if want_param_grads and w is not None:       # projection and parameter gradients in one pass over (gy, x)
-            gx, gw, gb = torch.empty_like(x), _new((m,), x), _new((m,), x)
-            check(L.ganlab_ln_bwd_cols_f32(_p(gy), _p(w), _p(x), _p(mean), _p(rstd), _p(sums), _p(gx), _p(gw), _p(gb), n, m,
-                                           _st()), 'ln_bwd_cols')
-        else:
-            gx = _ln_project(gy, w, x, mean, rstd, sums, None, n, m)   # P_x(gy * w)
-        ctx.save_for_backward(gy, x, w, mean, rstd, gx, sums, yact)
-        ctx.act_slope = act_slope
-        ctx.set_materialize_grads(False)
-        return gx, gw, gb
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, u, ggw, ggb):
-        gy, x, w, mean, rstd, gx, sums, yact = ctx.saved_tensors
-        if ggw is not None or ggb is not None:
-            raise NotImplementedError('LayerNorm double backward through the parameter gradients is not needed by the '
-                                      'GAN losses (the penalty differentiates the INPUT gradient only)')
-        if u is None:
-            return None, None, None, None, None, None, None, None
-        u = _c(u)
-        n = x.shape[0]
-        m = x.numel() // n
-        L = _lib.lib()
-        usums = _ln_rowsums(u, None, x, mean, rstd, n, m, b2=gy, w2=w)   # sum u, sum u*xhat, sum u*ghat
-        pu = _ln_project(u, None, x, mean, rstd, usums, None, n, m)      # P_x(u)
-        g_w = None
-        if w is not None:
-            g_gy = torch.empty_like(gy)
-            check(L.ganlab_colscale_f32(_p(pu), _p(w), _p(g_gy), n, m, _st()), 'ln_colscale')
-            if _want_param_grads() and ctx.needs_input_grad[2]:
-                g_w = _new((m,), x)
-                check(L.ganlab_coldot_f32(_p(gy), _p(pu), None, None, _p(g_w), None, n, m, _st()), 'ln_coldot')
-        else:
-            g_gy = pu
-        g_x = torch.empty_like(x)       # the per-row coefficients come from (sums, usums) inside the kernel
-        check(L.ganlab_ln_bwdbwd_apply_f32(_p(x), _p(mean), _p(rstd), _p(pu), _p(gx), _p(sums), _p(usums), _p(g_x),
-                                           n, m, _st()), 'ln_bwdbwd_apply')
-        if yact is not None:
-            g_gy = k_act_bwd(g_gy, yact, ctx.act_slope)
-        return g_gy, g_x, g_w, None, None, None, None, None
-
-
-def layer_norm(x, weight, bias, eps=1e-5, act_slope=None):
-    """nn.LayerNorm(normalized_shape = x.shape[1:]) semantics: per-sample statistics over all features (biased
-    variance), then the elementwise affine - fused kernels with an analytic double backward (csrc/norm.hip).
-    ``act_slope``: LeakyReLU(act_slope) (0 = ReLU) of the result in the same passes, forward and backward."""
-    return _LayerNorm.apply(x, weight, bias, float(eps), None if act_slope is None else float(act_slope))
-
-
-def layer_norm_composed(x, weight, bias, eps=1e-5):
-    """The same operator composed from channel sums / per-channel affines / products (every piece closed under
-    differentiation, so autograd derives any order): the cross-check of the fused kernels in the tests."""
-    shape = x.shape
-    n = shape[0]
-    f = x.numel() // n
-    xr = x.reshape(1, n, f)
-    mean = channel_sum(xr) / f
-    xc = chan_affine(xr, None, -mean)
-    var = channel_sum(mul(xc, xc)) / f
-    y = chan_affine(xc, torch.rsqrt(var + eps), None)
-    if weight is not None:
-        y = chan_affine(y.reshape(n, f, 1), weight.reshape(f), bias.reshape(f) if bias is not None else None)
-    return y.reshape(shape)
-
-
-# ---------------------------------------------------------------------------------------------- #
-# minibatch stddev statistic with explicit second order (discriminator, R1 path)
-# ---------------------------------------------------------------------------------------------- #
-class _MbstdStat(Function):
-    @staticmethod
-    def forward(ctx, x, gs, eps):
-        x = _c(x)
-        b = x.shape[0]
-        G, F = b // gs, x.numel() // b
-        stat = _new((G,), x)
-        check(_lib.lib().ganlab_mbstd_fwd_f32(_p(x), _p(stat), G, gs, F, eps, _st()), 'mbstd_fwd')
-        ctx.save_for_backward(x)
-        ctx.gs, ctx.eps = gs, eps
-        return stat
-
-    @staticmethod
-    def backward(ctx, gstat):
-        x, = ctx.saved_tensors
-        return _MbstdBwd.apply(x, gstat, ctx.gs, ctx.eps), None, None
-
-
-class _MbstdBwd(Function):
-    @staticmethod
-    def forward(ctx, x, gstat, gs, eps):
-        x, gstat = _c(x), _c(gstat)
-        b = x.shape[0]
-        G, F = b // gs, x.numel() // b
-        gx = torch.empty_like(x)
-        check(_lib.lib().ganlab_mbstd_bwd_f32(_p(x), _p(gstat), _p(gx), G, gs, F, eps, _st()), 'mbstd_bwd')
-        ctx.save_for_backward(x, gstat)
-        ctx.gs, ctx.eps = gs, eps
-        return gx
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, ggx):
-        x, gstat = ctx.saved_tensors
-        ggx = _c(ggx)
-        b = x.shape[0]
-        G, F = b // ctx.gs, x.numel() // b
-        g_gstat, g_x = _new((G,), x), torch.empty_like(x)
-        check(_lib.lib().ganlab_mbstd_bwdbwd_f32(_p(x), _p(gstat), _p(ggx), _p(g_gstat), _p(g_x), G, ctx.gs, F,
-                                                 ctx.eps, _st()), 'mbstd_bwdbwd')
-        return g_x, g_gstat, None, None
-
-
-# ---------------------------------------------------------------------------------------------- #
-# scalar reductions / losses (first-order)
-# ---------------------------------------------------------------------------------------------- #
-class _Sum(Function):
-    """scale * sum(x) or scale * sum(x^2) -> 0-dim tensor; the cotangent never leaves the device."""
-
-    @staticmethod
-    def forward(ctx, x, scale, squared):
-        ctx.save_for_backward(x if squared else None)
-        ctx.scale, ctx.squared, ctx.shape = scale, squared, x.shape
-        return k_sum(x, scale, squared)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gout):
-        x, = ctx.saved_tensors
-        if ctx.squared:
-            return k_scale_dev(x, gout.reshape(1), 2.0 * ctx.scale), None, None
-        return k_scale_dev(None, gout.reshape(1), ctx.scale, ctx.shape), None, None
-
-
-class _BceMean(Function):
-    @staticmethod
-    def forward(ctx, x, target):
-        x = _c(x)
-        out = _new((), x)
-        check(_lib.lib().ganlab_bce_logits_fwd_f32(_p(x), _p(out), x.numel(), target, _st()), 'bce_fwd')
-        ctx.save_for_backward(x)
-        ctx.target = target
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gout):
-        x, = ctx.saved_tensors
-        gx = torch.empty_like(x)
-        g1 = _c(gout).reshape(1)
-        check(_lib.lib().ganlab_bce_logits_bwd_f32(_p(x), _p(g1), _p(gx), x.numel(), ctx.target, _st()), 'bce_bwd')
-        return gx, None
-
-
-class _HingeMean(Function):
-    """mean(max(a + b*x, 0)) -> 0-dim tensor (the hinge loss terms: backprop_utils.hinge_loss_disc)."""
-
-    @staticmethod
-    def forward(ctx, x, a, b):
-        x = _c(x)
-        out = _new((), x)
-        check(_lib.lib().ganlab_hinge_fwd_f32(_p(x), _p(out), x.numel(), a, b, _st()), 'hinge_fwd')
-        ctx.save_for_backward(x)
-        ctx.a, ctx.b = a, b
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        x, = ctx.saved_tensors
-        return _HingeBwd.apply(x, gout, ctx.a, ctx.b), None, None
-
-
-class _HingeBwd(Function):
-    """gx = gout * [a + b*x > 0] * b / n: piecewise constant in x (its derivative towards x is zero), linear in gout."""
-
-    @staticmethod
-    def forward(ctx, x, gout, a, b):
-        gx = torch.empty_like(x)
-        g1 = _c(gout).reshape(1)
-        check(_lib.lib().ganlab_hinge_bwd_f32(_p(x), _p(g1), _p(gx), x.numel(), a, b, _st()), 'hinge_bwd')
-        ctx.save_for_backward(x)
-        ctx.a, ctx.b = a, b
-        return gx
-
-    @staticmethod
-    def backward(ctx, gg):
-        x, = ctx.saved_tensors
-        ggout = None
-        if ctx.needs_input_grad[1]:
-            one = torch.ones(1, dtype=torch.float32, device=x.device)
-            ggout = sum_all(mul(_c(gg), _HingeBwd.apply(x, one, ctx.a, ctx.b)))
-        return torch.zeros_like(x), ggout, None, None
-
-
-class _ChNormPenalty(Function):
-    """scale * sum_{n,hw} (||g[n,:,hw]||_2 - gamma)^2  (WGAN-GP, resnetgan/learner.py:817-823)."""
-
-    @staticmethod
-    def forward(ctx, g, gamma, scale):
-        g = _c(g)
-        n, c, hw = _nchw(g)
-        L = _lib.lib()
-        ws = torch.empty((L.ganlab_sum_workspace(n * hw) + 3) // 4, dtype=torch.float32, device=g.device)
-        out = _new((), g)
-        check(L.ganlab_chnorm_penalty_fwd_f32(_p(g), _p(out), n, c, hw, gamma, scale, _p(ws), ws.numel() * 4, _st()),
-              'chnorm_penalty_fwd')
-        ctx.save_for_backward(g)
-        ctx.gamma, ctx.scale = gamma, scale
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gout):
-        g, = ctx.saved_tensors
-        n, c, hw = _nchw(g)
-        gg = torch.empty_like(g)
-        g1 = _c(gout).reshape(1)
-        check(_lib.lib().ganlab_chnorm_penalty_bwd_f32(_p(g), _p(g1), _p(gg), n, c, hw, ctx.gamma, ctx.scale, _st()),
-              'chnorm_penalty_bwd')
-        return gg, None, None
-
-
 # ---------------------------------------------------------------------------------------------- #
 # functional API
 # ---------------------------------------------------------------------------------------------- #
@@ -3083,44 +2104,19 @@ def _with_stats(out, asked, fused):
     return (out[0], (out[1], out[2])) if fused is not None else (out, None)
 
 
-def blur(x):
-    return _Blur.apply(x)
-
-
-def avg_pool2(x):
-    return _Pool2.apply(x, 0.25)
-
-
-def upsample2(x):
-    return _Up2.apply(x, 1.0)
-
-
-def resample(x, mode, align_corners=False):
-    """``F.interpolate`` at scale 2 (``'bilinear_up'``) / 0.5 (``'bilinear_down'``, ``'nearest_down'``) of an NCHW map:
-    nn.Upsample(mode='bilinear') / BilinearPool2d / NearestPool2d of the reference (custom_layers.py:59-75)."""
-    if x.dim() == 3:
-        x = x.view(-1, *x.shape)
-    return _Resample.apply(x, mode, bool(align_corners), int(x.shape[2]), int(x.shape[3]), False)
-
-
-def lerp(a, b, alpha):
-    """a*(1-alpha) + b*alpha."""
-    return _Axpby.apply(a, b, float(1.0 - alpha), float(alpha))
-
-
-def scale(x, a):
-    return _Scale.apply(x, float(a))
-
-
-def add(a, b):
-    """Residual sum a + b."""
-    return _Axpby.apply(a, b, 1.0, 1.0)
-
-
-def global_avg_pool(x):
-    """nn.AvgPool2d(kernel_size=H) on an (N,C,H,H) map -> (N,C,1,1): plane sums through the channel-sum kernel."""
-    n, c, h, w = x.shape
-    return (_ChanSum.apply(x.reshape(1, n * c, h * w), None, 1.0 / (h * w))).view(n, c, 1, 1)
+# stays here, not with the rest of BatchNorm in _ops/norm.py: its eval path reads ``bias_act``, which tools/flip_probe.py rebinds
+def batch_norm(x, weight, bias, running_mean, running_var, training, momentum=0.1, eps=1e-5, batches=None,
+               act_slope=None):
+    """nn.BatchNorm2d semantics (biased variance for the normalisation, unbiased for the running estimate): fused
+    kernels in training mode (``batches``: the module's ``num_batches_tracked``, counted by the same launch that moves the
+    running estimates), one per-channel affine with the running statistics in eval mode."""
+    if training:
+        return _BatchNormTrain.apply(x, weight, bias, float(eps), running_mean, running_var, float(momentum), batches,
+                                     act_slope)[0]
+    xc = chan_affine(x, None, -running_mean)          # centred, like the training path
+    rstd = torch.rsqrt(running_var + eps)
+    y = chan_affine(xc, rstd * weight if weight is not None else rstd, bias)
+    return y if act_slope is None else bias_act(y, act='lrelu', slope=act_slope)
 
 
 def layer_tail(x, bias=None, noise=None, noise_w=None, style=None, bias_scale=1.0, act=None, slope=0.2, blur=False,
@@ -3145,10 +2141,6 @@ def instnorm_style(x, style=None, eps=1e-8, stats=None):
     return _InstNormStyle.apply(x, style, float(eps), stats[0], stats[1])
 
 
-def pixelnorm(x, eps=1e-8):
-    return _PixelNorm.apply(x, float(eps))
-
-
 def style_mod(x, style):
     """AdaIN's affine WITHOUT the normalisation (``use_instancenorm=False``, stylegan/architectures.py:497-526 with the
     norm list empty): ``x * (ys + 1) + yb`` with ``style`` = (N, 2C) = [ys | yb].  A per-(sample, channel) affine is the
@@ -3159,35 +2151,6 @@ def style_mod(x, style):
     ys1 = (st[:, 0] + 1.0).reshape(-1).contiguous()
     yb = st[:, 1].reshape(-1).contiguous()
     return chan_affine(x.reshape(1, n * c, *x.shape[2:]), ys1, yb).reshape(x.shape)
-
-
-def group_broadcast(stat, group_size, h, w):
-    return _GroupBroadcast.apply(stat, int(group_size), int(h), int(w))
-
-
-def mbstd_stat(x, group_size, eps=1e-8):
-    return _MbstdStat.apply(x, int(group_size), float(eps))
-
-
-def sum_all(x, scale=1.0):
-    return _Sum.apply(x, float(scale), False)
-
-
-def sumsq_all(x, scale=1.0):
-    return _Sum.apply(x, float(scale), True)
-
-
-def bce_logits_mean(x, target):
-    return _BceMean.apply(x, float(target))
-
-
-def hinge_mean(x, a, b):
-    """mean(relu(a + b*x)) with its first derivative; the double backward towards ``x`` is zero."""
-    return _HingeMean.apply(x, float(a), float(b))
-
-
-def chnorm_penalty(g, gamma, scale):
-    return _ChNormPenalty.apply(g, float(gamma), float(scale))
 
 
 def layer_tail_deferred(x, bias=None, noise=None, noise_w=None, style=None, bias_scale=1.0, act=None, slope=0.2,
@@ -3221,194 +2184,5 @@ def torgb_mod_ok(d, weight):
         return False
     n, c, h, w = d.a.shape
     return tuple(weight.shape[1:]) == (c, 1, 1) and weight.shape[0] <= 4 and c <= 16 and (h * w) % 4 == 0
-
-
-# ---------------------------------------------------------------------------------------------- #
-# self-attention (csrc/attention.hip; attention.py): first-order only
-# ---------------------------------------------------------------------------------------------- #
-_ATTN_SECOND_ORDER = ('self_attention: double backward through {} is not implemented (use hinge + spectral norm with '
-                      'gradient_penalty=None on a critic with attention)')
-
-
-def _attn_dims(q, k, v):
-    if not (q.dim() >= 3 and k.dim() >= 3 and v.dim() >= 3):
-        raise ValueError('attention: q, k, v must be (N, D, L...) tensors')
-    n, dk, dv = q.shape[0], q.shape[1], v.shape[1]
-    l, s = q[0, 0].numel(), k[0, 0].numel()
-    if k.shape[0] != n or v.shape[0] != n or k.shape[1] != dk or v[0, 0].numel() != s:
-        raise ValueError(f'attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit')
-    return n, dk, dv, l, s
-
-
-def attention_ok(n, dk, dv, l, s):
-    """Does the fused kernel take this geometry (``ganlab_attn_supported``)?"""
-    return bool(_lib.lib().ganlab_attn_supported(int(n), int(dk), int(dv), int(l), int(s)))
-
-
-def k_attn_fwd(q, k, v):
-    q, k, v = _c(q, 'attention q'), _c(k, 'attention k'), _c(v, 'attention v')
-    n, dk, dv, l, s = _attn_dims(q, k, v)
-    o, lse = _new((n, dv) + tuple(q.shape[2:]), q), _new((n, l), q)
-    check(_lib.lib().ganlab_attn_fwd_f32(_p(q), _p(k), _p(v), _p(o), _p(lse), n, dk, dv, l, s, _st()), 'attn_fwd')
-    return o, lse
-
-
-def k_attn_bwd(q, k, v, o, lse, go):
-    go = _c(go)
-    n, dk, dv, l, s = _attn_dims(q, k, v)
-    L = _lib.lib()
-    ws = _new(((L.ganlab_attn_bwd_workspace(n, l) + 3) // 4,), q)
-    gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    check(L.ganlab_attn_bwd_f32(_p(q), _p(k), _p(v), _p(o), _p(lse), _p(go), _p(gq), _p(gk), _p(gv), n, dk, dv, l, s,
-                                _p(ws), ws.numel() * 4, _st()), 'attn_bwd')
-    return gq, gk, gv
-
-
-class _Attention(Function):
-    """o = softmax_s(q^T k) applied to v, channel-major operands; saves q, k, v, o and the (N, L) log-sum-exp - never the map."""
-
-    @staticmethod
-    def forward(ctx, q, k, v):
-        q, k, v = _c(q, 'attention q'), _c(k, 'attention k'), _c(v, 'attention v')
-        o, lse = k_attn_fwd(q, k, v)
-        ctx.save_for_backward(q, k, v, o, lse)
-        return o
-
-    @staticmethod
-    def backward(ctx, go):
-        q, k, v, o, lse = ctx.saved_tensors
-        gq, gk, gv = _AttentionBwd.apply(go, q, k, v, o, lse)
-        return gq, gk, gv
-
-
-class _AttentionBwd(Function):
-    @staticmethod
-    def forward(ctx, go, q, k, v, o, lse):
-        return k_attn_bwd(q, k, v, o, lse, go)
-
-    @staticmethod
-    def backward(ctx, *gg):
-        raise NotImplementedError(_ATTN_SECOND_ORDER.format('attention'))
-
-
-def _pool_dims(x):
-    if x.dim() < 2 or x.shape[-1] % 2 or x.shape[-2] % 2:
-        raise ValueError(f'max_pool2x2: H and W must be even (got {tuple(x.shape)})')
-    h, w = x.shape[-2], x.shape[-1]
-    return x.numel() // (h * w), h, w
-
-
-def k_maxpool2x2(x):
-    x = _c(x, 'max_pool2x2 input')
-    planes, h, w = _pool_dims(x)
-    L = _lib.lib()
-    y = _new(tuple(x.shape[:-2]) + (h // 2, w // 2), x)
-    bits = torch.empty(L.ganlab_maxpool2x2_bits_bytes(planes, h, w), dtype=torch.uint8, device=x.device)
-    check(L.ganlab_maxpool2x2_f32(_p(x), _p(y), _p(bits), planes, h, w, _st()), 'maxpool2x2')
-    return y, bits
-
-
-def k_maxpool2x2_bwd(gy, bits, shape):
-    gy = _c(gy)
-    h, w = shape[-2], shape[-1]
-    gx = _new(tuple(shape), gy)
-    check(_lib.lib().ganlab_maxpool2x2_bwd_f32(_p(gy), _p(bits), _p(gx), gx.numel() // (h * w), h, w, _st()),
-          'maxpool2x2_bwd')
-    return gx
-
-
-class _MaxPool2x2(Function):
-    @staticmethod
-    def forward(ctx, x):
-        y, bits = k_maxpool2x2(x)
-        ctx.bits, ctx.shape = bits, tuple(x.shape)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        return _MaxPool2x2Bwd.apply(gy, ctx.bits, ctx.shape)
-
-
-class _MaxPool2x2Bwd(Function):
-    @staticmethod
-    def forward(ctx, gy, bits, shape):
-        return k_maxpool2x2_bwd(gy, bits, shape)
-
-    @staticmethod
-    def backward(ctx, gg):
-        raise NotImplementedError(_ATTN_SECOND_ORDER.format('max_pool2x2'))
-
-
-def k_gated_residual(x, y, gamma):
-    x, y, gamma = _c(x), _c(y), _c(gamma, 'gated_residual gamma')
-    assert x.shape == y.shape and gamma.numel() == 1
-    out = torch.empty_like(x)
-    check(_lib.lib().ganlab_gated_residual_f32(_p(x), _p(y), _p(gamma), _p(out), x.numel(), _st()), 'gated_residual')
-    return out
-
-
-def k_dot(a, b, sink=None):
-    a, b = _c(a), _c(b)
-    assert a.shape == b.shape
-    L = _lib.lib()
-    ws = _new(((L.ganlab_dot_workspace(a.numel()) + 3) // 4,), a)
-    out = _take(sink, (1,), a) if sink is not None else _new((1,), a)
-    check(L.ganlab_dot_f32(_p(a), _p(b), _p(out), a.numel(), _p(ws), ws.numel() * 4, _st()), 'dot')
-    return out
-
-
-class _GatedResidual(Function):
-    """out = x + gamma * y with ``gamma`` a one-element device tensor (the attention block's learned gate)."""
-
-    @staticmethod
-    def forward(ctx, x, y, gamma):
-        ctx.save_for_backward(y, gamma)
-        ctx.gamma_ref = gamma
-        return k_gated_residual(x, y, gamma)
-
-    @staticmethod
-    def backward(ctx, g):
-        y, gamma = ctx.saved_tensors
-        want_y = ctx.needs_input_grad[1]
-        want_g = ctx.needs_input_grad[2] and _want_param_grads()
-        _sink('ggamma', ctx.gamma_ref if want_g else None)
-        gy, gg = _GatedResidualBwd.apply(g, y, gamma, bool(want_y), bool(want_g))
-        if _sunk('ggamma'):
-            want_g = False
-        return (g if ctx.needs_input_grad[0] else None), (gy if want_y else None), \
-            (gg.view(gamma.shape) if want_g else None)
-
-
-class _GatedResidualBwd(Function):
-    """(dy, dgamma) = (gamma * g, <g, y>): the dot in fp64 partials added in a fixed order."""
-
-    @staticmethod
-    def forward(ctx, g, y, gamma, want_y, want_g):
-        g = _c(g)
-        gy = k_scale_dev(g, gamma, 1.0) if want_y else None
-        gg = k_dot(g, y, sink='ggamma') if want_g else None
-        return gy, gg
-
-    @staticmethod
-    def backward(ctx, *gg):
-        raise NotImplementedError(_ATTN_SECOND_ORDER.format('the gated residual'))
-
-
-def attention(q, k, v):
-    """SAGAN attention core on channel-major operands q (N, Dk, L...), k (N, Dk, S...), v (N, Dv, S...) -> (N, Dv, L...):
-    ``softmax_s(sum_d q[n,d,l] k[n,d,s])`` applied to ``v``, no ``1/sqrt(d)`` scale.  One fused kernel forward, three backward;
-    the (L, S) map is never stored.  Differentiable once."""
-    return _Attention.apply(q, k, v)
-
-
-def max_pool2x2(x):
-    """2x2 / stride-2 max pool over the last two dimensions (even sizes); ties go to the first of the four, as in ATen.
-    Differentiable once."""
-    return _MaxPool2x2.apply(x)
-
-
-def gated_residual(x, y, gamma):
-    """``x + gamma * y`` with a one-element device tensor ``gamma``.  Differentiable once."""
-    return _GatedResidual.apply(x, y, gamma)
 
 

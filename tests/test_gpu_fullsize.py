@@ -439,13 +439,7 @@ def test_learner_step_full_width_vs_oracle(res, b, capsys, tmp_path):
         # ---- the learner's own step ---------------------------------------------------------------------------------
         StyleAddNoise.honour_noise_in_training = True
         taken = [0]
-        take = ops._take
-
-        def counting(name, shape, like):
-            out = take(name, shape, like)
-            taken[0] += int(bool(ops._TAKEN.get(name)))
-            return out
-        ops._take = counting
+        before = ops.arena_takes()
         try:
             with _KernelCensus() as census:
                 L.set_requires_grad_disc(True)
@@ -458,7 +452,7 @@ def test_learner_step_full_width_vs_oracle(res, b, capsys, tmp_path):
                 gg = {k: v.detach().cpu().clone() for k, v in L.arena_g.views_of(L.arena_g.gflat).items()}
         finally:
             StyleAddNoise.honour_noise_in_training = False
-            ops._take = take
+            taken[0] = ops.arena_takes() - before
         torch.cuda.synchronize()
         t1 = time.time()
         new_g = {k: v.detach().cpu() for k, v in L.gen_model.state_dict().items()}

@@ -284,16 +284,9 @@ def test_direct_parameter_gradients_equal_the_accumulated_ones():
         rng.manual_seed(5)
         orig = ops.direct_param_grads
         taken = [0]
-        if direct:
-            take = ops._take
-
-            def counting(name, shape, like):
-                out = take(name, shape, like)
-                taken[0] += int(bool(ops._TAKEN.get(name)))
-                return out
-            ops._take = counting
-        else:
+        if not direct:
             ops.direct_param_grads = Off
+        before = ops.arena_takes()
         try:
             L.d_step(real, defer_update=True)
             gd = L.arena_d.gflat.clone()
@@ -301,8 +294,7 @@ def test_direct_parameter_gradients_equal_the_accumulated_ones():
             gg = L.arena_g.gflat.clone()
         finally:
             ops.direct_param_grads = orig
-            if direct:
-                ops._take = take
+            taken[0] = ops.arena_takes() - before
         torch.cuda.synchronize()
         n_params = len(L.arena_d.params) + len(L.arena_g.params)
         return gd, gg, L.arena_d.flat.clone(), L.arena_g.flat.clone(), taken[0], n_params
