@@ -213,23 +213,11 @@ def saved_config_fields(cfg):
 def reference_config_fields(config):
     """The config fields a reference-format checkpoint stores: ``diffaugment``, ``ada*``, ``swd_*``, ``msssim_*``, ``spectrum_*``, ``prdc_*``, ``fd_*``, ``kid_*``,
     ``ppl_*``, ``self_attention`` and ``cgan`` are this package's own and are left out while their feature is off, so the file is the reference's own."""
-    from . import frechet, kid, msssim, ppl, prdc, spectrum, swd
-    swd_off = not swd.wanted(getattr(config, 'gen_metrics', None))
-    msssim_off = not msssim.wanted(getattr(config, 'gen_metrics', None))
-    spectrum_off = not spectrum.wanted(getattr(config, 'gen_metrics', None))
-    prdc_off = not prdc.wanted(getattr(config, 'gen_metrics', None))
-    fd_off = not frechet.wanted(getattr(config, 'gen_metrics', None))
-    kid_off = not kid.wanted(getattr(config, 'gen_metrics', None))
-    ppl_off = not ppl.wanted(getattr(config, 'gen_metrics', None))
+    from . import validation
+    gen_metrics = getattr(config, 'gen_metrics', None)
+    off = tuple(s.name + '_' for s in validation.SCORERS if not s.module.wanted(gen_metrics))    # a set metric's fields: '<name>_*'
     return saved_config_fields({k: v for k, v in vars(config).items() if not (k == 'diffaugment' and v is None) and
-                                not (k in ('self_attention', 'cgan') and v is None) and
-                                not (swd_off and k.startswith('swd_')) and
-                                not (msssim_off and k.startswith('msssim_')) and
-                                not (spectrum_off and k.startswith('spectrum_')) and
-                                not (prdc_off and k.startswith('prdc_')) and
-                                not (fd_off and k.startswith('fd_')) and
-                                not (kid_off and k.startswith('kid_')) and
-                                not (ppl_off and k.startswith('ppl_'))})
+                                not (k in ('self_attention', 'cgan') and v is None) and not k.startswith(off)})
 
 
 def reference_checkpoint_dict(learner, g_names, d_names, extra=None):

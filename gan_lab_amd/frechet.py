@@ -10,26 +10,22 @@ common offset (images are not centred) then do not cancel catastrophically in ``
 ``eigh`` is what every FID implementation uses, and it runs (and is tested) without a GPU.  What the rows are is the caller's
 choice: the learners feed ``prdc.features`` (the image reduced by 2x2 means); a user with an embedding of their own feeds its rows.
 """
-import os
-
 import torch
 
 from . import ops, prdc
+from ._metric_common import check_rows, device_gate, host_only_error, wanted as _wanted
 
 MAX_DIM = ops.MOMENTS_MAX_DIM
 
 
 def wanted(metrics):
-    return any(isinstance(m, str) and m.casefold() == 'fd' for m in (metrics or ()))
+    return _wanted(metrics, 'fd')
 
 
 def validate_config(config):
     """Called when a learner is built: ``fd_res`` is checked whether or not the metric is requested, and 'fd' is refused among the
     critic's metrics (it compares image sets; the critic has no part in it).  Returns the resolution."""
-    try:
-        res = prdc.check_res(getattr(config, 'fd_res', 16), 'fd_res')
-    except ValueError as e:
-        raise ValueError(str(e).replace('prdc:', 'frechet:', 1)) from None
+    res = prdc.check_res(getattr(config, 'fd_res', 16), 'fd_res', prefix='frechet')
     if wanted(getattr(config, 'disc_metrics', None)):
         raise ValueError("config.disc_metrics lists 'fd': the Frechet distance is a generator metric (config.gen_metrics)")
     return res
@@ -66,11 +62,7 @@ class Frechet(object):
         if not isinstance(dim, int) or isinstance(dim, bool) or not 1 <= dim <= MAX_DIM:
             raise ValueError(f'frechet: dim must be an integer in [1, {MAX_DIM}], got {dim!r}')
         self.dim = dim
-        self.device = torch.device(device)
-        # GANLAB_HOST_LOGIC_ONLY=1 (CPU tests of the host logic): feeds are checked and counted, nothing is computed
-        self._host_only = self.device.type != 'cuda' and os.environ.get('GANLAB_HOST_LOGIC_ONLY') == '1'
-        if self.device.type != 'cuda' and not self._host_only:
-            raise TypeError(f'frechet: the metric runs on the GPU only (device={device!r}); the HIP path has no CPU fallback')
+        self.device, self._host_only = device_gate(device, 'frechet')
         if pivot is not None and (not isinstance(pivot, torch.Tensor) or tuple(pivot.shape) != (dim,) or
                                   pivot.dtype != torch.float32):
             raise ValueError(f'frechet: pivot must be a ({dim},) float32 tensor, got {tuple(getattr(pivot, "shape", ()))} '
@@ -98,9 +90,7 @@ class Frechet(object):
         self._feed('fake', rows)
 
     def _feed(self, which, rows):
-        if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[1] != self.dim or rows.dtype != torch.float32:
-            raise ValueError(f'frechet: a feed must be an (n, {self.dim}) float32 matrix, got '
-                             f'{tuple(getattr(rows, "shape", ()))} {getattr(rows, "dtype", type(rows).__name__)}')
+        check_rows(rows, self.dim, 'frechet')
         n = rows.shape[0]
         if n == 0:
             return
@@ -115,7 +105,7 @@ class Frechet(object):
         if which not in self._n:
             raise ValueError(f"frechet: which must be 'real' or 'fake', got {which!r}")
         if self._host_only:
-            raise RuntimeError('frechet: GANLAB_HOST_LOGIC_ONLY=1 checks the host logic only; the metric itself needs the GPU')
+            raise host_only_error('frechet')
 
     def raw(self, which):
         """(n, pivot fp32 (dim,), sum float64 (dim,), gram float64 (dim, dim)) of the 'real' or 'fake' set: copies."""

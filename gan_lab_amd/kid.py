@@ -10,17 +10,16 @@ rows of each set, the mmd2 of each pair of blocks, their mean and standard devia
 ``coef0 = 1`` on Inception pool features this is KID proper; what the rows are is the caller's choice (the learners feed
 ``prdc.features``, the image reduced by 2x2 means).
 """
-import os
-
 import torch
 
 from . import ops, prdc
+from ._metric_common import check_rows, device_gate, host_only_error, wanted as _wanted
 
 MIN_BLOCK = 2
 
 
 def wanted(metrics):
-    return any(isinstance(m, str) and m.casefold() == 'kid' for m in (metrics or ()))
+    return _wanted(metrics, 'kid')
 
 
 def check_block(block, what='block'):
@@ -32,10 +31,7 @@ def check_block(block, what='block'):
 def validate_config(config):
     """Called when a learner is built: ``kid_res`` / ``kid_block`` are checked whether or not the metric is requested, and 'kid'
     is refused among the critic's metrics (it compares image sets; the critic has no part in it).  Returns (res, block)."""
-    try:
-        res = prdc.check_res(getattr(config, 'kid_res', 32), 'kid_res')
-    except ValueError as e:
-        raise ValueError(str(e).replace('prdc:', 'kid:', 1)) from None
+    res = prdc.check_res(getattr(config, 'kid_res', 32), 'kid_res', prefix='kid')
     block = check_block(getattr(config, 'kid_block', 1000), 'kid_block')
     if wanted(getattr(config, 'disc_metrics', None)):
         raise ValueError("config.disc_metrics lists 'kid': the Kernel Inception Distance is a generator metric "
@@ -66,11 +62,7 @@ class KID(object):
         self.coef0 = float(coef0)
         if self.gamma != self.gamma or self.coef0 != self.coef0:
             raise ValueError(f'kid: gamma and coef0 must be numbers, got {gamma!r} and {coef0!r}')
-        self.device = torch.device(device)
-        # GANLAB_HOST_LOGIC_ONLY=1 (CPU tests of the host logic): feeds are checked and counted, nothing is computed
-        self._host_only = self.device.type != 'cuda' and os.environ.get('GANLAB_HOST_LOGIC_ONLY') == '1'
-        if self.device.type != 'cuda' and not self._host_only:
-            raise TypeError(f'kid: the metric runs on the GPU only (device={device!r}); the HIP path has no CPU fallback')
+        self.device, self._host_only = device_gate(device, 'kid')
         self._fed = {'real': 0, 'fake': 0}
         self._done = False
         if self._host_only:
@@ -98,9 +90,7 @@ class KID(object):
         self._feed('fake', rows)
 
     def _feed(self, which, rows):
-        if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[1] != self.dim or rows.dtype != torch.float32:
-            raise ValueError(f'kid: a feed must be an (n, {self.dim}) float32 matrix, got '
-                             f'{tuple(getattr(rows, "shape", ()))} {getattr(rows, "dtype", type(rows).__name__)}')
+        check_rows(rows, self.dim, 'kid')
         n, fed = rows.shape[0], self._fed[which]
         if fed + n > self.n[which]:
             raise ValueError(f'kid: the {which} set was declared with {self.n[which]} rows; this feed of {n} would make '
@@ -125,7 +115,7 @@ class KID(object):
             if self._fed[which] != n:
                 raise ValueError(f'kid: {n} {which} rows were declared, {self._fed[which]} were fed')
         if self._host_only:
-            raise RuntimeError('kid: GANLAB_HOST_LOGIC_ONLY=1 checks the host logic only; the metric itself needs the GPU')
+            raise host_only_error('kid')
         if self._done:
             return
         names = ('real_real', 'fake_fake', 'real_fake')

@@ -12,11 +12,11 @@ quantised to uint8, so the dynamic range L of C1 = (0.01 L)^2, C2 = (0.03 L)^2 i
 Nothing here is random and nothing depends on how the set was split into feeds: results are bitwise reproducible.
 """
 import math
-import os
 
 import torch
 
 from . import ops
+from ._metric_common import device_gate, host_only_error, wanted as _wanted
 
 MIN_RES = 16                         # five levels need R / 16 >= 1
 LEVELS = ops.MSSSIM_LEVELS
@@ -49,7 +49,7 @@ def validate_config(config):
 
 
 def wanted(metrics):
-    return any(isinstance(m, str) and m.casefold() == 'msssim' for m in (metrics or ()))
+    return _wanted(metrics, 'msssim')
 
 
 def constants(data_range):
@@ -107,11 +107,7 @@ class MultiScaleSSIM(object):
         self.n_images, self.n_pairs = n_images, n_images // 2
         self.data_range = check_options(data_range)
         self.c1, self.c2 = constants(self.data_range)
-        self.device = torch.device(device)
-        # GANLAB_HOST_LOGIC_ONLY=1 (CPU tests of the host logic): feeds are checked and counted, nothing is computed
-        self._host_only = self.device.type != 'cuda' and os.environ.get('GANLAB_HOST_LOGIC_ONLY') == '1'
-        if self.device.type != 'cuda' and not self._host_only:
-            raise TypeError(f'msssim: the metric runs on the GPU only (device={device!r}); the HIP path has no CPU fallback')
+        self.device, self._host_only = device_gate(device, 'msssim')
         self._fed = 0
         if self._host_only:
             return
@@ -153,7 +149,7 @@ class MultiScaleSSIM(object):
         if self._fed != self.n_images:
             raise ValueError(f'msssim: {self.n_images} images were declared, {self._fed} were fed')
         if self._host_only:
-            raise RuntimeError('msssim: GANLAB_HOST_LOGIC_ONLY=1 checks the host logic only; the metric itself needs the GPU')
+            raise host_only_error('msssim')
         ops.msssim_finish(self._ws, self.n_pairs, self.res, self._table, self._values, self._out)
         host = self._out.cpu().tolist()               # the evaluation's one host read
         return {'msssim': host[0], 'pairs': self.n_pairs, 'per_level': [host[1:LEVELS], host[LEVELS]]}

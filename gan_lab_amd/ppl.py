@@ -23,6 +23,7 @@ stream (gan_lab_amd/rng.py) is not touched.
 import torch
 
 from . import ops
+from ._metric_common import wanted as _wanted
 
 SPACES = ('z', 'w')
 SAMPLINGS = ('full', 'end')
@@ -38,7 +39,7 @@ def _substream(seed, k):
 
 
 def wanted(metrics):
-    return any(isinstance(m, str) and m.casefold() == 'ppl' for m in (metrics or ()))
+    return _wanted(metrics, 'ppl')
 
 
 def check_samples(n, what='n_samples'):

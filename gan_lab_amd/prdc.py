@@ -16,11 +16,10 @@ generated row included; no N x M matrix is ever stored.  What the rows are is th
 learners' default, the image itself reduced by 2x2 means - at 32 / 64 pixels a reasonable feature row (Naeem et al. find the
 numbers useful away from ImageNet embeddings) - and a user with an embedding of their own feeds its rows.
 """
-import os
-
 import torch
 
 from . import ops
+from ._metric_common import check_rows, device_gate, host_only_error, wanted as _wanted
 
 MAX_K = ops.PRDC_MAX_K
 MIN_RES = 4
@@ -32,9 +31,9 @@ def check_k(k, what='k'):
     return k
 
 
-def check_res(res, what='res'):
+def check_res(res, what='res', prefix='prdc'):
     if not isinstance(res, int) or isinstance(res, bool) or res < MIN_RES or res & (res - 1):
-        raise ValueError(f'prdc: {what} must be a power of two >= {MIN_RES}, got {res!r}')
+        raise ValueError(f'{prefix}: {what} must be a power of two >= {MIN_RES}, got {res!r}')
     return res
 
 
@@ -45,7 +44,7 @@ def _positive_int(v, name):
 
 
 def wanted(metrics):
-    return any(isinstance(m, str) and m.casefold() == 'prdc' for m in (metrics or ()))
+    return _wanted(metrics, 'prdc')
 
 
 def validate_config(config):
@@ -92,11 +91,7 @@ class PRDC(object):
             if self.k >= n:
                 raise ValueError(f'prdc: k must be below the size of both sets (k = {self.k}, n_{which} = {n}): the k-th '
                                  f'neighbour of a row is sought among the other rows of its set')
-        self.device = torch.device(device)
-        # GANLAB_HOST_LOGIC_ONLY=1 (CPU tests of the host logic): feeds are checked and counted, nothing is computed
-        self._host_only = self.device.type != 'cuda' and os.environ.get('GANLAB_HOST_LOGIC_ONLY') == '1'
-        if self.device.type != 'cuda' and not self._host_only:
-            raise TypeError(f'prdc: the metric runs on the GPU only (device={device!r}); the HIP path has no CPU fallback')
+        self.device, self._host_only = device_gate(device, 'prdc')
         self._fed = {'real': 0, 'fake': 0}
         self._done = False
         if self._host_only:
@@ -124,9 +119,7 @@ class PRDC(object):
         self._feed('fake', rows)
 
     def _feed(self, which, rows):
-        if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[1] != self.dim or rows.dtype != torch.float32:
-            raise ValueError(f'prdc: a feed must be an (n, {self.dim}) float32 matrix, got '
-                             f'{tuple(getattr(rows, "shape", ()))} {getattr(rows, "dtype", type(rows).__name__)}')
+        check_rows(rows, self.dim, 'prdc')
         n, fed = rows.shape[0], self._fed[which]
         if fed + n > self.n[which]:
             raise ValueError(f'prdc: the {which} set was declared with {self.n[which]} rows; this feed of {n} would make '
@@ -146,7 +139,7 @@ class PRDC(object):
             if self._fed[which] != n:
                 raise ValueError(f'prdc: {n} {which} rows were declared, {self._fed[which]} were fed')
         if self._host_only:
-            raise RuntimeError('prdc: GANLAB_HOST_LOGIC_ONLY=1 checks the host logic only; the metric itself needs the GPU')
+            raise host_only_error('prdc')
         if self._done:
             return
         for w in ('real', 'fake'):

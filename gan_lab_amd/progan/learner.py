@@ -22,7 +22,7 @@ import warnings
 import torch
 from torch import nn
 
-from .. import frechet, kid, msssim, ops, parallel, ppl, prdc, rng, spectrum, swd
+from .. import ops, parallel, rng, validation
 from .._int import LearnerConfigCopy
 from ..optim import EwmaTracker, ParamArena
 from ..resnetgan.learner import GANLearner
@@ -86,7 +86,9 @@ class ProGANLearner(GANLearner):
 
     def _init_progressive(self, config, learner_name):
         """Common constructor body of ProGANLearner / StyleGANLearner (progan/learner.py:104-206)."""
-        ppl.validate_config(config)      # the path length's options ('ppl' in config.gen_metrics; ppl.py), used by compute_metrics
+        for s in validation.SCORERS:     # the options of the set metrics of progressive learners alone ('ppl'), used by compute_metrics
+            if s.progressive_only:
+                s.module.validate_config(config)
         self.config = LearnerConfigCopy(config, learner_name, self._nonredefinable, REDEFINABLE_FROM_LEARNER_ATTRS)
         self._is_data_configed = False
         self._update_data_config(raise_exception=False)
@@ -489,11 +491,7 @@ class ProGANLearner(GANLearner):
                                 ((itr + 1) % c.num_iters_valid == 0 or itr == 0):     # (:921-928)
                             vals = self.compute_metrics(metrics=c.gen_metrics, metrics_type='Generator',
                                                         z_valid_dl=z_valid_dl,
-                                                        valid_dl=valid_dl if swd.wanted(c.gen_metrics) or
-                                                        msssim.wanted(c.gen_metrics) or
-                                                        spectrum.wanted(c.gen_metrics) or
-                                                        prdc.wanted(c.gen_metrics) or frechet.wanted(c.gen_metrics) or
-                                                        kid.wanted(c.gen_metrics) else None)
+                                                        valid_dl=valid_dl if validation.uses_reals(c.gen_metrics) else None)
                             if parallel.rank() == 0:
                                 print('|\n', 'Generator Validation Metrics:\n', *vals)
                     if num_gen_iters == 0:
@@ -552,50 +550,19 @@ class ProGANLearner(GANLearner):
         every metric is ``sum over the (batch, n_batches) table / len(z_valid_dl.dataset)``, i.e. 'fake realness' /
         'real realness' are mean logits and the two losses are batch-size-weighted means of per-batch losses
         (the gradient penalty is not included, :393-395).  Networks run in eval mode on the training device
-        (``config.metrics_dev`` is ignored: there is no CPU path) and return to train mode.  Returns the
-        reference's list of formatted lines; the raw numbers are kept in ``self.last_metrics``."""
+        (``config.metrics_dev`` is ignored: there is no CPU path) and return to train mode.  The set metrics
+        ('swd' ... 'ppl') are the scorers of validation.py: they score the generator this method evaluates and the
+        faded-in reals, in whole batches, and report after the table metrics.  Returns the reference's list of
+        formatted lines; the raw numbers are kept in ``self.last_metrics``."""
         c = self.config
         metrics_type = metrics_type.casefold()
         if metrics_type not in ('generator', 'critic', 'discriminator',):
             raise Exception('Invalid metrics_type. Only "generator", "critic", or "discriminator" are accepted.')
         metrics = [m.casefold() for m in metrics]
         want_grid = 'image grid' in metrics and metrics_type == 'generator'
-        want_swd = 'swd' in metrics
-        if want_swd and metrics_type != 'generator':
-            raise ValueError("'swd' is a generator metric: it compares the generated validation images with the validation "
-                             "reals and cannot be listed among the critic's metrics (config.disc_metrics)")
-        if want_swd and valid_dl is None:
-            raise ValueError("'swd' needs the validation reals: pass valid_dl (train(train_dl, valid_dl, z_valid_dl))")
-        want_ms = 'msssim' in metrics
-        if want_ms and metrics_type != 'generator':
-            raise ValueError("'msssim' is a generator metric: it compares generated validation images with each other and "
-                             "cannot be listed among the critic's metrics (config.disc_metrics)")
-        if want_ms and self.batch_size % 2:
-            raise ValueError(f"'msssim' scores adjacent pairs of a validation minibatch: config.batch_size must be even at "
-                             f"this resolution, got {self.batch_size}")
-        want_sp = 'spectrum' in metrics
-        if want_sp and metrics_type != 'generator':
-            raise ValueError("'spectrum' is a generator metric: it compares the generated validation images with the validation "
-                             "reals and cannot be listed among the critic's metrics (config.disc_metrics)")
-        if want_sp and valid_dl is None:
-            raise ValueError("'spectrum' needs the validation reals: pass valid_dl (train(train_dl, valid_dl, z_valid_dl))")
-        want_pr = 'prdc' in metrics
-        if want_pr and metrics_type != 'generator':
-            raise ValueError("'prdc' is a generator metric: it compares the generated validation images with the validation "
-                             "reals and cannot be listed among the critic's metrics (config.disc_metrics)")
-        if want_pr and valid_dl is None:
-            raise ValueError("'prdc' needs the validation reals: pass valid_dl (train(train_dl, valid_dl, z_valid_dl))")
-        want_fd, want_kid = 'fd' in metrics, 'kid' in metrics
-        for name, want in (('fd', want_fd), ('kid', want_kid)):
-            if want and metrics_type != 'generator':
-                raise ValueError(f"'{name}' is a generator metric: it compares the generated validation images with the "
-                                 f"validation reals and cannot be listed among the critic's metrics (config.disc_metrics)")
-            if want and valid_dl is None:
-                raise ValueError(f"'{name}' needs the validation reals: pass valid_dl (train(train_dl, valid_dl, z_valid_dl))")
-        want_ppl = 'ppl' in metrics
-        if want_ppl and metrics_type != 'generator':
-            raise ValueError("'ppl' is a generator metric: it measures the generator's latent space and cannot be listed among "
-                             "the critic's metrics (config.disc_metrics)")
+        active = [s for s in validation.SCORERS if s.name in metrics]       # the set metrics asked for (validation.py)
+        for s in active:
+            s.refuse(self, metrics_type, valid_dl)
         if want_grid and (self.ds_mean is None or self.data_config is None):
             self._update_data_config(raise_exception=True)
         self.disc_model.eval()
@@ -613,63 +580,30 @@ class ProGANLearner(GANLearner):
                                                    replacement=False)
                 self._grid_fill = 0
             self._img_grid_constructed = False
-            table = {m: torch.zeros(self.batch_size, n_batches, device=c.dev) for m in metrics
-                     if m not in ('swd', 'msssim', 'spectrum', 'prdc', 'fd', 'kid', 'ppl')}
-            swd_eval, swd_left = self._swd_begin(n_z, valid_dl) if want_swd else (None, 0)
-            ms_fake, ms_real, ms_fake_left, ms_real_left = self._msssim_begin(n_z, valid_dl) if want_ms else (None, None, 0, 0)
-            sp_fake, sp_real, sp_left = self._spectrum_begin(n_z, valid_dl) if want_sp else (None, None, 0)
-            pr_eval, pr_left = self._prdc_begin(n_z, valid_dl) if want_pr else (None, 0)
-            fd_eval, fd_left = self._fd_begin(n_z, valid_dl) if want_fd else (None, 0)
-            kid_eval, kid_left = self._kid_begin(n_z, valid_dl) if want_kid else (None, 0)
+            table = {m: torch.zeros(self.batch_size, n_batches, device=c.dev) for m in metrics if m not in validation.NAMES}
+            scorers = [s(self, int(self.gen_model.curr_res), n_z, valid_dl) for s in active]
+            feeding = validation.in_feed_order(scorers)
             for n, zbatch in enumerate(z_valid_dl):
                 zb = zbatch[0].to(c.dev).float()
                 gen_labels = zbatch[1].cpu() if len(zbatch) > 1 else None
                 k = len(zb)
                 xgen = self.gen_model(zb)
-                ms_fake_now = ms_fake_left > 0 and k == self.batch_size
-                ms_real_now = ms_real_left > 0 and k == self.batch_size
-                # 'swd', 'spectrum', 'prdc', 'fd' and 'kid' score the same two sets of equal size
-                both_left = max(swd_left, sp_left, pr_left, fd_left, kid_left)
-                if both_left > 0 or ms_fake_now or ms_real_now:
-                    # whole batches only, so that both sets hold the same images count; the generator evaluated is the one
-                    # this method evaluates, the reals follow its fade-in.  'swd', 'msssim' and 'spectrum' share the scored
-                    # fakes (one extra forward, not three) and the faded-in reals
-                    xb = xr = None
-                    if both_left > 0 or ms_real_now:
+                fake_for = [s for s in feeding if s.wants_fake(k)]
+                real_for = [s for s in feeding if s.wants_real(k)]
+                if fake_for or real_for:
+                    # the generator evaluated is the one this method evaluates, the reals follow its fade-in; all the metrics
+                    # share the scored fakes (one extra forward) and the faded-in reals
+                    xr = None
+                    if real_for:
                         xb = next(valid_iter)[0].to(c.dev).float()
-                        if k != len(xb) or (both_left > 0 and k > both_left):
-                            which = "'swd'" if swd_left > 0 else "'spectrum'" if sp_left > 0 else \
-                                "'prdc'" if pr_left > 0 else "'fd'" if fd_left > 0 else "'kid'" if kid_left > 0 else "'msssim'"
-                            raise ValueError(f"{which}: validation latents and reals must come in equal batches (got {k} and "
-                                             f"{len(xb)} with {both_left if both_left > 0 else ms_real_left} images to go)")
+                        first = real_for[0]
+                        if k != len(xb) or k > first.real_left:
+                            raise ValueError(f"'{first.name}': validation latents and reals must come in equal batches (got {k} and "
+                                             f"{len(xb)} with {first.real_left} images to go)")
                         xr = self.fade_in_real(xb)
-                    scored = self._swd_fakes(zb, xgen) if both_left > 0 or ms_fake_now else None
-                    if swd_left > 0:
-                        swd_eval.feed_fake(scored)
-                        swd_eval.feed_real(xr)
-                        swd_left -= k
-                    if sp_left > 0:
-                        sp_fake.feed(scored)
-                        sp_real.feed(xr)
-                        sp_left -= k
-                    if pr_left > 0:
-                        pr_eval.feed_fake(prdc.features(scored, c.prdc_res))
-                        pr_eval.feed_real(prdc.features(xr, c.prdc_res))
-                        pr_left -= k
-                    if fd_left > 0:
-                        fd_eval.feed_fake(prdc.features(scored, c.fd_res))
-                        fd_eval.feed_real(prdc.features(xr, c.fd_res))
-                        fd_left -= k
-                    if kid_left > 0:
-                        kid_eval.feed_fake(prdc.features(scored, c.kid_res))
-                        kid_eval.feed_real(prdc.features(xr, c.kid_res))
-                        kid_left -= k
-                    if ms_fake_now:
-                        ms_fake.feed(scored)
-                        ms_fake_left -= k
-                    if ms_real_now:
-                        ms_real.feed(xr)
-                        ms_real_left -= k
+                    scored = self._scored_fakes(zb, xgen) if fake_for else None
+                    for s in feeding:
+                        s.feed(k, scored, xr)
                 y_fake = None
                 if 'fake realness' in metrics:
                     y_fake = self.disc_model(xgen)
@@ -702,59 +636,22 @@ class ProGANLearner(GANLearner):
             else:
                 self.disc_metrics_num += 1
             vals = {m: float(t.sum() / n_z) for m, t in table.items() if m != 'image grid'}
-            swd_lines = []
-            if want_swd:
-                vals['swd'], swd_lines = self._swd_finish(swd_eval)
-            if want_ms:
-                vals['msssim'], ms_lines = self._msssim_finish(ms_fake, ms_real)
-                swd_lines = swd_lines + ms_lines
-            if want_sp:
-                vals['spectrum'], sp_lines = self._spectrum_finish(sp_fake, sp_real)
-                swd_lines = swd_lines + sp_lines
-            if want_pr:
-                vals['prdc'] = pr_eval.result()
-                swd_lines = swd_lines + [(name, vals['prdc'][name]) for name in ('precision', 'recall', 'density', 'coverage')]
-            if want_fd:
-                vals['fd'] = fd_eval.result()
-                swd_lines = swd_lines + [('fd', vals['fd']['fd'])]
-            if want_kid:
-                vals['kid'] = kid_eval.result()
-                swd_lines = swd_lines + [('kid', vals['kid']['kid'])]
-            if want_ppl:
-                vals['ppl'], ppl_lines = self._ppl_evaluate()
-                swd_lines = swd_lines + ppl_lines
+            set_lines = []
+            for s in scorers:
+                vals[s.name], lines_of = s.finish()
+                set_lines += lines_of
         finally:
             self.gen_model.train()
             self.disc_model.train()
         self.last_metrics[metrics_type] = vals
-        names = metrics + [name for name, _ in swd_lines]
+        names = metrics + [name for name, _ in set_lines]
         width = '%-' + str(max(len(m) for m in names) + 3) + 's'
         return ['    ' + (width % (m + ':')) + '%.4g' % vals[m] + '\n' for m in metrics
-                if m not in ('image grid', 'swd', 'msssim', 'spectrum', 'prdc', 'fd', 'kid', 'ppl')] + \
-            ['    ' + (width % (name + ':')) + (v if isinstance(v, str) else '%.4g' % v) + '\n' for name, v in swd_lines]
+                if m != 'image grid' and m not in validation.NAMES] + \
+            ['    ' + (width % (name + ':')) + (v if isinstance(v, str) else '%.4g' % v) + '\n' for name, v in set_lines]
 
-    def _swd_begin(self, n_z, valid_dl):
-        """The evaluation object of this resolution (buffers are kept across validation points of one resolution) and the
-        number of images per set: min(latents, reals) truncated to whole batches.  Below 16x16 the pyramid has no level:
-        (None, 0)."""
-        c = self.config
-        res = int(self.gen_model.curr_res)
-        if res < swd.MIN_RES:
-            return None, 0
-        n_use = min(n_z, len(valid_dl.dataset)) // self.batch_size * self.batch_size
-        if n_use < 1:
-            raise ValueError(f"'swd' needs at least one whole batch of {self.batch_size} validation latents and reals (got "
-                             f"{n_z} and {len(valid_dl.dataset)})")
-        key = (res, n_use)
-        if getattr(self, '_swd_eval', None) is None or self._swd_eval[0] != key:
-            self._swd_eval = (key, swd.SlicedWasserstein(res, n_use, nhoods_per_image=c.swd_nhoods,
-                                                         dir_repeats=c.swd_dir_repeats,
-                                                         dirs_per_repeat=c.swd_dirs_per_repeat, seed=c.swd_seed, device=c.dev))
-        self._swd_eval[1].reset()
-        return self._swd_eval[1], n_use
-
-    def _swd_fakes(self, zb, xgen):
-        """The images SWD, MS-SSIM and the power spectrum score for the latents ``zb``: the time-averaged generator's when ``use_ewma_gen`` is on (the
+    def _scored_fakes(self, zb, xgen):
+        """The images the set metrics score for the latents ``zb``: the time-averaged generator's when ``use_ewma_gen`` is on (the
         samples a user would draw), else ``xgen`` of the snapshot generator.  The extra forward's per-layer noise is drawn
         at the process stream's position, which is then put back: the metric leaves the training stream where it was."""
         if not self.config.use_ewma_gen:
@@ -764,143 +661,6 @@ class ProGANLearner(GANLearner):
             return self.gen_model_lagged(zb)
         finally:
             rng._STATE['offset'] = offset
-
-    def _ppl_evaluate(self):
-        """(the dict kept in last_metrics, [(line name, value)]): ``ppl.generator_path_length`` of the generator this method
-        scores - the time-averaged one when ``use_ewma_gen`` is on - over ``config.ppl_samples`` pairs in batches of the current
-        batch size.  It needs no validation data and leaves the training stream where it was."""
-        c = self.config
-        samples, space, sampling, epsilon, seed = ppl.validate_config(c)
-        if self.gen_model.fade_in_phase:
-            return {'ppl': float('nan'), 'space': space}, \
-                [('ppl', 'nan (not available while a resolution fades in: the image then blends two resolutions)')]
-        out = ppl.generator_path_length(self, samples, space, sampling=sampling, epsilon=epsilon, batch=self.batch_size, seed=seed)
-        out['space'] = space
-        return out, [('ppl', out['ppl'])]
-
-    def _swd_finish(self, swd_eval):
-        """(the dict kept in last_metrics, [(line name, value)])."""
-        if swd_eval is None:
-            res = int(self.gen_model.curr_res)
-            return {'levels': [], 'swd': [], 'mean': float('nan')}, \
-                [('swd', f'nan (the pyramid starts at {swd.MIN_RES}x{swd.MIN_RES}; the current resolution is {res}x{res})')]
-        out = swd_eval.result()
-        return out, [(f'swd {r}x{r}', v) for r, v in zip(out['levels'], out['swd'])] + [('swd mean', out['mean'])]
-
-    def _msssim_begin(self, n_z, valid_dl):
-        """(evaluation of the fakes, evaluation of the reals or None, images to feed to each) at this resolution; buffers are
-        kept across validation points of one resolution.  Whole batches only (a batch is an even number of images, so pairs
-        never straddle batches).  Below 16x16 there is no fifth level: (None, None, 0, 0)."""
-        c = self.config
-        res = int(self.gen_model.curr_res)
-        if res < msssim.MIN_RES:
-            return None, None, 0, 0
-        bs = self.batch_size
-        n_fake = n_z // bs * bs
-        if n_fake < 1:
-            raise ValueError(f"'msssim' needs at least one whole batch of {bs} validation latents (got {n_z})")
-        n_real = min(n_z, len(valid_dl.dataset)) // bs * bs if valid_dl is not None else 0
-        key = (res, n_fake, n_real)
-        if getattr(self, '_msssim_eval', None) is None or self._msssim_eval[0] != key:
-            make = lambda n: msssim.MultiScaleSSIM(res, n, data_range=c.msssim_range, device=c.dev)  # noqa: E731
-            self._msssim_eval = (key, make(n_fake), make(n_real) if n_real else None)
-        _, fake, real = self._msssim_eval
-        fake.reset()
-        if real is not None:
-            real.reset()
-        return fake, real, n_fake, n_real
-
-    def _msssim_finish(self, fake, real):
-        """(the dict kept in last_metrics, [(line name, value)]).  'msssim real' scores the faded-in validation reals: the
-        number to compare 'msssim fake' against."""
-        if fake is None:
-            res = int(self.gen_model.curr_res)
-            return {'msssim': float('nan'), 'pairs': 0, 'per_level': [[], float('nan')]}, \
-                [('msssim', f'nan (five levels need {msssim.MIN_RES}x{msssim.MIN_RES}; the current resolution is {res}x{res})')]
-        out = fake.result()
-        lines = [('msssim fake', out['msssim'])]
-        if real is not None:
-            out['real'] = real.result()
-            lines.append(('msssim real', out['real']['msssim']))
-        return out, lines
-
-    def _spectrum_begin(self, n_z, valid_dl):
-        """(evaluation of the fakes, evaluation of the reals, images per set) at this resolution: min(latents, reals) truncated to
-        whole batches, as SWD counts them; buffers are kept across validation points of one resolution.  Outside
-        [16, 1024] the kernels have no transform: (None, None, 0)."""
-        c = self.config
-        res = int(self.gen_model.curr_res)
-        if res < spectrum.MIN_RES or res > spectrum.MAX_RES:
-            return None, None, 0
-        n_use = min(n_z, len(valid_dl.dataset)) // self.batch_size * self.batch_size
-        if n_use < 1:
-            raise ValueError(f"'spectrum' needs at least one whole batch of {self.batch_size} validation latents and reals (got "
-                             f"{n_z} and {len(valid_dl.dataset)})")
-        key = (res, n_use)
-        if getattr(self, '_spectrum_eval', None) is None or self._spectrum_eval[0] != key:
-            make = lambda: spectrum.PowerSpectrum(res, n_use, window=c.spectrum_window, device=c.dev)  # noqa: E731
-            self._spectrum_eval = (key, make(), make())
-        _, fake, real = self._spectrum_eval
-        fake.reset()
-        real.reset()
-        return fake, real, n_use
-
-    def _prdc_begin(self, n_z, valid_dl):
-        """(the evaluation of this resolution, images per set): min(latents, reals) truncated to whole batches, as SWD counts
-        them; buffers are kept across validation points of one resolution.  The rows are the images reduced by 2x2 means to
-        at most ``config.prdc_res`` pixels (prdc.features)."""
-        c = self.config
-        res = int(self.gen_model.curr_res)
-        n_use = min(n_z, len(valid_dl.dataset)) // self.batch_size * self.batch_size
-        if n_use < 1:
-            raise ValueError(f"'prdc' needs at least one whole batch of {self.batch_size} validation latents and reals (got "
-                             f"{n_z} and {len(valid_dl.dataset)})")
-        key = (res, n_use, c.prdc_k, c.prdc_res)
-        if getattr(self, '_prdc_eval', None) is None or self._prdc_eval[0] != key:
-            self._prdc_eval = (key, prdc.PRDC(prdc.feature_dim(3, res, c.prdc_res), n_use, n_use, k=c.prdc_k, device=c.dev))
-        self._prdc_eval[1].reset()
-        return self._prdc_eval[1], n_use
-
-    def _fd_begin(self, n_z, valid_dl):
-        """(the Frechet evaluation of this resolution, images per set), counted as ``_prdc_begin`` counts them; the rows are the
-        images reduced by 2x2 means to at most ``config.fd_res`` pixels (prdc.features)."""
-        c = self.config
-        res = int(self.gen_model.curr_res)
-        n_use = min(n_z, len(valid_dl.dataset)) // self.batch_size * self.batch_size
-        if n_use < 1:
-            raise ValueError(f"'fd' needs at least one whole batch of {self.batch_size} validation latents and reals (got "
-                             f"{n_z} and {len(valid_dl.dataset)})")
-        key = (res, c.fd_res)
-        if getattr(self, '_fd_eval', None) is None or self._fd_eval[0] != key:
-            self._fd_eval = (key, frechet.Frechet(prdc.feature_dim(3, res, c.fd_res), device=c.dev))
-        self._fd_eval[1].reset()
-        return self._fd_eval[1], n_use
-
-    def _kid_begin(self, n_z, valid_dl):
-        """(the KID evaluation of this resolution, images per set), counted as ``_prdc_begin`` counts them; the rows are the
-        images reduced by 2x2 means to at most ``config.kid_res`` pixels (prdc.features)."""
-        c = self.config
-        res = int(self.gen_model.curr_res)
-        n_use = min(n_z, len(valid_dl.dataset)) // self.batch_size * self.batch_size
-        if n_use < 1:
-            raise ValueError(f"'kid' needs at least one whole batch of {self.batch_size} validation latents and reals (got "
-                             f"{n_z} and {len(valid_dl.dataset)})")
-        key = (res, n_use, c.kid_res, c.kid_block)
-        if getattr(self, '_kid_eval', None) is None or self._kid_eval[0] != key:
-            self._kid_eval = (key, kid.KID(prdc.feature_dim(3, res, c.kid_res), n_use, n_use, block=c.kid_block, device=c.dev))
-        self._kid_eval[1].reset()
-        return self._kid_eval[1], n_use
-
-    def _spectrum_finish(self, fake, real):
-        """(the dict kept in last_metrics: both profiles in dB, for plotting, and the two distances; [(line name, value)])."""
-        if fake is None:
-            res = int(self.gen_model.curr_res)
-            nan = float('nan')
-            return {'spectrum': nan, 'hf': nan, 'fake_db': [], 'real_db': [], 'images': 0}, \
-                [('spectrum', f'nan (the transform covers {spectrum.MIN_RES}x{spectrum.MIN_RES} to '
-                              f'{spectrum.MAX_RES}x{spectrum.MAX_RES}; the current resolution is {res}x{res})')]
-        out = spectrum.distance(fake, real)
-        return out, [('spectrum', out['spectrum']), ('spectrum hf', out['hf'])]
 
     def _collect_grid_inputs(self, zb, gen_labels, n):
         """Pick the img_grid_sz^2 randomly chosen validation latents (fixed across calls, :311-330)."""

@@ -71,22 +71,13 @@ class GANLearner(object):
         from .. import ada
         self.ada = ada.from_config(config)
         self.critic_aug = self.diffaug if self.diffaug is not None else self.ada
-        # the sliced Wasserstein metric's options ('swd' in config.gen_metrics; swd.py): checked here, used by compute_metrics
-        from .. import swd
-        swd.validate_config(config)
-        # ... and the multi-scale structural similarity's ('msssim' in config.gen_metrics; msssim.py)
-        from .. import msssim
-        msssim.validate_config(config)
-        # ... and the radial power-spectrum distance's ('spectrum' in config.gen_metrics; spectrum.py)
-        from .. import spectrum
-        spectrum.validate_config(config)
-        # ... and the k-nearest-neighbour precision / recall / density / coverage's ('prdc' in config.gen_metrics; prdc.py)
-        from .. import prdc
-        prdc.validate_config(config)
-        # ... and the Frechet distance's and the Kernel Inception Distance's ('fd' / 'kid' in config.gen_metrics; frechet.py, kid.py)
-        from .. import frechet, kid
-        frechet.validate_config(config)
-        kid.validate_config(config)
+        # the set metrics' options ('swd' ... 'kid' in config.gen_metrics; validation.py): checked here, used by compute_metrics,
+        # which keeps the evaluation objects across validation points: name -> (constructor arguments, objects)
+        from .. import validation
+        for s in validation.SCORERS:
+            if not s.progressive_only:
+                s.module.validate_config(config)
+        self._metric_evals = {}
         # self-attention (config.self_attention; attention.py): a ResNet GAN option, and first order only - a critic with a
         # block excludes the gradient penalties
         from .. import attention
@@ -211,7 +202,6 @@ class GANLearner(object):
         self.log_every = getattr(config, 'log_every', 50)
         self.last_losses = {}
         self.last_metrics = {}      # compute_metrics: {'generator': {'prdc': {...}, 'fd': {...}, 'kid': {...}}}
-        self._prdc_eval = self._fd_eval = self._kid_eval = None
         self._loss = config.loss.casefold()
         self._set_loss()
         self._make_arenas()
@@ -456,13 +446,13 @@ class GANLearner(object):
         in whole batches; the images are generated once for all metrics.  The process stream is put back where it was, so an
         evaluation does not move the training run.  Returns the formatted lines; the numbers are kept in
         ``self.last_metrics['generator'][name]``."""
-        from .. import frechet, kid, prdc, rng
+        from .. import rng, validation
         c = self.config
         metrics_type = metrics_type.casefold()
         if metrics_type not in ('generator', 'critic', 'discriminator'):
             raise Exception('Invalid metrics_type. Only "generator", "critic", or "discriminator" are accepted.')
         metrics = [m.casefold() for m in metrics]
-        unsupported = [m for m in metrics if m not in ('prdc', 'fd', 'kid')]
+        unsupported = [m for m in metrics if m not in [s.name for s in validation.ROW_SCORERS]]
         if unsupported:
             raise ValueError(f"the ResNet GAN learner computes 'prdc', 'fd' and 'kid' only; unsupported metrics: {unsupported}")
         if not metrics:
@@ -478,25 +468,7 @@ class GANLearner(object):
         if n_use < 1:
             raise ValueError(f"{first} needs at least one whole batch of {self.batch_size} validation latents and reals (got "
                              f"{len(z_valid_dl.dataset)} and {len(valid_dl.dataset)})")
-        evals = {}                   # name -> (evaluation, resolution of its feature rows)
-        if 'prdc' in metrics:
-            key = (n_use, c.prdc_k, c.prdc_res)
-            if self._prdc_eval is None or self._prdc_eval[0] != key:
-                dim = prdc.feature_dim(3, c.res_samples, c.prdc_res)
-                self._prdc_eval = (key, prdc.PRDC(dim, n_use, n_use, k=c.prdc_k, device=c.dev))
-            evals['prdc'] = (self._prdc_eval[1], c.prdc_res)
-        if 'fd' in metrics:
-            if self._fd_eval is None or self._fd_eval[0] != c.fd_res:
-                self._fd_eval = (c.fd_res, frechet.Frechet(prdc.feature_dim(3, c.res_samples, c.fd_res), device=c.dev))
-            evals['fd'] = (self._fd_eval[1], c.fd_res)
-        if 'kid' in metrics:
-            key = (n_use, c.kid_res, c.kid_block)
-            if self._kid_eval is None or self._kid_eval[0] != key:
-                dim = prdc.feature_dim(3, c.res_samples, c.kid_res)
-                self._kid_eval = (key, kid.KID(dim, n_use, n_use, block=c.kid_block, device=c.dev))
-            evals['kid'] = (self._kid_eval[1], c.kid_res)
-        for ev, _ in evals.values():
-            ev.reset()
+        scorers = [s(self, c.res_samples, len(z_valid_dl.dataset), valid_dl) for s in validation.ROW_SCORERS if s.name in metrics]
         offset, left, valid_iter = rng._STATE['offset'], n_use, iter(valid_dl)
         try:
             for zbatch in z_valid_dl:
@@ -508,18 +480,16 @@ class GANLearner(object):
                     raise ValueError(f"{first}: validation latents and reals must come in equal batches (got {len(zb)} and "
                                      f"{len(xb)} with {left} images to go)")
                 xgen = self.generate(zs=zb, truncation=None, time_average=True)
-                for ev, res in evals.values():
-                    ev.feed_fake(prdc.features(xgen, res))
-                    ev.feed_real(prdc.features(xb, res))
+                for s in scorers:
+                    s.feed(len(zb), xgen, xb)
                 left -= len(zb)
         finally:
             rng._STATE['offset'] = offset
-        out = {name: evals[name][0].result() for name in ('prdc', 'fd', 'kid') if name in evals}
+        out, lines = {}, []
+        for s in scorers:
+            out[s.name], lines_of = s.finish()
+            lines += lines_of
         self.last_metrics[metrics_type] = out
-        lines = []
-        if 'prdc' in out:
-            lines += [(name, out['prdc'][name]) for name in ('precision', 'recall', 'density', 'coverage')]
-        lines += [(name, out[name][name]) for name in ('fd', 'kid') if name in out]
         return ['    ' + ('%-12s' % (name + ':')) + '%.4g' % v + '\n' for name, v in lines]
 
     def _pair_critic_batches(self, xgenb, xb):
@@ -661,8 +631,8 @@ class GANLearner(object):
         loss_d = loss_g = None
         # the validation metrics of this learner ('prdc' / 'fd' / 'kid' in config.gen_metrics; compute_metrics): with both
         # loaders only
-        from .. import frechet, kid, prdc
-        valid_metrics = [name for name, mod in (('prdc', prdc), ('fd', frechet), ('kid', kid)) if mod.wanted(c.gen_metrics)]
+        from .. import validation
+        valid_metrics = [s.name for s in validation.ROW_SCORERS if s.module.wanted(c.gen_metrics)]
         want_valid = bool(valid_metrics) and valid_dl is not None and z_valid_dl is not None
         try:
             for itr in range(num_main_iters):

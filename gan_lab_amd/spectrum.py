@@ -15,11 +15,10 @@ dB_real[k])^2)`` apart (DC excluded: an overall brightness offset is normalisati
 
 Nothing here is random and nothing depends on how the set was split into feeds: results are bitwise reproducible.
 """
-import os
-
 import torch
 
 from . import ops
+from ._metric_common import device_gate, host_only_error, wanted as _wanted
 
 MIN_RES = ops.SPECTRUM_MIN_RES
 MAX_RES = ops.SPECTRUM_MAX_RES
@@ -51,7 +50,7 @@ def validate_config(config):
 
 
 def wanted(metrics):
-    return any(isinstance(m, str) and m.casefold() == 'spectrum' for m in (metrics or ()))
+    return _wanted(metrics, 'spectrum')
 
 
 def bins(res):
@@ -94,11 +93,7 @@ class PowerSpectrum(object):
             raise ValueError(f'spectrum: n_images must be a positive integer, got {n_images!r}')
         self.n_images = n_images
         self.window = check_options(window)
-        self.device = torch.device(device)
-        # GANLAB_HOST_LOGIC_ONLY=1 (CPU tests of the host logic): feeds are checked and counted, nothing is computed
-        self._host_only = self.device.type != 'cuda' and os.environ.get('GANLAB_HOST_LOGIC_ONLY') == '1'
-        if self.device.type != 'cuda' and not self._host_only:
-            raise TypeError(f'spectrum: the metric runs on the GPU only (device={device!r}); the HIP path has no CPU fallback')
+        self.device, self._host_only = device_gate(device, 'spectrum')
         self._fed = 0
         if self._host_only:
             return
@@ -130,7 +125,7 @@ class PowerSpectrum(object):
         if self._fed != self.n_images:
             raise ValueError(f'spectrum: {self.n_images} images were declared, {self._fed} were fed')
         if self._host_only:
-            raise RuntimeError('spectrum: GANLAB_HOST_LOGIC_ONLY=1 checks the host logic only; the metric itself needs the GPU')
+            raise host_only_error('spectrum')
 
     def profile(self):
         """{'power': [S[0] .. S[R/2]], 'db': [...]}: the set profile, with one host read."""

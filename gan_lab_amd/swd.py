@@ -14,11 +14,11 @@ Everything random is a pure function of ``seed``: the centres of image i at a le
 depend on how the set was fed, and the process RNG stream (latents, noise, augmentation) is never touched.
 """
 import math
-import os
 
 import torch
 
 from . import ops, rng
+from ._metric_common import device_gate, host_only_error, wanted as _wanted
 
 DESC = ops.SWD_DESC
 MIN_RES = 16
@@ -62,7 +62,7 @@ def validate_config(config):
 
 
 def wanted(metrics):
-    return any(isinstance(m, str) and m.casefold() == 'swd' for m in (metrics or ()))
+    return _wanted(metrics, 'swd')
 
 
 def levels_of(res, min_res=MIN_RES):
@@ -106,16 +106,12 @@ class SlicedWasserstein(object):
         self.n_images = _positive_int(n_images, 'n_images')
         check_options(nhoods_per_image, dir_repeats, dirs_per_repeat, seed)
         self.n, self.dir_repeats, self.dirs_per_repeat, self.seed = nhoods_per_image, dir_repeats, dirs_per_repeat, seed
-        self.device = torch.device(device)
         self.levels = levels_of(res)
         self.m = self.n_images * self.n
         if self.dirs_per_repeat * self.m >= 2 ** 32 - 1:
             raise ValueError(f'swd: dirs_per_repeat x descriptors = {self.dirs_per_repeat} x {self.m} exceeds the sort\'s '
                              f'2^32 - 1 keys; use fewer directions per repeat or fewer images')
-        # GANLAB_HOST_LOGIC_ONLY=1 (CPU tests of the host logic): feeds are checked and counted, nothing is computed
-        self._host_only = self.device.type != 'cuda' and os.environ.get('GANLAB_HOST_LOGIC_ONLY') == '1'
-        if self.device.type != 'cuda' and not self._host_only:
-            raise TypeError(f'swd: the metric runs on the GPU only (device={device!r}); the HIP path has no CPU fallback')
+        self.device, self._host_only = device_gate(device, 'swd')
         self._fed = {'real': 0, 'fake': 0}
         if self._host_only:
             return
@@ -173,7 +169,7 @@ class SlicedWasserstein(object):
         if r != self.n_images:
             raise ValueError(f'swd: {self.n_images} images per set were declared, {r} were fed')
         if self._host_only:
-            raise RuntimeError('swd: GANLAB_HOST_LOGIC_ONLY=1 checks the host logic only; the metric itself needs the GPU')
+            raise host_only_error('swd')
         d = self.dirs_per_repeat
         dists = []
         for li in range(len(self.levels)):

@@ -217,7 +217,7 @@ def test_resnet_learner_reports_fd_and_kid_and_leaves_prdc_alone(capsys):
     # without the two names: what it reported before, and nothing of theirs is allocated
     offset = rng._STATE['offset']
     lines = L.compute_metrics(['prdc'], 'Generator', z_dl, x_dl)
-    assert [ln.split(':')[0].strip() for ln in lines] == list(SCORES) and L._fd_eval is None and L._kid_eval is None
+    assert [ln.split(':')[0].strip() for ln in lines] == list(SCORES) and set(L._metric_evals) == {'prdc'}
     alone = L.last_metrics['generator']
     assert set(alone) == {'prdc'}
     pr = prdc.PRDC(3 * 8 * 8, 16, 16, k=3)

@@ -350,8 +350,8 @@ def test_compute_metrics_checks_on_the_device(_widths):
     lines = L.compute_metrics(['spectrum'], 'Generator', z_dl, SyntheticImageLoader(8, 4, 16))
     assert [ln.split(':')[0].strip() for ln in lines] == ['spectrum', 'spectrum hf']
     assert L.last_metrics['generator']['spectrum']['images'] == 8
-    first = L._spectrum_eval
+    first = L._metric_evals['spectrum']
     L.compute_metrics(['spectrum'], 'Generator', z_dl, SyntheticImageLoader(8, 4, 16))
-    assert L._spectrum_eval is first                                            # cached per (res, n)
+    assert L._metric_evals['spectrum'] is first                                 # cached per (res, n)
     with pytest.raises(ValueError, match='whole batch'):
         L.compute_metrics(['spectrum'], 'Generator', _ZLoader([(torch.randn(2, 16),)]), SyntheticImageLoader(8, 4, 16))
