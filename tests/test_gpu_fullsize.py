@@ -479,7 +479,13 @@ def test_learner_step_full_width_vs_oracle(res, b, capsys, tmp_path):
                 ('conv_s2_up_roll_blur_kernel<1',),
             'thin modulated layer with its tail (generator top)': ('conv_fwd_rollmod_kernel',),
             'rolling-window weight gradient': ('conv_wgrad_roll_kernel',),
-            'rolling-window stride-2 weight gradient': ('conv_s2_wgrad_roll2_kernel',)}
+            'rolling-window stride-2 weight gradient': ('conv_s2_wgrad_roll2_kernel',),
+            # the split-product (3 x bf16) families: x3_ok and its kin route to the exact kernels below their tile gates
+            'split-product conv: forward / input gradient (thick plain layers)': ('conv_x3_fwd_kernel',),
+            'split-product conv: up-layer forward / pooled-layer input gradient': ('conv_x3_up_kernel',),
+            'split-product conv: pooled-layer forward / up-layer input gradient': ('conv_x3_down_kernel',),
+            'split-product weight gradient': ('x3w_reduce_kernel',),
+            'split-product stride-2 weight gradient': ('x3sw_reduce_kernel',)}
     ran = {what: census.count(*needles) for what, needles in must.items()}
     rep = dict(loss_d=rel_err(ld, cpu['ld']), loss_g=rel_err(lg, cpu['lg']), kernels=ran,
                direct_gradients=f'{taken[0]} of {n_params} parameters')

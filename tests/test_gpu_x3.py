@@ -1,8 +1,10 @@
 """Split-product (3 x bf16) conv kernels (csrc/conv_x3.hip) through the C-ABI: every form against float64 on the CPU and
 against the exact-fp32 MFMA kernels of the same entry points, at the accuracy bar of the fp32 kernels (TOL of test_gpu_ops).
 The reference computes F.conv2d in fp32 (utils/custom_layers.py:202-211); the bar that the split products are 'fp32' is the
-rms distance to float64, which must not exceed ATen's own (tools/x3_bench.py; here: <= 1.1 x the exact kernels')."""
-import contextlib
+rms distance to float64, which must not exceed ATen's own (tools/x3_bench.py; here: <= 1.1 x the exact kernels').
+Every operand here is drawn from randn - the geometry cases: channel chunks, tiles, ragged counts.  The accuracy evidence on the
+operands a training step feeds these kernels (one-signed, offset, mixed exponents, zeros and subnormals, tiny / huge, non-finite)
+is tests/test_gpu_x3_operands.py, at the same bars."""
 import ctypes
 
 import pytest
@@ -10,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from util import assert_close
+from x3_forms import launched, rms_rel, x3_at_any_size
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-4
@@ -21,26 +24,6 @@ def ops():
     from gan_lab_amd import ops as _ops, _lib
     _lib.lib()
     return _ops
-
-
-@contextlib.contextmanager
-def x3_at_any_size(ops):
-    """The split-product kernels on these small cases too: no minimum tile count for the launch."""
-    old_min, ops._X3_MIN_TILES = ops._X3_MIN_TILES, 1
-    try:
-        yield
-    finally:
-        ops._X3_MIN_TILES = old_min
-
-
-def rms_rel(a, ref):
-    a, ref = a.double().cpu(), ref.double().cpu()
-    return ((a - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item()
-
-
-def launched(ops):
-    from gan_lab_amd import _lib
-    return _lib.last_launch()[0] or ''
 
 
 # N, Cin, Cout, H, W: one / two / three / four / eight 64-channel double chunks, 2+ co tiles, non-square.  At most 160 tiles: one
