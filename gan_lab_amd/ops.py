@@ -36,6 +36,7 @@ Layering:
 
 All ops require contiguous fp32 CUDA(HIP) tensors and raise otherwise - there is no CPU path.
 """
+import collections
 import ctypes
 import os
 
@@ -107,7 +108,7 @@ from ._ops.project import (  # noqa: F401
 # training step before).  Entries outside the range (the other network) stay valid.  ``bump_weight_epoch()`` without
 # ranges drops everything (growth events, graph capture).
 class _PackEntry(object):
-    __slots__ = ('w', 'out', 'serial', 'ptr', 'desc')
+    __slots__ = ('w', 'out', 'serial', 'ptr', 'row', 'desc')      # row: of _PACK_ROWS; desc: the PackDesc fields kind ... total
 
 
 _PACK_CACHE = {}
@@ -115,7 +116,29 @@ _PACK_SERIAL = [0]
 _PACK_GEN = [0]          # bumped when buffers a captured graph may point at are dropped: full flush, table rebuild
 _PACK_RANGES = {}        # (lo, hi) byte range -> serial of its last rewrite
 _PACK_TABLES = {}        # (lo, hi) -> (entry keys, device descriptor table, total blocks)
-_KIND_PLAIN, _KIND_S2, _KIND_BF16, _KIND_X3 = 0, 1, 2, 3
+_KIND_PLAIN, _KIND_S2, _KIND_BF16, _KIND_X3 = 0, 1, 2, 3      # GANLAB_PACKKIND_* (include/ganlab_hip.h)
+# The kernel families a conv can run on (``conv_route``): bf16 compute; split products plain, transposed (an up layer's forward, a
+# pooled layer's input gradient) and strided (the other two); exact stride-2; the long-contraction linear run as a weight gradient;
+# exact fp32.  A family that packs weights has the row of its name below.
+BF16, X3, X3_UP, X3_DOWN, S2, LINEAR, F32 = 'bf16', 'x3', 'x3_up', 'x3_down', 's2', 'linear', 'f32'
+
+# The packed layouts, one row each; a new kernel family's layout is a new row (and its branch in csrc/pack.hip).
+#   fn, dtype   library entry point ``ganlab_<fn>(w, out, Cout, Cin, *args, scale, stream)`` (``out`` NULL: size query), buffer dtype
+#   args        what the entry point takes between Cin and scale, in its order: the weight's ``ks``, the request's ``mode``
+#               (PACK_FWD / PACK_DGRAD; ``transpose`` to the stride-2 f32 entry point) and ``up``
+#   kind, ks    of ``_lib.PackDesc`` in the batched re-pack (ks None: the weight's own; 4 / 5: the stride-2 split-product layouts);
+#               its ``mode`` / ``up`` are the request's where ``args`` names them, else 0
+#   per_thread  packed elements per thread of pack_many_kernel, all taps of one weight position (None: ks * ks) - the kernel
+#               returns past ``total / per_thread`` threads of a descriptor, so the block count here must agree with csrc/pack.hip
+_PackRow = collections.namedtuple('_PackRow', 'fn dtype args kind ks per_thread')
+_PACK_ROWS = {
+    F32: _PackRow('conv_pack_f32', torch.float32, ('ks', 'mode'), _KIND_PLAIN, None, None),
+    S2: _PackRow('conv_s2_pack_f32', torch.float32, ('up', 'mode'), _KIND_S2, 3, 16),
+    BF16: _PackRow('conv_pack_bf16', torch.bfloat16, ('mode',), _KIND_BF16, 3, 9),
+    X3: _PackRow('conv_x3_pack', torch.bfloat16, ('mode',), _KIND_X3, 3, 27),
+    X3_UP: _PackRow('conv_s2_x3_pack', torch.bfloat16, ('up',), _KIND_X3, 4, 48),
+    X3_DOWN: _PackRow('conv_s2_down_x3_pack', torch.bfloat16, ('up',), _KIND_X3, 5, 48),
+}
 
 
 def bump_weight_epoch(ranges=None):
@@ -154,24 +177,18 @@ def mark_packs_stale():
         bump_weight_epoch([_ALL_ADDRESSES])
 
 
+def _pack_call(row, w, out, desc, stream):
+    """The row's entry point on one weight: the size query (``w``, ``out`` and ``stream`` None) or the pack kernel."""
+    _, cout, cin, ks, mode, up, scale, _ = desc
+    args = {'ks': ks, 'mode': mode, 'up': up}
+    return getattr(_lib.lib(), 'ganlab_' + row.fn)(_p(w), _p(out), cout, cin, *[args[a] for a in row.args], scale, stream)
+
+
 def _pack_one(e):
     """Re-pack one cache entry with its own kernel (the batched launch's table cannot be uploaded while a capture runs)."""
-    L = _lib.lib()
-    kind, cout, cin, ks, mode, up, scale, total = e.desc
-    if kind == _KIND_S2:
-        rc = L.ganlab_conv_s2_pack_f32(_p(e.w), _p(e.out), cout, cin, up, mode, scale, _st())
-    elif kind == _KIND_BF16:
-        rc = L.ganlab_conv_pack_bf16(_p(e.w), e.out.data_ptr(), cout, cin, mode, scale, _st())
-    elif kind == _KIND_X3 and ks == 4:
-        rc = L.ganlab_conv_s2_x3_pack(_p(e.w), e.out.data_ptr(), cout, cin, up, scale, _st())
-    elif kind == _KIND_X3 and ks == 5:
-        rc = L.ganlab_conv_s2_down_x3_pack(_p(e.w), e.out.data_ptr(), cout, cin, up, scale, _st())
-    elif kind == _KIND_X3:
-        rc = L.ganlab_conv_x3_pack(_p(e.w), e.out.data_ptr(), cout, cin, mode, scale, _st())
-    else:
-        rc = L.ganlab_conv_pack_f32(_p(e.w), _p(e.out), cout, cin, ks, mode, scale, _st())
-    if rc != total:
-        raise _lib.GanlabLibraryError(f're-pack failed ({rc} != {total})')
+    rc = _pack_call(e.row, e.w, e.out, e.desc, _st())
+    if rc != e.desc[7]:
+        raise _lib.GanlabLibraryError(f're-pack failed ({rc} != {e.desc[7]})')
 
 
 def _stale_range(e):
@@ -203,7 +220,7 @@ def _repack_range(r):
             d.kind, d.Cout, d.Cin, d.ks, d.mode, d.up, d.scale, d.total, d.block0 = kind, cout, cin, ks, mode, up, scale, \
                 total, blocks
             # one thread per weight position, all of its taps (csrc/pack.hip pack_many_kernel)
-            blocks += (total // (16 if kind == _KIND_S2 else (9 if kind == _KIND_BF16 else ((48 if ks >= 4 else 27) if kind == _KIND_X3 else ks * ks))) + 255) // 256
+            blocks += (total // (e.row.per_thread or ks * ks) + 255) // 256
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
         if tab is not None:
             _PACK_GEN[0] += 1       # the old table's memory goes back to the allocator
@@ -225,60 +242,45 @@ def _pack_lookup(key):
     return e.out
 
 
-def _pack_store(key, w, out, desc):
+def _pack_store(key, w, out, row, desc):
     if len(_PACK_CACHE) > 1024:
         bump_weight_epoch()
     e = _PackEntry()
-    e.w, e.out, e.serial, e.ptr, e.desc = w.detach(), out, _PACK_SERIAL[0], w.data_ptr(), desc
+    e.w, e.out, e.serial, e.ptr, e.row, e.desc = w.detach(), out, _PACK_SERIAL[0], w.data_ptr(), row, desc
     _PACK_CACHE[key] = e
     # a new entry changes the entry set of its range: the table is rebuilt at the next re-pack (keys differ)
     return out
 
 
+def _packed_as(layout, w, mode, up, scale):
+    """Weight ``w`` in the layout of row ``layout`` of ``_PACK_ROWS``, from the cache or packed now.  ``mode`` / ``up``: what the
+    row's entry point takes of them, 0 for the one it does not take."""
+    key = (w.data_ptr(), w._version, tuple(w.shape), mode, up, float(scale), layout)
+    hit = _pack_lookup(key)
+    if hit is not None:
+        return hit
+    row = _PACK_ROWS[layout]
+    desc = (row.kind, w.shape[0], w.shape[1], row.ks or w.shape[2], mode, up, float(scale))
+    n = _pack_call(row, None, None, desc + (0,), None)
+    if n <= 0:
+        raise _lib.GanlabLibraryError(f'{row.fn} size query failed ({n}) for weight {tuple(w.shape)}')
+    out = torch.empty((n,), dtype=row.dtype, device=w.device)
+    rc = _pack_call(row, w, out, desc + (0,), _st())
+    if rc != n:
+        raise _lib.GanlabLibraryError(f'{row.fn} failed ({rc})')
+    return _pack_store(key, w, out, row, desc + (int(n),))
+
+
 def _packed(w, mode, scale, s2_up=None):
     """mode: PACK_FWD / PACK_DGRAD.  s2_up: None -> plain [tap][ci][co] packing; 0 / 1 -> K4 packing of the
     stride-2 kernels for a down (pool) / up layer."""
-    key = (w.data_ptr(), w._version, tuple(w.shape), mode, float(scale), s2_up)
-    hit = _pack_lookup(key)
-    if hit is not None:
-        return hit
-    cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
-    L = _lib.lib()
     if s2_up is not None:
-        tr = 1 if mode == PACK_DGRAD else 0
-        n = L.ganlab_conv_s2_pack_f32(None, None, cout, cin, int(s2_up), tr, scale, None)
-        if n <= 0:
-            raise _lib.GanlabLibraryError(f'conv_s2_pack size query failed ({n}) for weight {tuple(w.shape)}')
-        out = _new((n,), w)
-        rc = L.ganlab_conv_s2_pack_f32(_p(w), _p(out), cout, cin, int(s2_up), tr, scale, _st())
-        if rc != n:
-            raise _lib.GanlabLibraryError(f'conv_s2_pack failed ({rc})')
-        return _pack_store(key, w, out, (_KIND_S2, cout, cin, 3, tr, int(s2_up), float(scale), int(n)))
-    n = L.ganlab_conv_pack_f32(None, None, cout, cin, ks, mode, scale, None)
-    if n <= 0:
-        raise _lib.GanlabLibraryError(f'conv_pack size query failed ({n}) for weight {tuple(w.shape)}')
-    out = _new((n,), w)
-    rc = L.ganlab_conv_pack_f32(_p(w), _p(out), cout, cin, ks, mode, scale, _st())
-    if rc != n:
-        raise _lib.GanlabLibraryError(f'conv_pack failed ({rc})')
-    return _pack_store(key, w, out, (_KIND_PLAIN, cout, cin, ks, mode, 0, float(scale), int(n)))
+        return _packed_as(S2, w, 1 if mode == PACK_DGRAD else 0, int(s2_up), scale)
+    return _packed_as(F32, w, mode, 0, scale)
 
 
 def _packed_bf16(w, mode, scale):
-    key = (w.data_ptr(), w._version, tuple(w.shape), mode, float(scale), 'bf16')
-    hit = _pack_lookup(key)
-    if hit is not None:
-        return hit
-    cout, cin = w.shape[0], w.shape[1]
-    L = _lib.lib()
-    n = L.ganlab_conv_pack_bf16(None, None, cout, cin, mode, scale, None)
-    if n <= 0:
-        raise _lib.GanlabLibraryError(f'conv_pack_bf16 size query failed ({n}) for weight {tuple(w.shape)}')
-    out = torch.empty((n,), dtype=torch.bfloat16, device=w.device)
-    rc = L.ganlab_conv_pack_bf16(_p(w), out.data_ptr(), cout, cin, mode, scale, _st())
-    if rc != n:
-        raise _lib.GanlabLibraryError(f'conv_pack_bf16 failed ({rc})')
-    return _pack_store(key, w, out, (_KIND_BF16, cout, cin, 3, mode, 0, float(scale), int(n)))
+    return _packed_as(BF16, w, mode, 0, scale)
 
 
 # ---- fp32 convolutions as split products on the bf16 matrix cores (csrc/conv_x3.hip) --------------------------------
@@ -300,28 +302,51 @@ def x3_enabled():
     return _X3[0]
 
 
+# The three tile gates: pixel rows, pixel columns and output channels of one tile, the flag the layer must carry for its FORWARD to
+# take the form (its input gradient: the other flag; None: a plain layer) and the library's predicate.  The resolution counted in
+# tiles is the layer's low one.
+_X3_GATES = {
+    X3: (16, 16, 64, None, 'conv_x3_supported'),
+    X3_UP: (8, 16, 32, 'up', 'conv_s2_x3_supported'),        # (32 output channels: both row parities in one workgroup)
+    X3_DOWN: (8, 16, 128, 'pool', 'conv_s2_down_x3_supported'),
+}
+
+
+def _x3_gate(form, g, dgrad):
+    """The Python conditions, then the minimum tile count, then the library's predicate (byte limits, divisibility)."""
+    if not _X3[0]:
+        return False
+    rows, cols, chans, flag, supported = _X3_GATES[form]
+    if flag is None:
+        if g.bf is not None or g.s2 or g.up or g.pool or g.ks != 3 or g.pad != 1:
+            return False
+        hl, wl = g.Hin, g.Win
+    else:
+        if dgrad:
+            flag = 'pool' if flag == 'up' else 'up'
+        if not g.s2 or getattr(g, flag) != 1:
+            return False
+        hl, wl = (g.Hin // 2, g.Win // 2) if flag == 'pool' else (g.Hin, g.Win)
+    co = g.Cin if dgrad else g.Cout
+    if g.N * (hl // rows) * (wl // cols) * (co // chans) < _X3_MIN_TILES:
+        return False
+    return bool(getattr(_lib.lib(), 'ganlab_' + supported)(g.ref(), 1 if dgrad else 0))
+
+
 def x3_ok(g, dgrad=False):
     """Does this conv (forward, or its input gradient) run on the split-product kernels?"""
-    if not _X3[0] or g.bf is not None or g.s2 or g.up or g.pool or g.ks != 3 or g.pad != 1:
-        return False
-    co = g.Cin if dgrad else g.Cout
-    if g.N * (g.Hin // 16) * (g.Win // 16) * (co // 64) < _X3_MIN_TILES:
-        return False
-    return bool(_lib.lib().ganlab_conv_x3_supported(g.ref(), 1 if dgrad else 0))
+    return _x3_gate(X3, g, dgrad)
 
 
 def x3_s2_ok(g, dgrad=False):
     """Does this stride-2 fused layer run on the split-product kernel's transposed form?  (An up layer's forward, a pooled
-    layer's input gradient; the strided form - pooled forward, up layer's input gradient - stays on the exact kernels.)"""
-    if not _X3[0] or not g.s2:
-        return False
-    if (g.pool if dgrad else g.up) != 1:
-        return False
-    co = g.Cin if dgrad else g.Cout
-    hl, wl = (g.Hin // 2, g.Win // 2) if dgrad else (g.Hin, g.Win)
-    if g.N * (hl // 8) * (wl // 16) * (co // 32) < _X3_MIN_TILES:       # (32 output channels: both row parities in one workgroup)
-        return False
-    return bool(_lib.lib().ganlab_conv_s2_x3_supported(g.ref(), 1 if dgrad else 0))
+    layer's input gradient.)"""
+    return _x3_gate(X3_UP, g, dgrad)
+
+
+def x3_s2_down_ok(g, dgrad=False):
+    """The strided stride-2 form on the split-product kernel: a pooled layer's forward, an up layer's input gradient."""
+    return _x3_gate(X3_DOWN, g, dgrad)
 
 
 def x3_wgrad_ok(g):
@@ -331,14 +356,6 @@ def x3_wgrad_ok(g):
     return bool(_lib.lib().ganlab_conv_wgrad_x3_supported(g.ref()))
 
 
-def _wgrad_x3(gy, x, s_, t_, gw, g, scale):
-    L = _lib.lib()
-    ws = torch.empty((L.ganlab_conv_wgrad_x3_workspace(g.ref()) + 3) // 4, dtype=torch.float32, device=x.device)
-    check(L.ganlab_conv_wgrad_x3(_p(gy), _p(x), _p(s_), _p(t_), _p(gw), g.ref(), scale, _p(ws), ws.numel() * 4, _st()),
-          'conv_wgrad_x3')
-    return gw
-
-
 def x3_s2_wgrad_ok(g):
     """Does this stride-2 layer's weight gradient run on the split-product box-sum kernel?"""
     if not _X3[0] or g.bf is not None or not g.s2 or g.ks != 3 or g.pad != 1:
@@ -346,59 +363,84 @@ def x3_s2_wgrad_ok(g):
     return bool(_lib.lib().ganlab_conv_s2_wgrad_x3_supported(g.ref()))
 
 
-def _wgrad_x3_s2(gy, x, s_, t_, gw, g, scale):
+def _wgrad_x3(gy, x, s_, t_, gw, g, scale):
+    """The split-product weight gradient of a plain layer or (``g.s2``) of a stride-2 one, the box-sum kernel."""
     L = _lib.lib()
-    ws = torch.empty((L.ganlab_conv_s2_wgrad_x3_workspace(g.ref()) + 3) // 4, dtype=torch.float32, device=x.device)
-    check(L.ganlab_conv_s2_wgrad_x3(_p(gy), _p(x), _p(s_), _p(t_), _p(gw), g.ref(), scale, _p(ws), ws.numel() * 4, _st()),
-          'conv_s2_wgrad_x3')
+    name = 'conv_s2_wgrad_x3' if g.s2 else 'conv_wgrad_x3'
+    ws = torch.empty((getattr(L, f'ganlab_{name}_workspace')(g.ref()) + 3) // 4, dtype=torch.float32, device=x.device)
+    check(getattr(L, 'ganlab_' + name)(_p(gy), _p(x), _p(s_), _p(t_), _p(gw), g.ref(), scale, _p(ws), ws.numel() * 4, _st()), name)
     return gw
-
-
-def x3_s2_down_ok(g, dgrad=False):
-    """The strided stride-2 form on the split-product kernel: a pooled layer's forward, an up layer's input gradient."""
-    if not _X3[0] or not g.s2:
-        return False
-    if (g.up if dgrad else g.pool) != 1:
-        return False
-    co = g.Cin if dgrad else g.Cout
-    hl, wl = (g.Hin, g.Win) if dgrad else (g.Hin // 2, g.Win // 2)
-    if g.N * (hl // 8) * (wl // 16) * (co // 128) < _X3_MIN_TILES:
-        return False
-    return bool(_lib.lib().ganlab_conv_s2_down_x3_supported(g.ref(), 1 if dgrad else 0))
-
-
-def _packed_x3_any(name, tag, w, sel, scale, ks):
-    """A weight's three bf16 planes in the layout of one split-product kernel: library function ``ganlab_<name>``, cache tag
-    ``tag``; ``sel`` is the function's mode / up argument, ``ks`` the descriptor's form (3: ``sel`` is its mode; 4, 5: its up)."""
-    key = (w.data_ptr(), w._version, tuple(w.shape), sel, float(scale), tag)
-    hit = _pack_lookup(key)
-    if hit is not None:
-        return hit
-    cout, cin = w.shape[0], w.shape[1]
-    pack = getattr(_lib.lib(), 'ganlab_' + name)
-    n = pack(None, None, cout, cin, sel, scale, None)
-    if n <= 0:
-        raise _lib.GanlabLibraryError(f'{name} size query failed ({n}) for weight {tuple(w.shape)}')
-    out = torch.empty((n,), dtype=torch.bfloat16, device=w.device)
-    rc = pack(_p(w), out.data_ptr(), cout, cin, sel, scale, _st())
-    if rc != n:
-        raise _lib.GanlabLibraryError(f'{name} failed ({rc})')
-    mode, up = (sel, 0) if ks == 3 else (0, sel)
-    return _pack_store(key, w, out, (_KIND_X3, cout, cin, ks, mode, up, float(scale), int(n)))
 
 
 def _packed_x3_s2_down(w, up, scale):
     """``up``: 0 = a pooled layer's forward weights, 1 = an up layer's input-gradient weights."""
-    return _packed_x3_any('conv_s2_down_x3_pack', 'x3s2d', w, int(up), scale, 5)
+    return _packed_as(X3_DOWN, w, 0, int(up), scale)
 
 
 def _packed_x3_s2(w, up, scale):
     """``up``: 1 = an up layer's forward weights, 0 = a pooled layer's input-gradient weights."""
-    return _packed_x3_any('conv_s2_x3_pack', 'x3s2', w, int(up), scale, 4)
+    return _packed_as(X3_UP, w, 0, int(up), scale)
 
 
 def _packed_x3(w, mode, scale):
-    return _packed_x3_any('conv_x3_pack', 'x3', w, mode, scale, 3)
+    return _packed_as(X3, w, mode, 0, scale)
+
+
+_packed_x3_any, _wgrad_x3_s2 = _packed_as, _wgrad_x3      # the names these two had before they took every layout / both forms
+
+
+# ---- which kernel family a conv runs on -------------------------------------------------------------------------------------------
+def conv_route(g, op):
+    """The kernel family the launcher of ``op`` ('fwd', 'dgrad', 'wgrad') uses for geometry ``g``.  The order of the questions
+    below is the specification and this is its only statement (of a stride-2 layer: the strided split-product gate before the transposed
+    one, both before the exact kernels); a new family is a line here, in front of the first family that would otherwise take its geometries.  The
+    stride-2 split-product weight gradient is one kernel for both layer kinds and goes by the form of its layer's forward.
+    Sub-choices that need a plan from the library (split-K, the rolling and 16-wide bf16 weight gradients) are made inside the
+    family's launcher body."""
+    if g.bf is not None:
+        return BF16
+    if op == 'wgrad':
+        if g.s2:
+            return (X3_UP if g.up else X3_DOWN) if x3_s2_wgrad_ok(g) else S2
+        return X3 if x3_wgrad_ok(g) else F32
+    dgrad = op == 'dgrad'
+    assert dgrad or op == 'fwd', op
+    if g.s2:
+        if x3_s2_down_ok(g, dgrad):
+            return X3_DOWN
+        return X3_UP if x3_s2_ok(g, dgrad) else S2
+    if not dgrad and g.ks == 1 and g.Hin == 1 and g.Win == 1 and g.N <= 64 and g.Cin >= 2048 and g.Cin % 128 == 0:
+        return LINEAR
+    return X3 if x3_ok(g, dgrad) else F32
+
+
+def _route_among(g, op, admitted):
+    """For a launcher whose form exists in some families only (masked, affine-on-load, one-pass layer tail): the routed family
+    where it is one of ``admitted``, else exact fp32 - whose entry point refuses a geometry it does not take."""
+    fam = conv_route(g, op)
+    return fam if fam in admitted else F32
+
+
+_AFF_FAMILIES = ((X3,), (X3_UP, S2))      # what the affine-on-load forms admit, by ``g.up``: they exist for plain and up layers
+
+
+def _packed_for(fam, w, g, scale, dgrad=False):
+    """``w`` as family ``fam``'s forward (``dgrad``: input-gradient) kernels read it."""
+    if fam == X3_UP:            # these two entry points take the layer kind: an up layer's forward, a pooled layer's input gradient
+        return _packed_as(fam, w, 0, 0 if dgrad else 1, scale)
+    if fam == X3_DOWN:          # a pooled layer's forward, an up layer's input gradient
+        return _packed_as(fam, w, 0, 1 if dgrad else 0, scale)
+    return _packed_as(fam, w, PACK_DGRAD if dgrad else PACK_FWD, g.up if fam == S2 else 0, scale)
+
+
+# family: its forward and its input-gradient entry point, for the families whose two launches are one call each with the
+# signatures (x, wp, bias, y, geom, bias_scale, act, slope, stream) and (gy, wp, gx, geom, stream)
+_CONV_ENTRY = {
+    X3_DOWN: ('conv_s2_down_fwd_x3', 'conv_s2_down_dgrad_x3'),
+    X3_UP: ('conv_s2_fwd_x3', 'conv_s2_dgrad_x3'),
+    S2: ('conv_s2_fwd_f32', 'conv_s2_dgrad_f32'),       # conv + average pool (S kernel) or upsample + conv (T kernel)
+    X3: ('conv_fwd_x3', 'conv_dgrad_x3'),
+}
 
 
 # ---------------------------------------------------------------------------------------------- #
@@ -413,35 +455,23 @@ def k_conv_fwd(x, w, bias, g, scale, bias_scale=1.0, act=ACT_NONE, slope=0.2):
         bias = _c(bias, 'bias')
         assert bias.numel() == g.Cout
     y = _new(g.out_shape, x)
-    if g.bf is not None:   # bf16-compute layer; a nearest upsample in front / average pool behind folds into the kernel
+    fam = conv_route(g, 'fwd')
+    L = _lib.lib()
+    if fam == BF16:   # bf16-compute layer; a nearest upsample in front / average pool behind folds into the kernel
         geom = g.bf_fused if g.bf_fused is not None else g.bf
         xin = k_up2(x, 1.0) if (g.up and g.bf_fused is None) else x
-        wp = _packed_bf16(w, PACK_FWD, scale)
-        L = _lib.lib()
+        wp = _packed_for(BF16, w, g, scale)
         split = L.ganlab_conv_bf16_splitk_plan(ctypes.byref(geom), 0)
         if split >= 2:     # few output tiles, long contraction (512-channel 16x16 layers at small batch)
             m = 2 if geom.up else 1
             ws = torch.empty((split * geom.N * geom.Cout * geom.Hin * m * geom.Win * m,), dtype=torch.float32, device=x.device)
-            check(L.ganlab_conv_fwd_bf16_splitk(_p(xin), wp.data_ptr(), _p(bias), _p(y), ctypes.byref(geom), bias_scale, act,
+            check(L.ganlab_conv_fwd_bf16_splitk(_p(xin), _p(wp), _p(bias), _p(y), ctypes.byref(geom), bias_scale, act,
                                                 slope, _p(ws), ws.numel() * 4, _st()), 'conv_fwd_bf16_splitk')
             return y
-        check(L.ganlab_conv_fwd_bf16(_p(xin), wp.data_ptr(), _p(bias), _p(y), ctypes.byref(geom), bias_scale,
+        check(L.ganlab_conv_fwd_bf16(_p(xin), _p(wp), _p(bias), _p(y), ctypes.byref(geom), bias_scale,
                                      act, slope, _st()), 'conv_fwd_bf16')
         return y
-    if x3_s2_down_ok(g):
-        check(_lib.lib().ganlab_conv_s2_down_fwd_x3(_p(x), _packed_x3_s2_down(w, 0, scale).data_ptr(), _p(bias), _p(y), g.ref(),
-                                                    bias_scale, act, slope, _st()), 'conv_s2_down_fwd_x3')
-        return y
-    if x3_s2_ok(g):
-        check(_lib.lib().ganlab_conv_s2_fwd_x3(_p(x), _packed_x3_s2(w, 1, scale).data_ptr(), _p(bias), _p(y), g.ref(), bias_scale,
-                                               act, slope, _st()), 'conv_s2_fwd_x3')
-        return y
-    if g.s2:   # stride-2 fused layer: conv+avgpool (S kernel) or upsample+conv (T kernel)
-        wp = _packed(w, PACK_FWD, scale, s2_up=g.up)
-        check(_lib.lib().ganlab_conv_s2_fwd_f32(_p(x), _p(wp), _p(bias), _p(y), g.ref(), bias_scale, act, slope,
-                                                _st()), 'conv_s2_fwd')
-        return y
-    if g.ks == 1 and g.Hin == 1 and g.Win == 1 and g.N <= 64 and g.Cin >= 2048 and g.Cin % 128 == 0:
+    if fam == LINEAR:
         # A linear layer with a long contraction and few rows (the critic's 4x4 "valid" conv: 8192 -> 512 on `batch`
         # rows): the forward kernel would walk all of K in 32 workgroups.  y[n][co] = sum_k x[n][k] w[co][k] is the
         # weight-gradient contraction with k as the pixel axis, x as a (1, N, k) "output gradient" and w as a
@@ -455,12 +485,11 @@ def k_conv_fwd(x, w, bias, g, scale, bias_scale=1.0, act=ACT_NONE, slope=0.2):
         if bias is not None or act != ACT_NONE:
             y = k_bias_act(y, bias, None, None, bias_scale, act, slope)
         return y
-    L = _lib.lib()
-    if x3_ok(g):
-        check(L.ganlab_conv_fwd_x3(_p(x), _packed_x3(w, PACK_FWD, scale).data_ptr(), _p(bias), _p(y), g.ref(), bias_scale, act,
-                                   slope, _st()), 'conv_fwd_x3')
+    wp = _packed_for(fam, w, g, scale)
+    if fam != F32:
+        name = _CONV_ENTRY[fam][0]
+        check(getattr(L, 'ganlab_' + name)(_p(x), _p(wp), _p(bias), _p(y), g.ref(), bias_scale, act, slope, _st()), name)
         return y
-    wp = _packed(w, PACK_FWD, scale)
     split = 0 if g.up else L.ganlab_conv_splitk_plan(g.ref(), 0)
     if split >= 2:     # few output tiles, long contraction (512-channel 4x4 / 8x8 maps, small-batch linears)
         ws = torch.empty((split,) + tuple(y.shape), dtype=torch.float32, device=x.device)
@@ -475,55 +504,39 @@ def k_conv_dgrad(gy, w, g, scale):
     gy, w = _c(gy, 'conv grad_out'), _c(w, 'conv weight')
     assert tuple(gy.shape) == g.out_shape, (tuple(gy.shape), g.out_shape)
     _note('dgrad', g)
-    if g.bf is not None:
-        wp = _packed_bf16(w, PACK_DGRAD, scale)
-        L = _lib.lib()
-
+    fam = conv_route(g, 'dgrad')
+    L = _lib.lib()
+    wp = _packed_for(fam, w, g, scale, dgrad=True)
+    if fam == BF16:
         def run(geom, out):
             split = L.ganlab_conv_bf16_splitk_plan(ctypes.byref(geom), 1)
             if split >= 2:
                 m = 2 if geom.up else 1
                 ws = torch.empty((split * geom.N * geom.Cin * geom.Hin * m * geom.Win * m,), dtype=torch.float32,
                                  device=gy.device)
-                check(L.ganlab_conv_dgrad_bf16_splitk(_p(gy), wp.data_ptr(), _p(out), ctypes.byref(geom), _p(ws),
+                check(L.ganlab_conv_dgrad_bf16_splitk(_p(gy), _p(wp), _p(out), ctypes.byref(geom), _p(ws),
                                                       ws.numel() * 4, _st()), 'conv_dgrad_bf16_splitk')
             else:
-                check(L.ganlab_conv_dgrad_bf16(_p(gy), wp.data_ptr(), _p(out), ctypes.byref(geom), _st()), 'conv_dgrad_bf16')
+                check(L.ganlab_conv_dgrad_bf16(_p(gy), _p(wp), _p(out), ctypes.byref(geom), _st()), 'conv_dgrad_bf16')
             return out
         if g.bf_fused is not None:     # the adjoint of the upsample (2 x 2 sum) / of the pool (upsample / 4) is in the kernel
             return run(g.bf_fused, _new(g.in_shape, gy))
         gxv = run(g.bf, _new((g.N, g.Cin, g.bf.Hin, g.bf.Win), gy))
         return k_pool2(gxv, 1.0) if g.up else gxv
-    if x3_s2_down_ok(g, True):
+    if fam != F32:
         gx = _new(g.in_shape, gy)
-        check(_lib.lib().ganlab_conv_s2_down_dgrad_x3(_p(gy), _packed_x3_s2_down(w, 1, scale).data_ptr(), _p(gx), g.ref(), _st()),
-              'conv_s2_down_dgrad_x3')
+        name = _CONV_ENTRY[fam][1]
+        check(getattr(L, 'ganlab_' + name)(_p(gy), _p(wp), _p(gx), g.ref(), _st()), name)
         return gx
-    if x3_s2_ok(g, True):
-        gx = _new(g.in_shape, gy)
-        check(_lib.lib().ganlab_conv_s2_dgrad_x3(_p(gy), _packed_x3_s2(w, 0, scale).data_ptr(), _p(gx), g.ref(), _st()),
-              'conv_s2_dgrad_x3')
-        return gx
-    if g.s2:
-        wp = _packed(w, PACK_DGRAD, scale, s2_up=g.up)
-        gx = _new(g.in_shape, gy)
-        check(_lib.lib().ganlab_conv_s2_dgrad_f32(_p(gy), _p(wp), _p(gx), g.ref(), _st()), 'conv_s2_dgrad')
-        return gx
-    if x3_ok(g, True):
-        gx = _new(g.in_shape, gy)
-        check(_lib.lib().ganlab_conv_dgrad_x3(_p(gy), _packed_x3(w, PACK_DGRAD, scale).data_ptr(), _p(gx), g.ref(), _st()),
-              'conv_dgrad_x3')
-        return gx
-    wp = _packed(w, PACK_DGRAD, scale)
     hv, wv = (2 * g.Hin, 2 * g.Win) if g.up else (g.Hin, g.Win)
     gxv = _new((g.N, g.Cin, hv, wv), gy)
-    split = 0 if g.up else _lib.lib().ganlab_conv_splitk_plan(g.ref(), 1)
+    split = 0 if g.up else L.ganlab_conv_splitk_plan(g.ref(), 1)
     if split >= 2:
         ws = torch.empty((split,) + tuple(gxv.shape), dtype=torch.float32, device=gy.device)
-        check(_lib.lib().ganlab_conv_dgrad_splitk_f32(_p(gy), _p(wp), _p(gxv), g.ref(), _p(ws), ws.numel() * 4, _st()),
+        check(L.ganlab_conv_dgrad_splitk_f32(_p(gy), _p(wp), _p(gxv), g.ref(), _p(ws), ws.numel() * 4, _st()),
               'conv_dgrad_splitk')
         return gxv
-    check(_lib.lib().ganlab_conv_dgrad_f32(_p(gy), _p(wp), _p(gxv), g.ref(), _st()), 'conv_dgrad')
+    check(L.ganlab_conv_dgrad_f32(_p(gy), _p(wp), _p(gxv), g.ref(), _st()), 'conv_dgrad')
     if g.up:
         return k_pool2(gxv, 1.0)   # adjoint of the nearest upsample
     return gxv
@@ -539,12 +552,10 @@ def k_conv_dgrad_mask(gy, w, x, g, scale, slope):
     assert tuple(gy.shape) == g.out_shape and tuple(x.shape) == g.in_shape
     _note('dgrad', g)
     gx = torch.empty_like(x)
-    if x3_ok(g, True):
-        check(_lib.lib().ganlab_conv_dgrad_mask_x3(_p(gy), _packed_x3(w, PACK_DGRAD, scale).data_ptr(), _p(x), _p(gx), g.ref(),
-                                                   slope, _st()), 'conv_dgrad_mask_x3')
-        return gx
-    check(_lib.lib().ganlab_conv_dgrad_mask_f32(_p(gy), _p(_packed(w, PACK_DGRAD, scale)), _p(x), _p(gx), g.ref(), slope,
-                                                _st()), 'conv_dgrad_mask')
+    fam = _route_among(g, 'dgrad', (X3,))
+    name = 'conv_dgrad_mask_x3' if fam == X3 else 'conv_dgrad_mask_f32'
+    check(getattr(_lib.lib(), 'ganlab_' + name)(_p(gy), _p(_packed_for(fam, w, g, scale, dgrad=True)), _p(x), _p(gx), g.ref(),
+                                                slope, _st()), name)
     return gx
 
 
@@ -642,7 +653,6 @@ def k_conv_fwd_blur_bits(x, w, bias, g, scale, bias_scale, slope):
 def conv_s2_blur_ok(g):
     """Does the thin transposed stride-2 kernel with the blur folded in (csrc/conv_s2_roll_blur.hip) take geometry ``g`` - an
     up layer for the generator's forward tail, a pooled layer for the critic's backward?"""
-    import os
     if get_compute_dtype() != 'f32' or g.bf is not None or not g.s2 or os.environ.get('GANLAB_S2_ROLL_BLUR') == '0':
         return False
     key = ('s2blur', g.N, g.Cin, g.Hin, g.Win, g.Cout, g.up, g.pool)
@@ -698,9 +708,10 @@ def k_conv_wgrad(gy, x, g, scale):
     _note('wgrad', g)
     L = _lib.lib()
     gw = _take('gw', (g.Cout, g.Cin, g.ks, g.ks), x)
-    if x3_wgrad_ok(g):
+    fam = conv_route(g, 'wgrad')
+    if fam in (X3, X3_UP, X3_DOWN):
         return _wgrad_x3(gy, x, None, None, gw, g, scale)
-    if g.bf is not None:
+    if fam == BF16:
         if g.bf_fused is not None:
             # the rolling-row kernel reads the half-resolution operand (x of conv(up2 x), gy of pool2(conv x)) in place
             nbytes = L.ganlab_conv_wgrad_bf16_workspace(ctypes.byref(g.bf_fused))
@@ -727,18 +738,10 @@ def k_conv_wgrad(gy, x, g, scale):
         check(L.ganlab_conv_wgrad_bf16(_p(gy), _p(xin), _p(gw), ctypes.byref(g.bf), scale, _p(ws), ws.numel() * 4,
                                        _st()), 'conv_wgrad_bf16')
         return gw
-    if g.s2:
-        if x3_s2_wgrad_ok(g):
-            return _wgrad_x3_s2(gy, x, None, None, gw, g, scale)
-        nbytes = L.ganlab_conv_s2_wgrad_workspace(g.ref())
-        ws = torch.empty((max(nbytes, 4) + 3) // 4, dtype=torch.float32, device=x.device)
-        check(L.ganlab_conv_s2_wgrad_f32(_p(gy), _p(x), _p(gw), g.ref(), scale, _p(ws), ws.numel() * 4, _st()),
-              'conv_s2_wgrad')
-        return gw
-    nbytes = L.ganlab_conv_wgrad_workspace(g.ref())
+    name = 'conv_s2_wgrad' if fam == S2 else 'conv_wgrad'
+    nbytes = getattr(L, f'ganlab_{name}_workspace')(g.ref())
     ws = torch.empty((max(nbytes, 4) + 3) // 4, dtype=torch.float32, device=x.device)
-    check(L.ganlab_conv_wgrad_f32(_p(gy), _p(x), _p(gw), g.ref(), scale, _p(ws), ws.numel() * 4, _st()),
-          'conv_wgrad')
+    check(getattr(L, f'ganlab_{name}_f32')(_p(gy), _p(x), _p(gw), g.ref(), scale, _p(ws), ws.numel() * 4, _st()), name)
     return gw
 
 
@@ -749,7 +752,6 @@ def mask_bits_ok(x):
     """The LeakyReLU backward of this (N,C,H,W) activation can run from its sign BITS (rows of whole 32-bit words):
     GANLAB_MASK_BITS=0 keeps the float tensor (A/B knob)."""
     if _MASK_BITS[0] is None:
-        import os
         _MASK_BITS[0] = os.environ.get('GANLAB_MASK_BITS') != '0'
     return _MASK_BITS[0] and x.dim() == 4 and bool(_lib.lib().ganlab_mask_bits_supported(int(x.shape[2]), int(x.shape[3])))
 
@@ -757,7 +759,6 @@ def mask_bits_ok(x):
 def mask_bits_ok_plane():
     """The A/B knob alone (GANLAB_MASK_BITS): callers check the plane size themselves."""
     if _MASK_BITS[0] is None:
-        import os
         _MASK_BITS[0] = os.environ.get('GANLAB_MASK_BITS') != '0'
     return _MASK_BITS[0]
 
@@ -1059,7 +1060,6 @@ class RgbHandoff(object):
 
 def _rgb_fold_ok(h, g):
     """May the input gradient of the conv with geometry ``g`` swallow the backward of the fromRGB layer ``h`` describes?"""
-    import os
     if h is None or h.bits is None or torch.is_grad_enabled() or not _DIRECT[0] or not _want_param_grads() or \
             os.environ.get('GANLAB_RGB_FOLD') == '0' or get_compute_dtype() != 'f32':
         return False
@@ -1503,7 +1503,6 @@ class RgbGradLink(object):
 
 
 def _rgb_link_ok(link, n, c, crgb, hw):
-    import os
     return link is not None and link.readers == 1 and get_compute_dtype() == 'f32' and \
         os.environ.get('GANLAB_TORGB_FOLD') != '0' and \
         bool(_lib.lib().ganlab_instnorm_bwd_rgb_supported(n, c, crgb, hw))
@@ -1707,7 +1706,6 @@ def conv_aff_ok(shape, weight, up=False, padding=1):
 def deferrable(x):
     """A layer output of this shape can stay un-normalised for an affine-on-load consumer: the fused statistics pass
     takes it (plane >= 32x32, rows of whole float4s)."""
-    import os
     if os.environ.get('GANLAB_DEFER') == '0':          # A/B knob: keep the two-pass layer tail of round 1
         return False
     n, c, h, w = x.shape
@@ -1720,22 +1718,11 @@ def k_conv_fwd_aff(a, s_, t_, w, g, scale):
     assert tuple(a.shape) == g.in_shape and tuple(s_.shape) == (g.N, g.Cin) and tuple(t_.shape) == (g.N, g.Cin)
     _note('fwd', g)
     y = _new(g.out_shape, a)
-    L = _lib.lib()
-    if g.up and x3_s2_ok(g):
-        check(L.ganlab_conv_s2_fwd_aff_x3(_p(a), _packed_x3_s2(w, 1, scale).data_ptr(), _p(s_), _p(t_), None, _p(y), g.ref(), 1.0,
-                                          ACT_NONE, 0.2, _st()), 'conv_s2_fwd_aff_x3')
-    elif g.up:
-        assert g.s2
-        wp = _packed(w, PACK_FWD, scale, s2_up=1)
-        check(L.ganlab_conv_s2_fwd_aff_f32(_p(a), _p(wp), _p(s_), _p(t_), None, _p(y), g.ref(), 1.0, ACT_NONE, 0.2, _st()),
-              'conv_s2_fwd_aff')
-    elif x3_ok(g):
-        check(L.ganlab_conv_fwd_aff_x3(_p(a), _packed_x3(w, PACK_FWD, scale).data_ptr(), _p(s_), _p(t_), None, _p(y), g.ref(), 1.0,
-                                       ACT_NONE, 0.2, _st()), 'conv_fwd_aff_x3')
-    else:
-        wp = _packed(w, PACK_FWD, scale)
-        check(L.ganlab_conv_fwd_aff_f32(_p(a), _p(wp), _p(s_), _p(t_), None, _p(y), g.ref(), 1.0, ACT_NONE, 0.2, _st()),
-              'conv_fwd_aff')
+    assert g.s2 or not g.up
+    fam = _route_among(g, 'fwd', _AFF_FAMILIES[g.up])
+    name = {X3_UP: 'conv_s2_fwd_aff_x3', S2: 'conv_s2_fwd_aff_f32', X3: 'conv_fwd_aff_x3', F32: 'conv_fwd_aff_f32'}[fam]
+    check(getattr(_lib.lib(), 'ganlab_' + name)(_p(a), _p(_packed_for(fam, w, g, scale)), _p(s_), _p(t_), None, _p(y), g.ref(),
+                                                1.0, ACT_NONE, 0.2, _st()), name)
     return y
 
 
@@ -1746,18 +1733,13 @@ def k_conv_wgrad_aff(gy, a, s_, t_, g, scale):
     _note('wgrad', g)
     L = _lib.lib()
     gw = _take('gw', (g.Cout, g.Cin, 3, 3), a)
-    if not g.up and x3_wgrad_ok(g):
+    fam = _route_among(g, 'wgrad', _AFF_FAMILIES[g.up])
+    if fam in (X3, X3_UP):
         return _wgrad_x3(gy, a, _c(s_), _c(t_), gw, g, scale)
-    if g.up and x3_s2_wgrad_ok(g):
-        return _wgrad_x3_s2(gy, a, _c(s_), _c(t_), gw, g, scale)
-    if g.up:
-        ws = torch.empty((max(L.ganlab_conv_s2_wgrad_workspace(g.ref()), 4) + 3) // 4, dtype=torch.float32, device=a.device)
-        check(L.ganlab_conv_s2_wgrad_aff_f32(_p(gy), _p(a), _p(s_), _p(t_), _p(gw), g.ref(), scale, _p(ws), ws.numel() * 4,
-                                             _st()), 'conv_s2_wgrad_aff')
-    else:
-        ws = torch.empty((max(L.ganlab_conv_wgrad_workspace(g.ref()), 4) + 3) // 4, dtype=torch.float32, device=a.device)
-        check(L.ganlab_conv_wgrad_aff_f32(_p(gy), _p(a), _p(s_), _p(t_), _p(gw), g.ref(), scale, _p(ws), ws.numel() * 4,
-                                          _st()), 'conv_wgrad_aff')
+    name = 'conv_s2_wgrad' if g.up else 'conv_wgrad'
+    ws = torch.empty((max(getattr(L, f'ganlab_{name}_workspace')(g.ref()), 4) + 3) // 4, dtype=torch.float32, device=a.device)
+    check(getattr(L, f'ganlab_{name}_aff_f32')(_p(gy), _p(a), _p(s_), _p(t_), _p(gw), g.ref(), scale, _p(ws), ws.numel() * 4,
+                                               _st()), name + '_aff')
     return gw
 
 
@@ -1813,29 +1795,17 @@ class _ConvModTail(Function):
         y = _new((n, cout, h, wd), a_in)
         mean, rstd = _new((n, cout), a_in), _new((n, cout), a_in)
         thin = mod_conv_shape_ok(a_in.shape, w)
-        if not thin and x3_ok(g):                  # thick layer on the split-product kernel, same one-pass form
-            chunks = L.ganlab_conv_fwd_aff_tail_x3_chunks(g.ref())
-            ws = torch.empty((n * cout * chunks * 2,), dtype=torch.float64, device=a_in.device)
-            check(L.ganlab_conv_fwd_aff_tail_x3(_p(a_in), _packed_x3(w, PACK_FWD, scale).data_ptr(), _p(s_in), _p(t_in), _p(bias),
-                                                _p(noise), _p(noise_w), _p(y), _p(mean), _p(rstd), g.ref(), bias_scale, act, slope,
-                                                eps, _p(ws), ws.numel() * 8, _st()), 'conv_fwd_aff_tail_x3')
-            wp = None
-        else:
-            wp = _packed(w, PACK_FWD, scale)
-        if wp is None:
-            pass
+        fam = F32 if thin else _route_among(g, 'fwd', (X3,))
+        if fam == X3:                              # thick layer on the split-product kernel, same one-pass form
+            name, chunks = 'conv_fwd_aff_tail_x3', L.ganlab_conv_fwd_aff_tail_x3_chunks(g.ref())
         elif thin:                                 # thin layer: the rolling-window kernel
-            chunks = L.ganlab_mod_conv_stat_chunks(g.ref())
-            ws = torch.empty((n * cout * chunks * 2,), dtype=torch.float64, device=a_in.device)
-            check(L.ganlab_mod_conv_fwd_f32(_p(a_in), _p(wp), _p(s_in), _p(t_in), _p(bias), _p(noise), _p(noise_w), _p(y),
-                                            _p(mean), _p(rstd), g.ref(), bias_scale, act, slope, eps, _p(ws), ws.numel() * 8,
-                                            _st()), 'mod_conv_fwd')
+            name, chunks = 'mod_conv_fwd_f32', L.ganlab_mod_conv_stat_chunks(g.ref())
         else:                                      # thicker layers: the tile kernels' TAIL epilogue
-            chunks = L.ganlab_conv_fwd_aff_tail_chunks(g.ref())
-            ws = torch.empty((n * cout * chunks * 2,), dtype=torch.float64, device=a_in.device)
-            check(L.ganlab_conv_fwd_aff_tail_f32(_p(a_in), _p(wp), _p(s_in), _p(t_in), _p(bias), _p(noise), _p(noise_w), _p(y),
-                                                 _p(mean), _p(rstd), g.ref(), bias_scale, act, slope, eps, _p(ws),
-                                                 ws.numel() * 8, _st()), 'conv_fwd_aff_tail')
+            name, chunks = 'conv_fwd_aff_tail_f32', L.ganlab_conv_fwd_aff_tail_chunks(g.ref())
+        ws = torch.empty((n * cout * chunks * 2,), dtype=torch.float64, device=a_in.device)
+        check(getattr(L, 'ganlab_' + name)(_p(a_in), _p(_packed_for(fam, w, g, scale)), _p(s_in), _p(t_in), _p(bias), _p(noise),
+                                           _p(noise_w), _p(y), _p(mean), _p(rstd), g.ref(), bias_scale, act, slope, eps, _p(ws),
+                                           ws.numel() * 8, _st()), name)
         style_c = _c(style) if style is not None else None
         s_, t_ = _affine_from_stats(mean, rstd, style_c, n, cout)
         ctx.save_for_backward(a_in, s_in, t_in, w, y, mean, rstd, style_c, noise)

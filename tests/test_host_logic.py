@@ -603,3 +603,29 @@ def test_x3_support_predicates_refuse_what_the_launchers_refuse(case):
         for role, (dgrad, fields) in geoms(*shape).items():
             g = _lib.ConvGeom(*fields)
             assert pred(ctypes.byref(g), dgrad) == want, (kernel, limit, role, shape)
+
+
+def test_conv_route_names_the_recorded_families():
+    """``ops.conv_route`` on every row of the dispatch census (tests/conv_census.py), against the kernels the commit before it
+    launched for that row (tests/golden/conv_census.json): only predicates run, so the routing order is pinned without a GPU.  The
+    table must reach every family and every packed layout."""
+    import conv_census as C
+    from gan_lab_amd import _lib, ops
+    if not os.path.exists(_lib.SO_PATH):
+        _lib.build()
+    recorded = C.load()
+    assert sorted(recorded) == sorted(r[0] for r in C.ROWS)
+    assert ops.x3_enabled() and ops._X3_MIN_TILES == 128 and ops.get_compute_dtype() == 'f32'
+    families, packs = set(), set()
+    for row in C.ROWS:
+        first, second = recorded[row[0]]
+        g = C.geom_of(ops, row)
+        assert C.admitted(ops, row, g), row[0]
+        want = C.family_of(row, second)
+        assert ops.conv_route(g, row[1]) == want, (row[0], want)
+        families.add(want)
+        packs |= C.pack_rows_of(first)
+        if want in ops._PACK_ROWS and row[1] != 'wgrad':        # the family packs into the row of its name
+            assert C.pack_rows_of(first) == {want}, (row[0], first)
+    assert families == set(C.FAMILIES) == {ops.BF16, ops.X3, ops.X3_UP, ops.X3_DOWN, ops.S2, ops.LINEAR, ops.F32}
+    assert packs == set(ops._PACK_ROWS)
