@@ -39,6 +39,10 @@ inline int pw_contig() {
   return v;
 }
 
+// 16-byte alignment of every pointer given (NULL counts as aligned): a contiguous view may start at any element
+template <class... P>
+inline bool aligned16(const P*... p) { return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0; }
+
 #define GRID_STRIDE(i, n) \
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
 
@@ -692,11 +696,11 @@ __global__ void channel_sum_stage2(const double* __restrict__ part, float* __res
 // grid (chunks, C); partial sums go to part[c][chunk], channel_sum_stage2 finishes them.
 __global__ __launch_bounds__(256) void act_bwd_bias_stage1(const float* __restrict__ gy, const float* __restrict__ y,
                                                            float* __restrict__ gz, double* __restrict__ part, int N,
-                                                           int C, long long HW, int chunks, float slope) {
+                                                           int C, long long HW, int chunks, float slope, int vec) {
   __shared__ double red[4];
   const int c = blockIdx.y, chunk = blockIdx.x;
   double s = 0.0;
-  if ((HW & 3) == 0) {
+  if (vec) {      // HW % 4 == 0 and gy / y / gz 16-byte aligned (decided by the host)
     const long long hw4 = HW >> 2, total = (long long)N * hw4;
     for (long long i = chunk * 256LL + threadIdx.x; i < total; i += (long long)chunks * 256) {
       const long long n = i / hw4, q = i - n * hw4;
@@ -1014,7 +1018,7 @@ __global__ __launch_bounds__(256) void instnorm_bwd_reduce_kernel(const float* _
                                                                   const float* __restrict__ mean,
                                                                   const float* __restrict__ rstd,
                                                                   float* __restrict__ s1, float* __restrict__ s2,
-                                                                  long long planes, long long HW) {
+                                                                  long long planes, long long HW, int vec) {
   __shared__ double red[2][4];
   const int sub = (T == 64) ? (threadIdx.x >> 6) : 0;
   const int t = (T == 64) ? (threadIdx.x & 63) : threadIdx.x;
@@ -1024,7 +1028,7 @@ __global__ __launch_bounds__(256) void instnorm_bwd_reduce_kernel(const float* _
     const float m = mean[pl], r = rstd[pl];
     const float* pg = gy + pl * HW;
     const float* px = x + pl * HW;
-    if ((HW & 3) == 0) {
+    if (vec) {      // HW % 4 == 0 and gy / x 16-byte aligned (decided by the host)
       for (long long i = t; i < (HW >> 2); i += T) {
         const float4 g = reinterpret_cast<const float4*>(pg)[i];
         const float4 v = reinterpret_cast<const float4*>(px)[i];
@@ -1756,8 +1760,9 @@ int ganlab_act_bwd_bias_f32(const float* gy, const float* y, float* gz, float* g
   if (!gy || !y || !gz || !gb || N <= 0 || C <= 0 || HW <= 0) return GANLAB_EINVAL;
   const int chunks = channel_chunks(N, HW);
   if (!workspace || workspace_bytes < (size_t)C * chunks * sizeof(double)) return GANLAB_EWORKSPACE;
+  const int vec = ((HW & 3) == 0 && aligned16(gy, y, gz)) ? 1 : 0;
   GL_LAUNCH(act_bwd_bias_stage1, dim3(chunks, C), dim3(256), 0, ST, gy, y, gz, (double*)workspace, N, C, HW, chunks,
-            slope);
+            slope, vec);
   GL_LAUNCH(channel_sum_stage2, dim3(C), dim3(64), 0, ST, (const double*)workspace, gb, C, chunks, scale);
   return GL_CHECK_LAUNCH();
 }
@@ -1772,7 +1777,7 @@ size_t ganlab_blur_fused_workspace(int N, int C, int H, int W) {
 int ganlab_blur_bias_act_f32(const float* x, const float* bias, const float* noise, const float* noise_w, float* y,
                              int N, int C, int H, int W, float bias_scale, int act, float slope, void* stream) {
   if (!x || !y || N <= 0 || C <= 0 || (noise && !noise_w)) return GANLAB_EINVAL;
-  if (!ganlab_blur_fused_supported(H, W)) return GANLAB_EUNSUPPORTED;
+  if (!ganlab_blur_fused_supported(H, W) || !aligned16(x, noise, y)) return GANLAB_EUNSUPPORTED;
   const int chunks = blur_fused_chunks(N, H, W);
   BLUR_FUSED_LAUNCH(BF_FWD, x, (const float*)nullptr, noise, bias, noise_w, y, (double*)nullptr, N, C, H, W, chunks,
                     bias_scale, act, slope, 0);
@@ -1799,7 +1804,7 @@ int ganlab_instnorm_style_bwd_act_f32(const float* gy, const float* x, const flo
                                       void* stream) {
   if (!gy || !x || !mean || !rstd || !s1 || !s2 || !gz || N <= 0 || C <= 0 || HW <= 0 || (gnw && !noise))
     return GANLAB_EINVAL;
-  if ((HW & 3) != 0) return GANLAB_EUNSUPPORTED;
+  if ((HW & 3) != 0 || !aligned16(gy, x, noise, gz)) return GANLAB_EUNSUPPORTED;
   if ((gb || gnw) && (!workspace || workspace_bytes < ganlab_instnorm_bwd_act_workspace(N, C, HW)))
     return GANLAB_EWORKSPACE;
   const long long hw4 = HW / 4, planes = (long long)N * C;
@@ -1838,7 +1843,7 @@ int ganlab_instnorm_style_bwd_reduce_rgb_f32(const float* grgb, const float* wp,
                                              const float* mean, const float* rstd, float* s1, float* s2, int N, int C,
                                              long long HW, void* workspace, size_t workspace_bytes, void* stream) {
   if (!grgb || !wp || !x || !mean || !rstd || !s1 || !s2) return GANLAB_EINVAL;
-  if (!ganlab_instnorm_bwd_rgb_supported(N, C, crgb, HW)) return GANLAB_EUNSUPPORTED;
+  if (!ganlab_instnorm_bwd_rgb_supported(N, C, crgb, HW) || !aligned16(grgb, x)) return GANLAB_EUNSUPPORTED;
   if (!workspace || workspace_bytes < ganlab_instnorm_bwd_reduce_rgb_workspace(N, C, HW)) return GANLAB_EWORKSPACE;
   const long long hw4 = HW / 4, planes = (long long)N * C;
   const int chunks = act_stats_chunks(hw4);
@@ -1860,7 +1865,7 @@ int ganlab_instnorm_style_bwd_act_rgb_f32(const float* grgb, const float* wp, in
                                           int act, float slope, float bias_scale, void* workspace, size_t workspace_bytes,
                                           void* stream) {
   if (!grgb || !wp || !x || !mean || !rstd || !s1 || !s2 || !gz || (gnw && !noise)) return GANLAB_EINVAL;
-  if (!ganlab_instnorm_bwd_rgb_supported(N, C, crgb, HW)) return GANLAB_EUNSUPPORTED;
+  if (!ganlab_instnorm_bwd_rgb_supported(N, C, crgb, HW) || !aligned16(grgb, x, noise, gz)) return GANLAB_EUNSUPPORTED;
   if ((gb || gnw) && (!workspace || workspace_bytes < ganlab_instnorm_bwd_act_workspace(N, C, HW)))
     return GANLAB_EWORKSPACE;
   const long long hw4 = HW / 4;
@@ -1889,7 +1894,7 @@ int ganlab_instnorm_style_bwd_act_blur_f32(const float* gy, const float* x, cons
                                            float slope, float bias_scale, void* workspace, size_t workspace_bytes,
                                            void* stream) {
   if (!gy || !x || !mean || !rstd || !s1 || !s2 || !out || N <= 0 || C <= 0 || (gnw && !noise)) return GANLAB_EINVAL;
-  if (!ganlab_blur_fused_supported(H, W) || N > 65535 || C > 65535) return GANLAB_EUNSUPPORTED;
+  if (!ganlab_blur_fused_supported(H, W) || N > 65535 || C > 65535 || !aligned16(gy, x, noise, out)) return GANLAB_EUNSUPPORTED;
   const long long HW = (long long)H * W;
   if ((gb || gnw) && (!workspace || workspace_bytes < ganlab_instnorm_bwd_act_workspace(N, C, HW))) return GANLAB_EWORKSPACE;
   const int rows = blur_rows(H);
@@ -1917,7 +1922,7 @@ int ganlab_bias_act_stats_f32(const float* x, const float* bias, const float* no
                               float* mean, float* rstd, int N, int C, long long HW, float bias_scale, int act,
                               float slope, float eps, void* workspace, size_t workspace_bytes, void* stream) {
   if (!x || !y || !mean || !rstd || N <= 0 || C <= 0 || HW <= 0 || (noise && !noise_w)) return GANLAB_EINVAL;
-  if ((HW & 3) != 0) return GANLAB_EUNSUPPORTED;
+  if ((HW & 3) != 0 || !aligned16(x, noise, y)) return GANLAB_EUNSUPPORTED;
   if (!workspace || workspace_bytes < ganlab_act_stats_workspace(N, C, HW)) return GANLAB_EWORKSPACE;
   const long long hw4 = HW / 4, planes = (long long)N * C;
   const int chunks = act_stats_chunks(hw4);
@@ -1935,7 +1940,7 @@ int ganlab_blur_bias_act_stats_f32(const float* x, const float* bias, const floa
                                    int act, float slope, float eps, void* workspace, size_t workspace_bytes,
                                    void* stream) {
   if (!x || !y || !mean || !rstd || N <= 0 || C <= 0 || (noise && !noise_w)) return GANLAB_EINVAL;
-  if (!ganlab_blur_fused_supported(H, W)) return GANLAB_EUNSUPPORTED;
+  if (!ganlab_blur_fused_supported(H, W) || !aligned16(x, noise, y)) return GANLAB_EUNSUPPORTED;
   if (!workspace || workspace_bytes < ganlab_act_stats_workspace(N, C, (long long)H * W)) return GANLAB_EWORKSPACE;
   const int rows = blur_rows_mode(H, BF_FWD);
   long long per_n = (long long)(H / rows) * (W / 4);
@@ -1962,7 +1967,7 @@ int ganlab_blur_bias_act_stats_f32(const float* x, const float* bias, const floa
 int ganlab_blur_act_bwd_f32(const float* g, const float* y, float* out, float* gb, int N, int C, int H, int W,
                             float slope, float bias_scale, void* workspace, size_t workspace_bytes, void* stream) {
   if (!g || !y || !out || N <= 0 || C <= 0) return GANLAB_EINVAL;
-  if (!ganlab_blur_fused_supported(H, W)) return GANLAB_EUNSUPPORTED;
+  if (!ganlab_blur_fused_supported(H, W) || !aligned16(g, y, out)) return GANLAB_EUNSUPPORTED;
   const int chunks = blur_fused_chunks(N, H, W);
   if (gb && (!workspace || workspace_bytes < (size_t)C * chunks * sizeof(double))) return GANLAB_EWORKSPACE;
   BLUR_FUSED_LAUNCH(BF_A, g, y, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, out,
@@ -1975,7 +1980,7 @@ int ganlab_blur_act_bwd_f32(const float* g, const float* y, float* out, float* g
 int ganlab_blur_act_bwd_bits_f32(const float* g, const unsigned* ybits, float* out, float* gb, int N, int C, int H, int W,
                                  float slope, float bias_scale, void* workspace, size_t workspace_bytes, void* stream) {
   if (!g || !ybits || !out || N <= 0 || C <= 0) return GANLAB_EINVAL;
-  if (!ganlab_blur_fused_supported(H, W) || !ganlab_mask_bits_supported(H, W)) return GANLAB_EUNSUPPORTED;
+  if (!ganlab_blur_fused_supported(H, W) || !ganlab_mask_bits_supported(H, W) || !aligned16(g, out)) return GANLAB_EUNSUPPORTED;
   const int chunks = blur_fused_chunks(N, H, W);
   if (gb && (!workspace || workspace_bytes < (size_t)C * chunks * sizeof(double))) return GANLAB_EWORKSPACE;
   BLUR_FUSED_LAUNCH_BITS(BF_A, g, reinterpret_cast<const float*>(ybits), (const float*)nullptr, (const float*)nullptr,
@@ -1989,7 +1994,8 @@ int ganlab_act_bwd_blur_bits_f32(const float* g, const unsigned* ybits, const fl
                                  float* gnw, int N, int C, int H, int W, float slope, float bias_scale, void* workspace,
                                  size_t workspace_bytes, void* stream) {
   if (!g || !ybits || !out || N <= 0 || C <= 0 || (gnw && !noise)) return GANLAB_EINVAL;
-  if (!ganlab_blur_fused_supported(H, W) || !ganlab_mask_bits_supported(H, W)) return GANLAB_EUNSUPPORTED;
+  if (!ganlab_blur_fused_supported(H, W) || !ganlab_mask_bits_supported(H, W) || !aligned16(g, noise, out))
+    return GANLAB_EUNSUPPORTED;
   const int chunks = blur_fused_chunks(N, H, W);
   const int sums = (gb || gnw) ? 1 : 0;
   if (sums && (!workspace || workspace_bytes < (size_t)2 * C * chunks * sizeof(double))) return GANLAB_EWORKSPACE;
@@ -2007,7 +2013,7 @@ int ganlab_act_bwd_blur_f32(const float* g, const float* y, const float* noise, 
                             int N, int C, int H, int W, float slope, float bias_scale, void* workspace,
                             size_t workspace_bytes, void* stream) {
   if (!g || !y || !out || N <= 0 || C <= 0 || (gnw && !noise)) return GANLAB_EINVAL;
-  if (!ganlab_blur_fused_supported(H, W)) return GANLAB_EUNSUPPORTED;
+  if (!ganlab_blur_fused_supported(H, W) || !aligned16(g, y, noise, out)) return GANLAB_EUNSUPPORTED;
   const int chunks = blur_fused_chunks(N, H, W);
   const int sums = (gb || gnw) ? 1 : 0;
   if (sums && (!workspace || workspace_bytes < (size_t)2 * C * chunks * sizeof(double))) return GANLAB_EWORKSPACE;
@@ -2067,13 +2073,14 @@ int ganlab_instnorm_style_fwd_f32(const float* x, const float* mean, const float
     const int v = e ? atoi(e) : 2;
     return (v == 0 || v == 2 || v == 4 || v == 8) ? v : 2;
   }();
-  if (chunk_u > 0 && HW % (1024 * 8) == 0 && (long long)N * C * (HW / (1024 * chunk_u)) < 0x7fffffffLL) {
+  const bool al = aligned16(x, y);      // the float4 forms need both; a misaligned view takes the scalar kernel
+  if (al && chunk_u > 0 && HW % (1024 * 8) == 0 && (long long)N * C * (HW / (1024 * chunk_u)) < 0x7fffffffLL) {
     const int chunks = (int)(HW / (1024 * chunk_u));
     const unsigned grid = (unsigned)((long long)N * C * chunks);
     if (chunk_u == 8) GL_LAUNCH(instnorm_style_fwd_chunk_kernel<8>, dim3(grid), dim3(256), 0, ST, x, mean, rstd, style, y, C, chunks, HW);
     else if (chunk_u == 2) GL_LAUNCH(instnorm_style_fwd_chunk_kernel<2>, dim3(grid), dim3(256), 0, ST, x, mean, rstd, style, y, C, chunks, HW);
     else GL_LAUNCH(instnorm_style_fwd_chunk_kernel<4>, dim3(grid), dim3(256), 0, ST, x, mean, rstd, style, y, C, chunks, HW);
-  } else if ((HW & 3) == 0)
+  } else if (al && (HW & 3) == 0)
     GL_LAUNCH(instnorm_style_fwd_kernel<4>, dim3(ew_blocks((long long)N * C * HW / 4)), dim3(256), 0, ST,
                        x, mean, rstd, style, y, N, C, HW);
   else
@@ -2085,12 +2092,13 @@ int ganlab_instnorm_style_fwd_f32(const float* x, const float* mean, const float
 int ganlab_instnorm_style_bwd_reduce_f32(const float* gy, const float* x, const float* mean, const float* rstd,
                                          float* s1, float* s2, long long planes, long long HW, void* stream) {
   if (!gy || !x || !mean || !rstd || !s1 || !s2 || planes <= 0 || HW <= 0) return GANLAB_EINVAL;
+  const int vec = ((HW & 3) == 0 && aligned16(gy, x)) ? 1 : 0;
   if (HW >= 1024)
     GL_LAUNCH(instnorm_bwd_reduce_kernel<256>, dim3((unsigned)planes), dim3(256), 0, ST, gy, x, mean,
-                       rstd, s1, s2, planes, HW);
+                       rstd, s1, s2, planes, HW, vec);
   else
     GL_LAUNCH(instnorm_bwd_reduce_kernel<64>, dim3((unsigned)((planes + 3) / 4)), dim3(256), 0, ST, gy, x,
-                       mean, rstd, s1, s2, planes, HW);
+                       mean, rstd, s1, s2, planes, HW, vec);
   return GL_CHECK_LAUNCH();
 }
 
@@ -2098,7 +2106,7 @@ int ganlab_instnorm_style_bwd_apply_f32(const float* gy, const float* x, const f
                                         const float* style, const float* s1, const float* s2, float* gx, int N,
                                         int C, long long HW, void* stream) {
   if (!gy || !x || !mean || !rstd || !s1 || !s2 || !gx || N <= 0 || C <= 0 || HW <= 0) return GANLAB_EINVAL;
-  if ((HW & 3) == 0)
+  if ((HW & 3) == 0 && aligned16(gy, x, gx))
     GL_LAUNCH(instnorm_bwd_apply_kernel<4>, dim3(ew_blocks((long long)N * C * HW / 4)), dim3(256), 0, ST,
                        gy, x, mean, rstd, style, s1, s2, gx, N, C, HW);
   else

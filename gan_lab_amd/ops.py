@@ -766,7 +766,7 @@ def mask_bits_ok_plane():
 def k_blur_bits(x):
     """(blur(x), sign bits of x): the bits are all the LeakyReLU backward of x's producer needs (int32 words, bit e of the
     NCHW-linear element index e set iff x[e] > 0)."""
-    x = _c(x)
+    x = _aligned16(_c(x))         # (these kernels only have float4 forms: a view that starts off a 16-byte boundary is copied)
     n, c, h, w = x.shape
     y = torch.empty_like(x)
     bits = torch.empty((x.numel() // 32,), dtype=torch.int32, device=x.device)
@@ -790,11 +790,11 @@ def _blur_ws(x):
 
 
 def k_blur_bias_act(x, bias, noise, noise_w, bias_scale, act, slope):
-    x = _c(x)
+    x = _aligned16(_c(x))
     n, c, h, w = x.shape
     bias = _c(bias) if bias is not None else None
     if noise is not None:
-        noise, noise_w = _c(noise), _c(noise_w)
+        noise, noise_w = _aligned16(_c(noise)), _c(noise_w)
         assert noise.numel() == n * h * w and noise_w.numel() == c
     y = torch.empty_like(x)
     check(_lib.lib().ganlab_blur_bias_act_f32(_p(x), _p(bias), _p(noise), _p(noise_w), _p(y), n, c, h, w, bias_scale,
@@ -810,11 +810,11 @@ def _stats_out(x, n, c, hw):
 
 def k_blur_bias_act_stats(x, bias, noise, noise_w, bias_scale, act, slope, eps):
     """k_blur_bias_act that also returns the InstanceNorm statistics (mean, rstd) of its output."""
-    x = _c(x)
+    x = _aligned16(_c(x))
     n, c, h, w = x.shape
     bias = _c(bias) if bias is not None else None
     if noise is not None:
-        noise, noise_w = _c(noise), _c(noise_w)
+        noise, noise_w = _aligned16(_c(noise)), _c(noise_w)
         assert noise.numel() == n * h * w and noise_w.numel() == c
     y = torch.empty_like(x)
     mean, rstd, ws = _stats_out(x, n, c, h * w)
@@ -825,11 +825,11 @@ def k_blur_bias_act_stats(x, bias, noise, noise_w, bias_scale, act, slope, eps):
 
 
 def k_bias_act_stats(x, bias, noise, noise_w, bias_scale, act, slope, eps):
-    x = _c(x)
+    x = _aligned16(_c(x))
     n, c, hw = _nchw(x)
     y = torch.empty_like(x)
     bias = _c(bias) if bias is not None else None
-    noise = _c(noise) if noise is not None else None
+    noise = _aligned16(_c(noise)) if noise is not None else None
     noise_w = _c(noise_w) if noise_w is not None else None
     if noise is not None:
         assert noise.numel() == n * hw and noise_w.numel() == c
@@ -842,7 +842,7 @@ def k_bias_act_stats(x, bias, noise, noise_w, bias_scale, act, slope, eps):
 
 def k_blur_act_bwd(g, y, slope, bias_scale, want_gb):
     """``y``: the LeakyReLU output, or its sign bits (``k_blur_bits``)."""
-    g = _c(g)
+    g = _aligned16(_c(g))
     n, c, h, w = g.shape
     out = torch.empty_like(g)
     gb = _take('gb', (c,), g) if want_gb else None
@@ -853,7 +853,7 @@ def k_blur_act_bwd(g, y, slope, bias_scale, want_gb):
                                                       _p(ws), ws.numel() * 4 if ws is not None else 0, _st()),
               'blur_act_bwd_bits')
         return out, gb
-    y = _c(y)
+    y = _aligned16(_c(y))
     assert g.shape == y.shape
     check(_lib.lib().ganlab_blur_act_bwd_f32(_p(g), _p(y), _p(out), _p(gb), n, c, h, w, slope, bias_scale, _p(ws),
                                              ws.numel() * 4 if ws is not None else 0, _st()), 'blur_act_bwd')
@@ -861,7 +861,8 @@ def k_blur_act_bwd(g, y, slope, bias_scale, want_gb):
 
 
 def k_act_bwd_blur(g, y, noise, slope, bias_scale, want_gb, want_gnw):
-    g = _c(g)
+    g = _aligned16(_c(g))
+    noise = _aligned16(_c(noise)) if want_gnw else None
     n, c, h, w = g.shape
     out = torch.empty_like(g)
     gb = _take('gb', (c,), g) if want_gb else None
@@ -869,13 +870,13 @@ def k_act_bwd_blur(g, y, noise, slope, bias_scale, want_gb, want_gnw):
     ws = _blur_ws(g) if (want_gb or want_gnw) else None
     if _is_bits(y):
         assert y.numel() * 32 == g.numel()
-        check(_lib.lib().ganlab_act_bwd_blur_bits_f32(_p(g), y.data_ptr(), _p(_c(noise)) if want_gnw else None, _p(out),
+        check(_lib.lib().ganlab_act_bwd_blur_bits_f32(_p(g), y.data_ptr(), _p(noise), _p(out),
                                                       _p(gb), _p(gnw), n, c, h, w, slope, bias_scale, _p(ws),
                                                       ws.numel() * 4 if ws is not None else 0, _st()), 'act_bwd_blur_bits')
         return out, gb, gnw
-    y = _c(y)
+    y = _aligned16(_c(y))
     assert g.shape == y.shape
-    check(_lib.lib().ganlab_act_bwd_blur_f32(_p(g), _p(y), _p(_c(noise)) if want_gnw else None, _p(out), _p(gb),
+    check(_lib.lib().ganlab_act_bwd_blur_f32(_p(g), _p(y), _p(noise), _p(out), _p(gb),
                                              _p(gnw), n, c, h, w, slope, bias_scale, _p(ws),
                                              ws.numel() * 4 if ws is not None else 0, _st()), 'act_bwd_blur')
     return out, gb, gnw
@@ -1439,7 +1440,7 @@ class _LayerTail(Function):
     @staticmethod
     def forward(ctx, x, bias, noise, noise_w, style, bias_scale, act, slope, blur, eps):
         kern = k_blur_bias_act_stats if blur else k_bias_act_stats
-        noise = _c(noise) if noise is not None else None
+        noise = _aligned16(_c(noise)) if noise is not None else None
         y, mean, rstd = kern(x, bias, noise, noise_w, bias_scale, act, slope, eps)
         n, c, hw = _nchw(y)
         style_c = _c(style) if style is not None else None
@@ -1521,6 +1522,7 @@ def _layer_tail_backward(ctx, saved_tail, gout, blur=False):
     ``blur``: the tail sits behind a blur - the (self-adjoint) blur of gz runs in the SAME pass and gz is never written.
     Returns (gz or blur(gz), gb, gnw, gstyle)."""
     y, mean, rstd, style, noise = saved_tail
+    noise = _aligned16(noise) if noise is not None else None
     n, c, hw = _nchw(y)
     L = _lib.lib()
     rgb = getattr(ctx, 'link', None)
@@ -1532,7 +1534,7 @@ def _layer_tail_backward(ctx, saved_tail, gout, blur=False):
     s1, s2 = _new((n, c), y), _new((n, c), y)
     if rgb is not None:            # ``gout`` is toRGB's placeholder: the gradient is recomputed from the image gradient
         assert not blur
-        grgb, wp_rgb, crgb = rgb.grgb, rgb.wp, rgb.crgb
+        grgb, wp_rgb, crgb = _aligned16(rgb.grgb), rgb.wp, rgb.crgb
         rgb.grgb = rgb.wp = None
         wsr = torch.empty((L.ganlab_instnorm_bwd_reduce_rgb_workspace(n, c, hw) + 3) // 4, dtype=torch.float32,
                           device=y.device)
@@ -1540,7 +1542,7 @@ def _layer_tail_backward(ctx, saved_tail, gout, blur=False):
                                                          _p(s2), n, c, hw, _p(wsr), wsr.numel() * 4, _st()),
               'instnorm_bwd_reduce_rgb')
     else:
-        gout = _c(gout)
+        gout = _aligned16(_c(gout))     # (the apply passes below only have float4 forms)
         check(L.ganlab_instnorm_style_bwd_reduce_f32(_p(gout), _p(y), _p(mean), _p(rstd), _p(s1), _p(s2), n * c, hw,
                                                      _st()), 'instnorm_bwd_reduce')
     gz = gb = gnw = None
@@ -1590,7 +1592,7 @@ class _LayerTailDeferred(Function):
     @staticmethod
     def forward(ctx, x, bias, noise, noise_w, style, bias_scale, act, slope, blur, eps, link=None):
         kern = k_blur_bias_act_stats if blur else k_bias_act_stats
-        noise = _c(noise) if noise is not None else None
+        noise = _aligned16(_c(noise)) if noise is not None else None
         ctx.link = link
         y, mean, rstd = kern(x, bias, noise, noise_w, bias_scale, act, slope, eps)
         n, c, _ = _nchw(y)
