@@ -32,7 +32,7 @@ def rnd(gen, *shape):
 CONV_CASES = [
     # N, Cin, H, W, Cout, ks, pad, up, bias, act
     (3, 6, 7, 7, 5, 3, 1, False, True, None),          # odd sizes, channel padding
-    (2, 16, 64, 64, 16, 3, 1, False, False, None),     # thin 16->16 (the 1024^2 layer shape, small image)
+    (2, 16, 64, 64, 16, 3, 1, False, False, None),     # thin 16->16 (the 1024^2 layer shape, small image): conv_fwd_roll2_kernel, 16 steps = 8 + 8
     (2, 32, 32, 32, 16, 3, 1, True, False, None),      # upsample folded in: 32@32^2 -> 16@64^2
     (2, 3, 64, 64, 16, 1, 0, False, True, 'lrelu'),    # fromRGB
     (2, 16, 64, 64, 3, 1, 0, False, True, None),       # toRGB
@@ -41,24 +41,24 @@ CONV_CASES = [
     (8, 256, 4, 4, 256, 3, 1, False, True, 'lrelu'),   # 4x4x16 geometry
     (4, 257, 4, 4, 64, 3, 1, False, True, 'lrelu'),    # mbstd-style odd Cin (513 in the real net)
     (2, 32, 8, 8, 32, 3, 1, True, False, None),        # up at small res
-    (1, 16, 128, 96, 16, 3, 1, False, False, None),    # non-square, 32x8 geometry with ragged tiles
+    (1, 16, 128, 96, 16, 3, 1, False, False, None),    # non-square: vertical strip kernel, 32x8 tiles, three column blocks
     (5, 24, 20, 20, 40, 3, 1, False, True, None),      # nothing a power of two
     (8, 16, 16, 16, 16, 3, 1, False, True, 'lrelu'),   # thin layer, 16x16-tile variant of the vertical strip kernel
     (2, 12, 64, 16, 16, 3, 1, False, False, None),     # thin, channel padding (12 -> 16), tall narrow image
-    (2, 16, 24, 64, 16, 3, 1, False, True, None),      # thin, three tile rows of 8: strips with a top / bottom edge each
+    (2, 16, 24, 64, 16, 3, 1, False, True, None),      # thin: rolling forward (conv_fwd_roll2_kernel), 6 steps in one strip
     # split-K (few output tiles, long contraction): forward and input gradient share tiles between S workgroups
     (32, 512, 8, 8, 512, 3, 1, False, True, 'lrelu'),  # the benchmark's 8x8 layer: 256 workgroups -> S = 2
     (32, 513, 4, 4, 512, 3, 1, False, True, 'lrelu'),  # critic's last 3x3 (mbstd channel): S = 4, odd Cin
-    (3, 200, 5, 7, 72, 3, 1, False, True, None),       # ragged everything: 13 K-chunks of 16 -> 25 of 8, S = 4
-    (2, 72, 8, 8, 200, 3, 1, False, False, 'lrelu'),   # 9 K-chunks: S is cut back so no workgroup gets an empty range
+    (3, 200, 5, 7, 72, 3, 1, False, True, None),       # ragged everything: 26 K-chunks of 8, S = 4 (input gradient: S = 2)
+    (2, 72, 8, 8, 200, 3, 1, False, False, 'lrelu'),   # 10 K-chunks of 8: S = 2 (input gradient: 4); a cut-back S: tests/exact_forms.py
     (8, 256, 16, 16, 128, 3, 1, False, True, 'lrelu'), # 16x16 tiles on the vector-staged kernel, S = 4
-    (32, 512, 16, 16, 512, 3, 1, False, True, None),   # the benchmark's 16x16 layer, S = 2
+    (32, 512, 16, 16, 512, 3, 1, False, True, None),   # the benchmark's 16x16 layer: no split-K, the split-product kernels take it
     # rolling-window weight gradient (wgrad_roll.hip: thin layers, W % 64 == 0, H % 4 == 0)
     (3, 12, 40, 64, 10, 3, 1, False, True, None),      # channel padding on both sides, 10 steps in one strip
     (2, 32, 16, 64, 24, 3, 1, False, True, 'lrelu'),   # 2 x 2 channel-tile pairs, ragged co tile
     (1, 5, 72, 192, 32, 3, 1, False, False, None),     # three columns, 18 steps = two strips (16 + 2)
     (2, 16, 8, 128, 16, 3, 1, False, True, None),      # two steps only: prologue + one prefetch
-    (2, 16, 68, 64, 16, 3, 1, False, False, None),     # 17 steps: a strip of one step
+    (2, 16, 68, 64, 16, 3, 1, False, False, None),     # 17 steps: weight-gradient units of 16 + 1; H % 8 != 0, so forward and input gradient run the tile kernel
 ]
 
 
@@ -401,7 +401,7 @@ S2_CASES = [
     # rolling-window 16-tap weight gradient (wgrad_roll.hip): low-resolution width a multiple of 32
     (3, 24, 24, 128, 40, 'pool'),     # channel padding on both operands, two columns, 6 steps
     (1, 40, 6, 64, 12, 'up'),         # three steps, NBA = 2 with a ragged low-channel tile
-    (2, 16, 68, 32, 16, 'up'),        # NBA = 1, 34 steps = two strips (32 + 2)
+    (2, 16, 68, 32, 16, 'up'),        # NBA = 1, 34 steps = three units (16 + 16 + 2)
     (2, 64, 36, 64, 64, 'pool'),      # 2 x 4 channel-tile pairs
     # rolling-window S / T kernels (conv_s2_roll.hip: 16 <-> 32 channels, low-resolution width a multiple of 32)
     (3, 12, 24, 128, 20, 'pool'),     # channel padding on both sides, two column strips, 6 steps; T as its input gradient
