@@ -39,7 +39,7 @@ CASES = [
     (2, 64, 8, 32, 64, False, False, None),       # one tile, one co block, two K chunks
     (2, 128, 16, 64, 64, False, True, 'lrelu'),   # several tiles, 4 K chunks, fused epilogue
     (1, 64, 32, 32, 192, False, True, None),      # 3 co blocks
-    (2, 64, 16, 16, 128, True, False, None),      # nearest upsample in front (materialised, then bf16 conv)
+    (2, 64, 16, 16, 128, True, False, None),      # nearest upsample in front, folded into the kernels: taps at 32 x 32
     (3, 192, 24, 96, 128, False, True, 'lrelu'),  # nothing a power of two except the tile
     (8, 320, 16, 96, 320, False, False, None),    # 25 channel tiles: every weight-gradient pipeline walks 2 segments
     (3, 128, 16, 16, 64, False, True, 'lrelu'),   # 16-wide maps: 16 x 16 pixel tiles; the weight gradient stays fp32
