@@ -290,6 +290,12 @@ SIGNATURES = {
     'ganlab_spectrum_feed_f32': (_c_int, [_c_p, _c_ll, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_sz, _c_p, _c_sz, _c_p]),
     'ganlab_spectrum_finish_f64': (_c_int, [_c_p, _c_p, _c_sz, _c_int, _c_int, _c_p, _c_sz, _c_p]),
     'ganlab_adam_dev_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_f, _c_f, _c_f, _c_f, _c_p]),
+    'ganlab_rmsprop_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
+    'ganlab_rmsprop_dev_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_f, _c_f, _c_f, _c_f, _c_p]),
+    'ganlab_sgd_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_f, _c_f, _c_f, _c_int, _c_p]),
+    'ganlab_sgd_dev_f32': (_c_int, [_c_p, _c_p, _c_p, _c_ll, _c_p, _c_f, _c_f, _c_p]),
+    'ganlab_oadam_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
+    'ganlab_oadam_dev_f32': (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_ll, _c_p, _c_f, _c_f, _c_f, _c_f, _c_p]),
     'ganlab_sn_job_size': (_c_int, []),
     'ganlab_sn_refresh': (_c_int, [_c_p, _c_int, _c_ll, _c_ll, _c_ll, _c_int, _c_f, _c_p]),
     'ganlab_sn_backward': (_c_int, [_c_p, _c_int, _c_ll, _c_p]),

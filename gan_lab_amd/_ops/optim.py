@@ -1,7 +1,8 @@
-"""Whole-network parameter passes: spectral normalisation, orthogonal regularisation, Adam, the step-scalar block, the lagged
-(EWMA) generator.
+"""Whole-network parameter passes: spectral normalisation, orthogonal regularisation, Adam, RMSprop / SGD / optimistic Adam, the
+step-scalar block, the lagged (EWMA) generator.
 
-Drives csrc/spectral.hip, csrc/ortho.hip, csrc/sample.hip (``ewma_many``) and the optimiser entry points of csrc/pointwise.hip;
+Drives csrc/spectral.hip, csrc/ortho.hip, csrc/sample.hip (``ewma_many``), csrc/optim.hip and the optimiser entry points of
+csrc/pointwise.hip;
 composed in gan_lab_amd/spectral_norm.py, ortho_reg.py, optim.py, sampling.py and graphs.py.  Re-exported by ``gan_lab_amd.ops``."""
 import ctypes
 
@@ -190,6 +191,76 @@ def adam_step_dev(p, g, m, v, scalars, beta1, beta2, eps, wd):
                         f'{scalars!r})')
     check(_lib.lib().ganlab_adam_dev_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), ctypes.c_void_p(scalars), beta1, beta2, eps,
                                          wd, _st()), 'adam_dev')
+
+
+# ---- RMSprop, SGD with momentum, optimistic Adam (csrc/optim.hip) ---------------------------------------------------------------
+def _optim_operands(op, named):
+    """The checks ``_adam_operands`` makes, over ``named`` = [(what, tensor)]; a ``None`` tensor (a null ``buf``) is left out."""
+    named = [(what, t) for what, t in named if t is not None]
+    for what, t in named:
+        _inplace(t, f'{op} {what}')
+    _same_numel(op, named)
+
+
+def _dev_scalars(op, scalars):
+    if isinstance(scalars, bool) or not isinstance(scalars, int) or scalars <= 0:
+        raise TypeError(f'gan_lab_amd.ops: {op} scalars must be a device address inside the step-scalar block (got {scalars!r})')
+    return ctypes.c_void_p(scalars)
+
+
+def _momentum_buf(op, momentum, buf):
+    momentum = float(momentum)
+    if not (0.0 <= momentum < float('inf')):
+        raise ValueError(f'gan_lab_amd.ops: {op} momentum must be a finite number >= 0 (got {momentum!r})')
+    if momentum > 0.0 and buf is None:
+        raise TypeError(f'gan_lab_amd.ops: {op} with momentum > 0 needs its momentum buffer (got None)')
+    return momentum, (buf if momentum > 0.0 else None)
+
+
+def rmsprop_step(p, g, sq, buf, lr, alpha, eps, wd, momentum):
+    """One ``torch.optim.RMSprop(centered=False)`` step over flat float32 GPU tensors; ``buf`` is None with ``momentum`` = 0."""
+    momentum, buf = _momentum_buf('rmsprop_step', momentum, buf)
+    _optim_operands('rmsprop_step', [('p', p), ('g', g), ('sq', sq), ('buf', buf)])
+    check(_lib.lib().ganlab_rmsprop_f32(_p(p), _p(g), _p(sq), _p(buf), p.numel(), lr, alpha, eps, wd, momentum, _st()),
+          'rmsprop')
+
+
+def rmsprop_step_dev(p, g, sq, buf, scalars, alpha, eps, wd, momentum):
+    """``rmsprop_step`` with lr read from the first of the three floats at ``scalars`` (a device pointer)."""
+    momentum, buf = _momentum_buf('rmsprop_step_dev', momentum, buf)
+    _optim_operands('rmsprop_step_dev', [('p', p), ('g', g), ('sq', sq), ('buf', buf)])
+    check(_lib.lib().ganlab_rmsprop_dev_f32(_p(p), _p(g), _p(sq), _p(buf), p.numel(), _dev_scalars('rmsprop_step_dev', scalars),
+                                            alpha, eps, wd, momentum, _st()), 'rmsprop_dev')
+
+
+def sgd_step(p, g, buf, lr, wd, momentum, first):
+    """One ``torch.optim.SGD(dampening=0, nesterov=False)`` step; ``first``: the momentum buffer is set to g' instead of updated
+    (torch's first step).  ``buf`` is None with ``momentum`` = 0."""
+    momentum, buf = _momentum_buf('sgd_step', momentum, buf)
+    _optim_operands('sgd_step', [('p', p), ('g', g), ('buf', buf)])
+    check(_lib.lib().ganlab_sgd_f32(_p(p), _p(g), _p(buf), p.numel(), lr, wd, momentum, 1 if first else 0, _st()), 'sgd')
+
+
+def sgd_step_dev(p, g, buf, scalars, wd, momentum):
+    """``sgd_step`` with (lr, first) read from the first two of the three floats at ``scalars``; first = 1.0 on step 1, else 0.0."""
+    momentum, buf = _momentum_buf('sgd_step_dev', momentum, buf)
+    _optim_operands('sgd_step_dev', [('p', p), ('g', g), ('buf', buf)])
+    check(_lib.lib().ganlab_sgd_dev_f32(_p(p), _p(g), _p(buf), p.numel(), _dev_scalars('sgd_step_dev', scalars), wd, momentum,
+                                        _st()), 'sgd_dev')
+
+
+def oadam_step(p, g, m, v, prev, lr, beta1, beta2, eps, wd, bc1, bc2):
+    """One optimistic Adam step (Daskalakis et al. 2018): p -= 2 lr d - lr prev, prev = d, d Adam's bias-corrected direction."""
+    _optim_operands('oadam_step', [('p', p), ('g', g), ('m', m), ('v', v), ('prev', prev)])
+    check(_lib.lib().ganlab_oadam_f32(_p(p), _p(g), _p(m), _p(v), _p(prev), p.numel(), lr, beta1, beta2, eps, wd, bc1, bc2,
+                                      _st()), 'oadam')
+
+
+def oadam_step_dev(p, g, m, v, prev, scalars, beta1, beta2, eps, wd):
+    """``oadam_step`` with (lr, 1 - beta1^t, 1 - beta2^t) read from the three floats at ``scalars`` (a device pointer)."""
+    _optim_operands('oadam_step_dev', [('p', p), ('g', g), ('m', m), ('v', v), ('prev', prev)])
+    check(_lib.lib().ganlab_oadam_dev_f32(_p(p), _p(g), _p(m), _p(v), _p(prev), p.numel(), _dev_scalars('oadam_step_dev', scalars),
+                                          beta1, beta2, eps, wd, _st()), 'oadam_dev')
 
 
 def set_step_scalars(block, rng_base, floats):

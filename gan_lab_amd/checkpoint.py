@@ -216,7 +216,9 @@ def reference_config_fields(config):
     from . import validation
     gen_metrics = getattr(config, 'gen_metrics', None)
     off = tuple(s.name + '_' for s in validation.SCORERS if not s.module.wanted(gen_metrics))    # a set metric's fields: '<name>_*'
-    return saved_config_fields({k: v for k, v in vars(config).items() if not (k == 'diffaugment' and v is None) and
+    from . import optim         # (``momentum`` / ``rmsprop_momentum``: this package's own, never written under Adam)
+    return saved_config_fields({k: v for k, v in optim.saved_config_fields(vars(config)).items()
+                                if not (k == 'diffaugment' and v is None) and
                                 not (k in ('self_attention', 'cgan') and v is None) and not k.startswith(off)})
 
 

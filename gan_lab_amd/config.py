@@ -119,6 +119,16 @@ every level the resolution allows, not LPIPS (no pretrained network ships here):
 numbers.  The metric needs no validation reals and is not available while a resolution fades in (its line then says so).  A
 value outside these ranges, or ``'ppl'`` among ``disc_metrics``, raises ValueError when the learner is built and names its field;
 the ResNet GAN has none of the five fields.
+``optimizer`` (all three models) is ``'adam'`` (the default, unchanged), ``'rmsprop'``, ``'momentum'``, ``'sgd'`` or ``'oadam'``
+(optimistic Adam, Daskalakis et al. 2018); each is a fused arena optimiser of optim.py, one launch per update, and works with the
+LR schedules, step graphs and checkpoints like Adam.  The mapping of fields: ``lr_base``, ``eps`` and ``wd`` are shared by all;
+``'adam'`` and ``'oadam'`` read ``beta1`` / ``beta2``; ``'rmsprop'`` reads alpha = ``beta2`` (torch.optim.RMSprop's smoothing
+constant; ``beta1`` is unused) and its momentum from ``rmsprop_momentum`` (float, default 0.0, in [0, 1)) alone; ``'momentum'`` is
+SGD with the coefficient ``momentum`` (float, default 0.9, in [0, 1), and > 0 for this optimiser); ``'sgd'`` is plain SGD and reads
+neither.  ``beta2``'s default differs by model (0.99 for ProGAN / StyleGAN, 0.9 for the ResNet GAN), so RMSprop's alpha does too;
+these are the user's choice and nothing was tuned here.  A value outside these ranges raises ValueError when the learner is built and
+names its field; a checkpoint saved under one optimiser does not load under another, ``reference_format=True`` needs ``'adam'``,
+and files saved under ``'adam'`` do not carry the two new fields.
 ``--gradient_penalty=none`` on the command line means no penalty (None), as ``make_config(gradient_penalty=None)`` does.
 """
 import argparse
@@ -179,6 +189,7 @@ def _spec(model_type):
         ('prdc_k', int, 5), ('prdc_res', int, 32),
         ('fd_res', int, 16), ('kid_res', int, 32), ('kid_block', int, 1000),
         ('self_attention', _str_or_none, None), ('cgan', _str_or_none, None),
+        ('momentum', float, 0.9), ('rmsprop_momentum', float, 0.0),
     ]
     if model_type == 'ResNet GAN':
         rows += [('batch_size', int, BS), ('num_main_iters', int, 300000), ('num_disc_iters', int, 5),

@@ -13,7 +13,7 @@ name, so ``ops.<name>`` is the one way in for callers:
   _ops/loss.py       minibatch stddev, scalar reductions, BCE / hinge / channel-norm penalty
   _ops/attention.py  attention, 2x2 max pool, gated residual
   _ops/metrics.py    SWD, PRDC, Frechet moments / KID, path length, MS-SSIM, radial spectrum
-  _ops/optim.py      spectral norm, orthogonal regularisation, Adam, EWMA
+  _ops/optim.py      spectral norm, orthogonal regularisation, Adam / RMSprop / SGD / optimistic Adam, EWMA
   _ops/augment.py    random draws, DiffAugment, ADA
   _ops/cond.py       labels, conditional BatchNorm
   _ops/hier.py       hierarchical latents, modulated BatchNorm, class projection
@@ -78,7 +78,8 @@ from ._ops.metrics import (  # noqa: F401
     spectrum_workspace, spectrum_scratch, spectrum_feed, spectrum_finish)
 from ._ops.optim import (  # noqa: F401
     SN_EPS, SnTable, sn_refresh, sn_backward, ortho_plan, OrthoTable, ortho_apply, lerp_rows, _adam_operands, adam_step,
-    adam_step_dev, set_step_scalars, ewma_step, EwmaTable, ewma_many)
+    adam_step_dev, _optim_operands, rmsprop_step, rmsprop_step_dev, sgd_step, sgd_step_dev, oadam_step, oadam_step_dev,
+    set_step_scalars, ewma_step, EwmaTable, ewma_many)
 from ._ops.augment import (  # noqa: F401
     randn, check_truncation, trunc_randn, randn_dev, diffaug_params, diffaug_params_dev, k_diffaug, ADA_ROW, ADA_COUNTERS,
     ada_params, ada_params_dev, k_ada, ADA_EXT_ROW, ADA_EXT_COUNTERS, ADA_FILTER_TAPS, ADA_FILTER, ADA_NOISE, ADA_CUTOUT,

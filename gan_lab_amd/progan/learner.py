@@ -28,7 +28,7 @@ from ..optim import EwmaTracker, ParamArena
 from ..resnetgan.learner import GANLearner
 from ..schedule import FINAL, GROW, STABILISE, PhaseSchedule, ewma_beta
 from ..utils import backprop_utils as bp
-from ..utils.backprop_utils import configure_adam_for_gan
+from ..utils.backprop_utils import configure_optimizer_for_gan
 from ..utils.latent_utils import gen_rand_latent_vars
 from .architectures import ProDiscriminator, ProGenerator
 from .base import ProGAN
@@ -154,15 +154,9 @@ class ProGANLearner(GANLearner):
             self.lagged_params = self.ewma.lagged_params
 
     def _set_optimizer(self):
-        """Fresh Adam (state reset) over the current parameter set; prev_torgb / prev_fromrgb are left
-        out once the fade-in is over (progan/learner.py:1064-1095)."""
-        if self._optimizer != 'adam':
-            if self._optimizer in ('rmsprop', 'momentum', 'sgd'):
-                raise NotImplementedError(f'{self._optimizer} optimizer not yet implemented.')
-            raise ValueError("config does not support this optimizer.\nSupported Optimizers are: "
-                             "[ 'adam', 'rmsprop', 'momentum', 'sgd' ]")
-        c = self.config
-        adam_gan = configure_adam_for_gan(lr_base=c.lr_base, betas=(c.beta1, c.beta2), eps=c.eps, wd=c.wd)
+        """Fresh optimisers (state reset) of ``config.optimizer`` over the current parameter set; prev_torgb / prev_fromrgb are
+        left out once the fade-in is over (progan/learner.py:1064-1095)."""
+        adam_gan = configure_optimizer_for_gan(self.config, optimizer=self._optimizer)
         fade = self.gen_model.fade_in_phase
         self._graph_gen = getattr(self, '_graph_gen', 0) + 1    # ... and at the old optimisers' moment buffers
         self.opt_gen = adam_gan(params=list(self.gen_model.most_parameters(excluded_params=[] if fade else _EXCL_G)))
@@ -785,7 +779,8 @@ class ProGANLearner(GANLearner):
         (``checkpoint.reference_checkpoint_dict``).  Under data parallelism only rank 0 writes (replicas are identical),
         through a temporary file + ``os.replace``; every rank waits for the file to be complete (``sync=False``: no
         barrier - the interrupt path, where the ranks are not at the same point of the step)."""
-        from .. import checkpoint as ckpt
+        from .. import checkpoint as ckpt, optim
+        optim.check_save_format(self._optimizer, reference_format)
         if self.not_trained_yet and reference_format:
             raise Exception('Please train your model for atleast 1 iteration before saving.')
         if parallel.rank() == 0:
@@ -800,12 +795,13 @@ class ProGANLearner(GANLearner):
             parallel.barrier()
 
     def _plain_checkpoint_dict(self):
-        from .. import checkpoint as ckpt
+        from .. import checkpoint as ckpt, optim
         cpu = lambda sd: {k: v.detach().cpu() for k, v in sd.items()}  # noqa: E731
         lagged = self.materialize_lagged_generator() if self.config.use_ewma_gen else None
         tcpu = lambda v: None if v is None else v.detach().cpu()  # noqa: E731
         ck = {
-            'config': ckpt.saved_config_fields({k: v for k, v in vars(self.config).items() if not k.startswith('_') and
+            'config': ckpt.saved_config_fields({k: v for k, v in optim.saved_config_fields(vars(self.config), self._optimizer).items()
+                                                if not k.startswith('_') and
                                                 isinstance(v, (int, float, str, bool, dict, list, tuple, type(None)))}),
             'curr_res': self.gen_model.curr_res,
             'alpha': self.gen_model.alpha,
@@ -849,6 +845,8 @@ class ProGANLearner(GANLearner):
         from .. import checkpoint as ckpt
         ck = ckpt.load_checkpoint(load_path, dev_of_saved_model)
         ref = ckpt.is_reference_format(ck)
+        from .. import optim
+        optim.check_saved_optimizer(ck.get('optimizer'), self._optimizer)
         ckpt.check_architecture(ckpt.config_dict(ck), self.config)
         self._family.reset_state()
         self.gen_model, self.disc_model = self._build_networks()
@@ -883,7 +881,7 @@ class ProGANLearner(GANLearner):
         mg, md = ck.get('opt_gen_state_dict'), ck.get('opt_disc_state_dict')
         if ref:
             mg, md = ckpt.moments_from_torch_adam(mg, g_names), ckpt.moments_from_torch_adam(md, d_names)
-        if mg is not None and mg.get('exp_avg'):
+        if mg is not None and mg.get('step'):
             self.opt_gen.import_moments(self.gen_model.named_parameters(), mg)
             self.opt_disc.import_moments(self.disc_model.named_parameters(), md)
         for k in ('sched_stop_step', 'curr_dataset_batch_num', 'curr_epoch_num', 'tot_num_epochs', 'dataset_sz',

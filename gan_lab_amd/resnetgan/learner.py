@@ -38,7 +38,7 @@ from .._int import FMAP_SAMPLES, LearnerConfigCopy, get_current_configuration  #
 from ..optim import ParamArena
 from ..sampling import FROM_CONFIG
 from ..utils import backprop_utils as bp
-from ..utils.backprop_utils import configure_adam_for_gan
+from ..utils.backprop_utils import configure_optimizer_for_gan
 from ..utils.custom_layers import LeakyReLU, Tanh, make_downsampler, make_upsampler
 from ..utils.latent_utils import gen_rand_latent_vars
 
@@ -244,15 +244,9 @@ class GANLearner(object):
             self.gen_ema.rebind(self.gen_model, self.arena_g)
 
     def _set_optimizer(self):
-        """resnetgan/learner.py:884-908: Adam through configure_adam_for_gan; the others are not implemented
-        upstream either."""
-        if self._optimizer != 'adam':
-            if self._optimizer in ('rmsprop', 'momentum', 'sgd'):
-                raise NotImplementedError(f'{self._optimizer} optimizer not yet implemented.')
-            raise ValueError("config does not support this optimizer.\nSupported Optimizers are: "
-                             "[ 'adam', 'rmsprop', 'momentum', 'sgd' ]")
-        c = self.config
-        adam_gan = configure_adam_for_gan(lr_base=c.lr_base, betas=(c.beta1, c.beta2), eps=c.eps, wd=c.wd)
+        """resnetgan/learner.py:884-908, with every ``config.optimizer`` value built (the reference stops at Adam): the fused arena
+        optimiser of that name through configure_optimizer_for_gan, which validates ``momentum`` / ``rmsprop_momentum``."""
+        adam_gan = configure_optimizer_for_gan(self.config, optimizer=self._optimizer)
         self._graph_gen = getattr(self, '_graph_gen', 0) + 1
         self.opt_gen = adam_gan(params=list(self.gen_model.parameters()))
         self.opt_disc = adam_gan(params=list(self.disc_model.parameters()))
@@ -702,6 +696,8 @@ class GANLearner(object):
                                       reference_format)
         from .. import sampling
         sampling.check_save_format(self.gen_ema is not None, reference_format)
+        from .. import optim
+        optim.check_save_format(self._optimizer, reference_format)
         if reference_format:
             raise NotImplementedError('the ResNet GAN learner writes plain-data checkpoints only')
         if self.not_trained_yet:
@@ -713,8 +709,8 @@ class GANLearner(object):
         ck = {
             'config': ckpt.saved_config_fields({k: v for k, v in
                                                 conditional.saved_config_fields(consistency.saved_config_fields(
-                                                    quantize.saved_config_fields(
-                                                        sampling.saved_config_fields(vars(self.config))))).items()
+                                                    quantize.saved_config_fields(sampling.saved_config_fields(
+                                                        optim.saved_config_fields(vars(self.config), self._optimizer))))).items()
                                                 if not k.startswith('_') and
                                                 isinstance(v, (int, float, str, bool, dict, list, tuple, type(None))) and
                                                 not (k in ('self_attention', 'cgan') and v is None) and
@@ -743,6 +739,8 @@ class GANLearner(object):
     def load_model(self, load_path, dev_of_saved_model='cpu'):
         from .. import checkpoint as ckpt
         ck = ckpt.load_checkpoint(load_path, dev_of_saved_model)
+        from .. import optim
+        optim.check_saved_optimizer(ck.get('optimizer'), self._optimizer)
         self.gen_model.load_state_dict(ck['gen_model_state_dict'])
         self.disc_model.load_state_dict(ck['disc_model_state_dict'])
         self.gen_model.to(self.config.dev)

@@ -127,3 +127,37 @@ def configure_adam_for_gan(lr_base, betas: tuple, eps=1.e-8, wd=0):
     assert isinstance(betas, tuple)
     from ..optim import FusedAdam
     return partial(FusedAdam, lr=lr_base, betas=betas, eps=eps, weight_decay=wd)
+
+
+def _unit_interval(config, name, default):
+    v = getattr(config, name, default)
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < 1:
+        raise ValueError(f'config.{name} must be a number in [0, 1) (got {v!r})')
+    return float(v)
+
+
+def configure_optimizer_for_gan(config, optimizer=None):
+    """``config.optimizer`` -> the constructor of its fused arena optimiser (optim.py), taking ``params=``.  'adam' is
+    ``configure_adam_for_gan`` unchanged; 'rmsprop' reads alpha = ``beta2`` and momentum = ``rmsprop_momentum``; 'momentum' is SGD
+    with ``momentum`` (which must be > 0); 'sgd' is SGD without; 'oadam' is optimistic Adam with Adam's fields.  ``lr_base``,
+    ``eps`` and ``wd`` are shared.  ``optimizer``: the learner's current value where it was redefined after construction
+    (default: ``config.optimizer``).  Raises ValueError naming the field for a value outside its range or an unknown optimiser."""
+    from .. import optim
+    name = str(config.optimizer if optimizer is None else optimizer).casefold()
+    if name not in optim.OPTIMIZERS:
+        raise ValueError("config does not support this optimizer.\nSupported Optimizers are: "
+                         "[ 'adam', 'rmsprop', 'momentum', 'sgd', 'oadam' ]")
+    momentum = _unit_interval(config, 'momentum', 0.9)
+    rmsprop_momentum = _unit_interval(config, 'rmsprop_momentum', 0.0)
+    c = config
+    if name == 'adam':
+        return configure_adam_for_gan(lr_base=c.lr_base, betas=(c.beta1, c.beta2), eps=c.eps, wd=c.wd)
+    if name == 'oadam':
+        return partial(optim.FusedOptimisticAdam, lr=c.lr_base, betas=(c.beta1, c.beta2), eps=c.eps, weight_decay=c.wd)
+    if name == 'rmsprop':
+        return partial(optim.FusedRMSprop, lr=c.lr_base, alpha=c.beta2, eps=c.eps, weight_decay=c.wd, momentum=rmsprop_momentum)
+    if name == 'momentum':
+        if momentum == 0:
+            raise ValueError("config.momentum must be > 0 with optimizer='momentum' (plain SGD is optimizer='sgd')")
+        return partial(optim.FusedSGD, lr=c.lr_base, momentum=momentum, weight_decay=c.wd)
+    return partial(optim.FusedSGD, lr=c.lr_base, momentum=0.0, weight_decay=c.wd)

@@ -488,6 +488,31 @@ int ganlab_randn_dev_f32(float* out, long long n, uint64_t seed, const void* bas
 int ganlab_adam_dev_f32(float* p, const float* g, float* m, float* v, long long n, const float* lr_bc1_bc2, float beta1,
                         float beta2, float eps, float wd, void* stream);
 
+/* ---- the other fused arena optimisers (csrc/optim.hip; optim.py FusedRMSprop / FusedSGD / FusedOptimisticAdam) ----------
+ * One launch over a flat run of n floats each; 16-byte accesses where every buffer is 16-byte aligned, scalar ones for the
+ * last n % 4 elements.  No atomics: results are bitwise reproducible.  g' = g + wd p throughout.
+ * rmsprop (torch.optim.RMSprop, centered=False): sq = alpha sq + (1 - alpha) g'^2; d = g' / (sqrt(sq) + eps);
+ *   momentum > 0: buf = momentum buf + d, p -= lr buf; momentum == 0: p -= lr d and `buf` may be NULL.
+ * sgd (torch.optim.SGD, dampening 0, no Nesterov): momentum > 0: buf = first ? g' : momentum buf + g', p -= lr buf;
+ *   momentum == 0: p -= lr g' and `buf` may be NULL.
+ * oadam (optimistic Adam, Daskalakis et al. 2018, Algorithm 1): m, v, bc1, bc2 as in ganlab_adam_f32;
+ *   d = (m / bc1) / (sqrt(v) rsqrt(bc2) + eps); p -= 2 lr d - lr prev; prev = d.
+ * The *_dev forms read their per-step scalars from the same 3-float block ganlab_adam_dev_f32 reads:
+ *   slot 0 = lr for all three; slots 1, 2 = (bc1, bc2) for oadam; slot 1 = `first` for sgd (1.0 on step 1, else 0.0; slot 2
+ *   unused); rmsprop reads slot 0 only. */
+int ganlab_rmsprop_f32(float* p, const float* g, float* sq, float* buf, long long n, float lr, float alpha, float eps, float wd,
+                       float momentum, void* stream);
+int ganlab_rmsprop_dev_f32(float* p, const float* g, float* sq, float* buf, long long n, const float* lr_x_x, float alpha,
+                           float eps, float wd, float momentum, void* stream);
+int ganlab_sgd_f32(float* p, const float* g, float* buf, long long n, float lr, float wd, float momentum, int first,
+                   void* stream);
+int ganlab_sgd_dev_f32(float* p, const float* g, float* buf, long long n, const float* lr_first_x, float wd, float momentum,
+                       void* stream);
+int ganlab_oadam_f32(float* p, const float* g, float* m, float* v, float* prev, long long n, float lr, float beta1, float beta2,
+                     float eps, float wd, float bc1, float bc2, void* stream);
+int ganlab_oadam_dev_f32(float* p, const float* g, float* m, float* v, float* prev, long long n, const float* lr_bc1_bc2,
+                         float beta1, float beta2, float eps, float wd, void* stream);
+
 
 /* ---- DiffAugment (Zhao et al. 2020): differentiable augmentation of the critic's inputs (csrc/augment.hip) ---------------
  * x, y: (N, 3, H, W), W % 4 == 0, N <= 65535.  params: (N, 8) rows (b, s, c, tx, ty, ox, oy, 0); policy: OR of the bits below,
