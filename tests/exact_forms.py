@@ -823,7 +823,8 @@ UNREACHED = [
     ('conv_s2_down_kernel / conv_s2_up_kernel at the thin rolling shapes', 'GANLAB_S2_ROLL=0'),
     ('conv_wgrad_kernel / conv_s2_wgrad_kernel at the rolling shapes', 'GANLAB_WGRAD_ROLL=0'),
 ]
-# kernels of the seven files that are no convolution: packing, the toRGB / style pointwise kernels of mod.hip (tests/test_gpu_ops.py)
+# kernels of the seven files that are no convolution: packing (tests/test_gpu_ops.py), and the toRGB / style pointwise kernels of
+# mod.hip - by name against float64 in tests/test_gpu_mod.py (restated in tests/mod_reference.py)
 NOT_CONV = ['pack_kernel', 'pack_s2_kernel', 'rm_torgb_prep_kernel', 'rm_torgb_wgrad_kernel', 'in_affine_kernel', 'rm_torgb_fwd_kernel',
             'rm_torgb_cross_kernel', 'rm_torgb_cross_finish_kernel']
 

@@ -925,7 +925,9 @@ def test_deferred_instancenorm_chain_equals_composed(ops, shape, monkeypatch):
     (deferred) -> thin plain 3x3 layer that applies the affine while staging its input and has noise + bias + LeakyReLU +
     statistics in its epilogue -> (deferred) -> toRGB with per-sample weights - against the SAME chain composed from the round-1 ops
     (layer_tail: two passes; conv2d; layer_tail; conv2d 1x1): image and every gradient (input, both conv weights, biases,
-    noise weights, styles).  Reference semantics: stylegan/architectures.py:497-526."""
+    noise weights, styles).  Reference semantics: stylegan/architectures.py:497-526.
+    This compares one GPU path with another; the comparison with float64 - every kernel of csrc/mod.hip by name, and the deferred
+    chain against the materialised definition on near-constant planes - lives in tests/test_gpu_mod.py."""
     n, c0, h, w, c1 = shape
     gen = torch.Generator().manual_seed(zlib.crc32(repr(shape).encode()))
 
