@@ -94,7 +94,7 @@ def k_diffaug(x, params, policy, adjoint=False):
     return out
 
 
-ADA_ROW, ADA_COUNTERS = 32, 8        # GANLAB_ADA_ROW, GANLAB_ADA_COUNTERS (include/ganlab_hip.h)
+ADA_ROW, ADA_COUNTERS = _lib.DEFINES['GANLAB_ADA_ROW'], _lib.DEFINES['GANLAB_ADA_COUNTERS']
 
 
 def ada_params(n, h, w, state, policy, seed, offset, device):
@@ -131,8 +131,8 @@ def k_ada(x, params, adjoint=False):
     return out
 
 
-ADA_EXT_ROW, ADA_EXT_COUNTERS, ADA_FILTER_TAPS = 16, 4, 43      # GANLAB_ADA_EXT_ROW, ..._EXT_COUNTERS, ..._FILTER_TAPS
-ADA_FILTER, ADA_NOISE, ADA_CUTOUT = 8, 16, 32       # GANLAB_ADA_FILTER, GANLAB_ADA_NOISE, GANLAB_ADA_CUTOUT
+ADA_EXT_ROW, ADA_EXT_COUNTERS, ADA_FILTER_TAPS, ADA_FILTER, ADA_NOISE, ADA_CUTOUT = (
+    _lib.DEFINES['GANLAB_ADA_' + n] for n in ('EXT_ROW', 'EXT_COUNTERS', 'FILTER_TAPS', 'FILTER', 'NOISE', 'CUTOUT'))
 ADA_NEW_GROUPS = ADA_FILTER | ADA_NOISE | ADA_CUTOUT
 
 

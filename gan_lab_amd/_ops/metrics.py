@@ -10,7 +10,7 @@ from .core import _c, _ct, _new, _p, _st
 
 
 # ---- sliced Wasserstein distance (csrc/swd.hip; composed in gan_lab_amd/swd.py) ----------------------------------------------
-SWD_DESC = 147                       # GANLAB_SWD_DESC (include/ganlab_hip.h)
+SWD_DESC = _lib.DEFINES['GANLAB_SWD_DESC']
 
 
 def _swd_planes(x, what):
@@ -157,7 +157,7 @@ def swd_directions(n_dirs, seed, offset, device):
 
 
 # ---- k-nearest-neighbour precision / recall / density / coverage (csrc/prdc.hip; composed in gan_lab_amd/prdc.py) --------------
-PRDC_MAX_K = 16                      # GANLAB_PRDC_MAX_K (include/ganlab_hip.h)
+PRDC_MAX_K = _lib.DEFINES['GANLAB_PRDC_MAX_K']
 
 
 def _prdc_rows(t, what):
@@ -275,9 +275,9 @@ def kid_rowsums(queries, keys, gamma, coef0=1.0, exclude_diag=False, out=None):
 
 
 # ---- perceptual path length (csrc/ppl.hip; composed in gan_lab_amd/ppl.py) -----------------------------------------------------
-PPL_MAX_DIM = 4096                   # GANLAB_PPL_MAX_DIM (include/ganlab_hip.h)
-PPL_MODES = {'lerp': 0, 'slerp': 1}                  # GANLAB_PPL_LERP / _SLERP
-PPL_SAMPLINGS = {'full': 0, 'end': 1}                # GANLAB_PPL_FULL / _END
+PPL_MAX_DIM = _lib.DEFINES['GANLAB_PPL_MAX_DIM']
+PPL_MODES = {'lerp': _lib.DEFINES['GANLAB_PPL_LERP'], 'slerp': _lib.DEFINES['GANLAB_PPL_SLERP']}
+PPL_SAMPLINGS = {'full': _lib.DEFINES['GANLAB_PPL_FULL'], 'end': _lib.DEFINES['GANLAB_PPL_END']}
 PPL_RECORD = ('mean', 'lo', 'hi', 'kept', 'nonfinite')
 
 
@@ -356,7 +356,7 @@ def trimmed_mean(v, q_lo=0.01, q_hi=0.99):
 
 
 # ---- multi-scale structural similarity (csrc/msssim.hip; composed in gan_lab_amd/msssim.py) -------------------------------------
-MSSSIM_LEVELS = 5                    # GANLAB_MSSSIM_LEVELS (include/ganlab_hip.h)
+MSSSIM_LEVELS = _lib.DEFINES['GANLAB_MSSSIM_LEVELS']
 
 
 def _msssim_images(t, side, what):
@@ -423,8 +423,8 @@ def msssim_finish(workspace, pairs, res, table, values, out):
 
 
 # ---- radial power spectrum (csrc/spectrum.hip; composed in gan_lab_amd/spectrum.py) ---------------------------------------------
-SPECTRUM_MIN_RES, SPECTRUM_MAX_RES = 16, 1024        # GANLAB_SPECTRUM_MIN_RES / _MAX_RES (include/ganlab_hip.h)
-SPECTRUM_WINDOWS = {'none': 0, 'hann': 1}            # GANLAB_SPECTRUM_WINDOW_*
+SPECTRUM_MIN_RES, SPECTRUM_MAX_RES = _lib.DEFINES['GANLAB_SPECTRUM_MIN_RES'], _lib.DEFINES['GANLAB_SPECTRUM_MAX_RES']
+SPECTRUM_WINDOWS = {'none': _lib.DEFINES['GANLAB_SPECTRUM_WINDOW_NONE'], 'hann': _lib.DEFINES['GANLAB_SPECTRUM_WINDOW_HANN']}
 
 
 def _spectrum_size(query, count, res, what):

@@ -18,7 +18,7 @@ from .cr import _first_order
 # projection into StyleGAN's latent space (csrc/project.hip; project.py): the multi-scale reconstruction loss, the moments of W,
 # the latent update
 # ---------------------------------------------------------------------------------------------- #
-PYRAMID_MAX_LEVELS = 6                               # GANLAB_PYRAMID_MAX_LEVELS (include/ganlab_hip.h)
+PYRAMID_MAX_LEVELS = _lib.DEFINES['GANLAB_PYRAMID_MAX_LEVELS']
 PROJECT_SCHEDULE = {'lr0': 0.1, 'initial_noise_factor': 0.05, 'lr_rampdown_length': 0.25, 'lr_rampup_length': 0.05,
                     'noise_ramp_length': 0.75}       # the StyleGAN2 projector's defaults
 

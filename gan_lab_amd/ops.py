@@ -117,7 +117,7 @@ _PACK_SERIAL = [0]
 _PACK_GEN = [0]          # bumped when buffers a captured graph may point at are dropped: full flush, table rebuild
 _PACK_RANGES = {}        # (lo, hi) byte range -> serial of its last rewrite
 _PACK_TABLES = {}        # (lo, hi) -> (entry keys, device descriptor table, total blocks)
-_KIND_PLAIN, _KIND_S2, _KIND_BF16, _KIND_X3 = 0, 1, 2, 3      # GANLAB_PACKKIND_* (include/ganlab_hip.h)
+_KIND_PLAIN, _KIND_S2, _KIND_BF16, _KIND_X3 = (_lib.DEFINES['GANLAB_PACKKIND_' + n] for n in ('PLAIN', 'S2', 'BF16', 'X3'))
 # The kernel families a conv can run on (``conv_route``): bf16 compute; split products plain, transposed (an up layer's forward, a
 # pooled layer's input gradient) and strided (the other two); exact stride-2; the long-contraction linear run as a weight gradient;
 # exact fp32.  A family that packs weights has the row of its name below.
