@@ -1,7 +1,8 @@
-"""Launchers of the validation metrics.  No autograd: metrics run under ``torch.no_grad``.
+"""Launchers of the validation metrics.  No autograd: metrics run under ``torch.no_grad`` - except the power-spectrum regulariser
+at the end (``spectrum_loss``), the one metric that is also a loss term and the one ``autograd.Function`` here.
 
 Drives csrc/swd.hip, csrc/prdc.hip, csrc/frechet.hip, csrc/kid.hip, csrc/ppl.hip, csrc/msssim.hip and csrc/spectrum.hip; composed
-in gan_lab_amd/swd.py, prdc.py, frechet.py, kid.py, ppl.py, msssim.py and spectrum.py.  Re-exported by ``gan_lab_amd.ops``."""
+in gan_lab_amd/swd.py, prdc.py, frechet.py, kid.py, ppl.py, msssim.py, spectrum.py and spectrum_reg.py.  Re-exported by ``gan_lab_amd.ops``."""
 import torch
 
 from .. import _lib
@@ -494,3 +495,147 @@ def spectrum_finish(workspace_a, workspace_b, n_images, res, out):
     check(_lib.lib().ganlab_spectrum_finish_f64(_p(workspace_a), _p(workspace_b), workspace_a.numel() * 8, int(n_images), int(res),
                                                 _p(out), out.numel() * 8, _st()), 'spectrum_finish')
     return out
+
+
+# ---- the power-spectrum regulariser (csrc/spectrum.hip; composed in gan_lab_amd/spectrum_reg.py) ----------------
+SPECTRUM_BANDS = {'all': _lib.DEFINES['GANLAB_SPECTRUM_BAND_ALL'], 'hf': _lib.DEFINES['GANLAB_SPECTRUM_BAND_HF']}
+_SPECTRUM_REG_SCRATCH_BYTES = 64 << 20      # the half spectra of one chunk of images, forward and backward alike
+
+
+def _spectrum_batch(x, what):
+    """``x`` as the spectrum kernels walk it: a (N, 3, R, R) fp32 GPU batch whose images are contiguous blocks a fixed number of
+    floats apart - a whole batch or a slice of one along dim 0, taken as it is; anything else is made contiguous."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+        _c(x, what)
+    if x.dim() != 4 or x.shape[0] < 1 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        raise ValueError(f'{what}: needs a (N, 3, R, R) batch, got {tuple(x.shape)}')
+    res = int(x.shape[2])
+    if res < SPECTRUM_MIN_RES or res > SPECTRUM_MAX_RES or res & (res - 1):
+        raise ValueError(f'{what}: R must be a power of two in [{SPECTRUM_MIN_RES}, {SPECTRUM_MAX_RES}], got {res}')
+    if tuple(x.stride()[1:]) != (res * res, res, 1) or (x.shape[0] > 1 and x.stride(0) < 3 * res * res):
+        x = x.contiguous()
+    return x, res
+
+
+def _spectrum_chunk(res, n, chunk):
+    if chunk is None:
+        per_image = spectrum_scratch_bytes(2, res) - spectrum_scratch_bytes(1, res)
+        return max(1, min(n, _SPECTRUM_REG_SCRATCH_BYTES // per_image))
+    if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:
+        raise ValueError(f'spectrum: chunk must be a positive integer or None, got {chunk!r}')
+    return min(n, chunk)
+
+
+def _spectrum_window(window, what):
+    if window not in SPECTRUM_WINDOWS:
+        raise ValueError(f'{what}: window must be one of {sorted(SPECTRUM_WINDOWS)}, got {window!r}')
+    return window
+
+
+def _spectrum_profiles(x, res, window, chunk):
+    """The (N, res / 2 + 1) per-image profiles of ``x``, walked ``chunk`` images at a time through one scratch."""
+    n = int(x.shape[0])
+    ws = spectrum_workspace(n, res, x.device)
+    scratch = spectrum_scratch(chunk, res, x.device)
+    for off in range(0, n, chunk):
+        spectrum_feed(x[off:off + chunk], res, window, scratch, ws, off, n)
+    return ws
+
+
+def spectrum_profile_mean(x, window='hann', chunk=None):
+    """The set profile ``S`` of a (N, 3, R, R) fp32 batch: a (R/2 + 1,) fp64 device tensor (the images in index order; no host
+    read).  No autograd."""
+    window = _spectrum_window(window, 'spectrum_profile_mean')
+    x, res = _spectrum_batch(x.detach() if isinstance(x, torch.Tensor) else x, 'spectrum_profile_mean x')
+    n = int(x.shape[0])
+    ws = _spectrum_profiles(x, res, window, _spectrum_chunk(res, n, chunk))
+    out = torch.empty(res // 2 + 1, dtype=torch.float64, device=x.device)
+    check(_lib.lib().ganlab_spectrum_reg_target_f64(_p(ws), ws.numel() * 8, n, res, 0.0, 1, _p(out), _st()), 'spectrum_reg_target')
+    return out
+
+
+def spectrum_target_update(x, target, decay, first, window='hann', chunk=None):
+    """``target <- decay target + (1 - decay) S(x)`` in place (``first``: ``target <- S(x)``), one small kernel behind the
+    profiles; no host read.  What ``SpectrumRegulariser.observe`` runs in the critic step (DESIGN.md 4.9b lists it with the ops)."""
+    window = _spectrum_window(window, 'spectrum_target_update')
+    x, res = _spectrum_batch(x.detach() if isinstance(x, torch.Tensor) else x, 'spectrum_target_update x')
+    target = _ct(target, torch.float64, 'spectrum_target_update target')
+    if not target.is_contiguous() or tuple(target.shape) != (res // 2 + 1,):
+        raise ValueError(f'spectrum_target_update: target must be a contiguous ({res // 2 + 1},) tensor, got {tuple(target.shape)}')
+    if not 0.0 <= float(decay) < 1.0:
+        raise ValueError(f'spectrum_target_update: decay must be in [0, 1), got {decay!r}')
+    n = int(x.shape[0])
+    ws = _spectrum_profiles(x, res, window, _spectrum_chunk(res, n, chunk))
+    check(_lib.lib().ganlab_spectrum_reg_target_f64(_p(ws), ws.numel() * 8, n, res, float(decay), 1 if first else 0, _p(target),
+                                                    _st()), 'spectrum_reg_target')
+    return target
+
+
+class _SpectrumLossBwd(torch.autograd.Function):
+    """The gradients ``_SpectrumLoss.backward`` computed, tied to its inputs: differentiating them - a second differentiation of the
+    loss - raises by the op's name."""
+
+    @staticmethod
+    def forward(ctx, x, gout, gx):
+        return gx.view_as(gx)
+
+    @staticmethod
+    def backward(ctx, gg):
+        raise RuntimeError('gan_lab_amd.ops.spectrum_loss is first order only: its backward was asked to differentiate twice (no '
+                           'double backward is provided; keep it out of create_graph=True penalties)')
+
+
+class _SpectrumLoss(torch.autograd.Function):
+    """L(S(x), T) -> 0-dim fp32; the backward recomputes the half spectrum chunk by chunk (nothing but ``x`` and R/2 + 1 doubles is
+    kept between the two)."""
+
+    @staticmethod
+    def forward(ctx, x, target, band, window, chunk):
+        res, n = int(x.shape[2]), int(x.shape[0])
+        ws = _spectrum_profiles(x, res, window, chunk)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        coef = torch.empty(res // 2 + 1, dtype=torch.float64, device=x.device)
+        check(_lib.lib().ganlab_spectrum_reg_finish_f64(_p(ws), ws.numel() * 8, n, res, SPECTRUM_WINDOWS[window],
+                                                        SPECTRUM_BANDS[band], _p(target), _p(loss), _p(coef), _st()),
+              'spectrum_reg_finish')
+        ctx.save_for_backward(x, coef)
+        ctx.window, ctx.chunk = window, chunk
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, coef = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        res, n, chunk = int(x.shape[2]), int(x.shape[0]), ctx.chunk
+        g = _c(gout.detach(), 'spectrum_loss cotangent')
+        gx = torch.empty((n, 3, res, res), dtype=torch.float32, device=x.device)
+        L = _lib.lib()
+        nbytes = L.ganlab_spectrum_reg_scratch(chunk, res)
+        scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+        stride = x.stride(0) if n > 1 else 3 * res * res
+        xd = x.detach()
+        for off in range(0, n, chunk):
+            count = min(chunk, n - off)
+            check(L.ganlab_spectrum_reg_backward_f32(_p(xd[off:off + count]), stride, count, res, SPECTRUM_WINDOWS[ctx.window],
+                                                     _p(coef), _p(g), _p(gx[off:off + count]), _p(scratch), scratch.numel() * 8,
+                                                     _st()), 'spectrum_reg_backward')
+        if torch.is_grad_enabled():
+            gx = _SpectrumLossBwd.apply(x, gout, gx)
+        return gx, None, None, None, None
+
+
+def spectrum_loss(x, target, band='all', window='hann', chunk=None):
+    """``mean_{k in band} (ln max(S[k], 1e-30) - ln max(target[k], 1e-30))^2`` of the set profile S of the (N, 3, R, R) fp32 batch
+    ``x`` against the (R/2 + 1,) fp64 device profile ``target``: a 0-dim fp32 device tensor.  ``band``: 'all' (k = 1 .. R/2) or
+    'hf' (k = R/4+1 .. R/2).  Differentiable ONCE in ``x`` (a second differentiation raises); ``target`` gets no gradient and is
+    not written.  ``chunk``: images per pass through the scratch (None: as many as 64 MiB of half spectra hold)."""
+    window = _spectrum_window(window, 'spectrum_loss')
+    if band not in SPECTRUM_BANDS:
+        raise ValueError(f'spectrum_loss: band must be one of {sorted(SPECTRUM_BANDS)}, got {band!r}')
+    x, res = _spectrum_batch(x, 'spectrum_loss x')
+    target = _ct(target, torch.float64, 'spectrum_loss target')
+    if tuple(target.shape) != (res // 2 + 1,):
+        raise ValueError(f'spectrum_loss: target must hold the {res // 2 + 1} bins of a {res} x {res} image, got '
+                         f'{tuple(target.shape)}')
+    return _SpectrumLoss.apply(x, target.detach(), band, window, _spectrum_chunk(res, int(x.shape[0]), chunk))

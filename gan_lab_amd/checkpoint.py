@@ -217,9 +217,13 @@ def reference_config_fields(config):
     gen_metrics = getattr(config, 'gen_metrics', None)
     off = tuple(s.name + '_' for s in validation.SCORERS if not s.module.wanted(gen_metrics))    # a set metric's fields: '<name>_*'
     from . import optim         # (``momentum`` / ``rmsprop_momentum``: this package's own, never written under Adam)
+    # ``spectrum_reg*`` share the 'spectrum' row's prefix and go with its fields; while the regulariser is on they are written
+    # whether or not the metric is wanted
+    from . import spectrum_reg
+    reg = spectrum_reg.FIELDS if getattr(config, 'spectrum_reg', 0) else ()
     return saved_config_fields({k: v for k, v in optim.saved_config_fields(vars(config)).items()
                                 if not (k == 'diffaugment' and v is None) and
-                                not (k in ('self_attention', 'cgan') and v is None) and not k.startswith(off)})
+                                not (k in ('self_attention', 'cgan') and v is None) and (k in reg or not k.startswith(off))})
 
 
 def reference_checkpoint_dict(learner, g_names, d_names, extra=None):

@@ -129,6 +129,16 @@ neither.  ``beta2``'s default differs by model (0.99 for ProGAN / StyleGAN, 0.9 
 these are the user's choice and nothing was tuned here.  A value outside these ranges raises ValueError when the learner is built and
 names its field; a checkpoint saved under one optimiser does not load under another, ``reference_format=True`` needs ``'adam'``,
 and files saved under ``'adam'`` do not carry the two new fields.
+``spectrum_reg`` (ProGAN and StyleGAN; float, 0 = off, finite and >= 0) adds the power-spectrum regulariser of spectrum_reg.py
+(Durall et al. 2020) to the generator's loss: ``spectrum_reg`` times the mean over a band of radii of the squared difference of the
+natural logarithms of the generated batch's radial power spectrum and a target profile, which the critic step keeps as a moving
+average over the real batches with ``spectrum_reg_decay`` (float, default 0.99, in [0, 1); the first batch copies).
+``spectrum_reg_band`` is ``'hf'`` (the default: radii R/4+1 .. R/2, where up-convolution artifacts live) or ``'all'`` (1 .. R/2), the
+'spectrum' metric's own two bands, and the window is that metric's ``spectrum_window``.  The term is computed on the un-augmented
+images, per rank, from 16x16 on (the 4x4 and 8x8 phases launch nothing); the target restarts at a growth event and travels in
+checkpoints only while the option is on; with the option on the learner steps eagerly (no step graphs).  The paper's weight depends
+on its loss normalisation; these are the user's choice and nothing was tuned here.  A negative or non-finite weight, another band or
+a decay outside [0, 1) raises ValueError when the learner is built and names its field; the ResNet GAN has none of the three fields.
 ``--gradient_penalty=none`` on the command line means no penalty (None), as ``make_config(gradient_penalty=None)`` does.
 """
 import argparse
@@ -217,7 +227,8 @@ def _spec(model_type):
                  ('use_equalized_lr', bool, True), ('normalize_z', bool, True), ('mbstd_group_size', int, 4),
                  ('use_ewma_gen', bool, True),
                  ('ppl_samples', int, 1024), ('ppl_space', _str_or_none, None), ('ppl_sampling', str.casefold, 'full'),
-                 ('ppl_epsilon', float, 1e-4), ('ppl_seed', int, 0)]
+                 ('ppl_epsilon', float, 1e-4), ('ppl_seed', int, 0),
+                 ('spectrum_reg', float, 0.), ('spectrum_reg_band', str.casefold, 'hf'), ('spectrum_reg_decay', float, 0.99)]
         if model_type == 'ProGAN':
             rows += [('num_main_iters', int, (NIMG_TRANSITION // BS) * 20),
                      ('lr_fctr_dict', dict, {4: 1., 8: 1., 16: 1., 32: 1., 64: 1., 128: 1., 256: 1., 512: 1.,

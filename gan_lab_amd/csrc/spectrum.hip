@@ -13,6 +13,16 @@
 // The FFT is an in-place radix-2 decimation in frequency whose stages are taken two at a time (a radix-4 pass in registers);
 // output slot s holds frequency bitrev(s), which binning and the Hermitian split look up instead of reordering.
 // No atomics: every result is bitwise reproducible and does not depend on how the images were split over calls.
+//
+// The regulariser (gan_lab_amd/spectrum_reg.py) is the second half of the file: the same forward up to the per-image
+// profiles, then
+//   reg finish  S[k], L = mean_{k in B} (ln S[k] - ln T[k])^2 as one fp32 scalar, and coef[k] = dL/dS[k] / (N members_k 3 R^2 W)
+//   target      T <- decay T + (1 - decay) S, or T <- S
+//   cols bwd    per column tile of the recomputed half spectrum: the column transform again, every coefficient times
+//               coef[bin] dL (the same integer binning), conjugated and put into natural order, transformed once more (the inverse
+//               transform as the forward one on conjugated data) and written back over the tile, unnormalised
+//   rows bwd    two rows of the result are completed by Hermitian symmetry and packed as real and imaginary part of one inverse
+//               transform; times 2 (the 2 R^2 of the adjoint over the two unnormalised inverses) and the window -> dx
 #include <cmath>
 
 #include "common.h"
@@ -323,6 +333,236 @@ int ganlab_spectrum_finish_f64(const void* workspace_a, const void* workspace_b,
   if (out_bytes < (workspace_b ? 4 * NB + 2 : 2 * NB) * sizeof(double)) return GANLAB_EINVAL;
   GL_LAUNCH(spectrum_finish_kernel, dim3(1), dim3(kThreads), 0, gl_stream(stream), reinterpret_cast<const double*>(workspace_a),
             reinterpret_cast<const double*>(workspace_b), out, N, R);
+  return GL_CHECK_LAUNCH();
+}
+
+}  // extern "C"
+
+// ---- the power-spectrum regulariser: L(S, T) and its gradient with respect to the images -----------------------
+namespace {
+
+// the bin of the coefficient (|ku|, |kv|) = (v, m): the k with (2k-1)^2 <= 4 (v^2 + m^2) < (2k+1)^2, as sp_run_lo draws the runs
+__device__ __forceinline__ int sp_bin(int v, int m) {
+  const long long t = 4LL * ((long long)v * v + (long long)m * m);
+  long long k = (long long)((sqrt((double)t) + 1.) * 0.5);
+  while ((2 * k + 1) * (2 * k + 1) <= t) ++k;
+  while (k > 0 && (2 * k - 1) * (2 * k - 1) > t) --k;
+  return (int)k;
+}
+
+// the number of coefficients of bin k (spectrum_profile_kernel's count)
+__device__ inline long long sp_members(int R, int k) {
+  long long members = 0;
+  for (int v = 0; v <= R / 2; ++v) {
+    const int a = sp_run_lo(v, k), b = min(sp_run_lo(v, k + 1), R / 2 + 1);
+    if (b <= a) continue;
+    const int rows = 2 * (b - a) - (a == 0 ? 1 : 0) - (b == R / 2 + 1 ? 1 : 0);
+    members += (v == 0 || v == R / 2 ? 1 : 2) * rows;
+  }
+  return members;
+}
+
+// S[k] exactly as spectrum_finish_kernel forms it: the images in index order, then one division
+__device__ __forceinline__ double sp_set_mean(const double* __restrict__ prof, int N, int NB, int k) {
+  double t = 0.;
+  for (int n = 0; n < N; ++n) t += prof[(long long)n * NB + k];
+  return t / (double)N;
+}
+
+// loss[0] = mean_{k = first .. R/2} (ln max(S[k], floor) - ln max(T[k], floor))^2;  coef[k] = dL/dS[k] inv_norm / (N members_k),
+// 0 outside the band and where S[k] sits on the floor
+__global__ __launch_bounds__(kThreads) void spectrum_reg_finish_kernel(const double* __restrict__ prof,
+                                                                       const double* __restrict__ target, float* __restrict__ loss,
+                                                                       double* __restrict__ coef, int N, int R, int first,
+                                                                       double inv_norm) {
+  __shared__ double sq[kMaxRes / 2 + 1];
+  const int NB = R / 2 + 1;
+  const double band = (double)(R / 2 - first + 1);
+  for (int k = threadIdx.x; k < NB; k += kThreads) {
+    double d2 = 0., c = 0.;
+    if (k >= first) {
+      const double s = sp_set_mean(prof, N, NB, k), t = target[k];
+      const double d = log(s > kDbFloor ? s : kDbFloor) - log(t > kDbFloor ? t : kDbFloor);
+      d2 = d * d;
+      if (s > kDbFloor) c = 2. * d / (band * s) * inv_norm / ((double)N * (double)sp_members(R, k));
+    }
+    sq[k] = d2;
+    coef[k] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.;
+    for (int k = first; k <= R / 2; ++k) t += sq[k];
+    loss[0] = (float)(t / band);
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void spectrum_reg_target_kernel(const double* __restrict__ prof, double* __restrict__ target,
+                                                                       int N, int R, double decay, int first) {
+  const int NB = R / 2 + 1;
+  for (int k = threadIdx.x; k < NB; k += kThreads) {
+    const double s = sp_set_mean(prof, N, NB, k);
+    target[k] = first ? s : decay * target[k] + (1. - decay) * s;
+  }
+}
+
+// half: the row-transformed half spectra of this call's images (spectrum_rows_kernel); on return the unnormalised inverse column
+// transform of coef[bin] dL F in their place.  One workgroup owns its tile's columns of one image: no other touches them.
+template <int R>
+__global__ __launch_bounds__(kThreads) void spectrum_reg_cols_bwd_kernel(float2* __restrict__ half, const float* __restrict__ tab,
+                                                                         const double* __restrict__ coef,
+                                                                         const float* __restrict__ grad_loss) {
+  constexpr int C = sp_cols(R), NB = R / 2 + 1, STRIDE = R + 1, TILES = (NB + C - 1) / C;
+  __shared__ float2 buf[C * STRIDE];
+  __shared__ float2 tw[R / 2];
+  __shared__ float wk[NB];
+  const int tid = threadIdx.x;
+  const long long img = blockIdx.x / TILES;
+  const int tile = (int)(blockIdx.x - img * TILES);
+  const int v0 = tile * C;
+  for (int i = tid; i < R / 2; i += kThreads) tw[i] = float2{tab[R + 2 * i], tab[R + 2 * i + 1]};
+  const double gl = (double)grad_loss[0];
+  for (int k = tid; k < NB; k += kThreads) wk[k] = (float)(coef[k] * gl);
+
+  for (int ch = 0; ch < 3; ++ch) {
+    float2* plane = half + (img * 3 + ch) * (long long)R * NB;
+    __syncthreads();                                // the previous channel's stores have read buf
+    for (int e = tid; e < C * R; e += kThreads) {
+      const int u = e / C, c = e - u * C;
+      buf[c * STRIDE + u] = v0 + c < NB ? plane[(long long)u * NB + v0 + c] : float2{0.f, 0.f};
+    }
+    sp_fft<R>(buf, tw, C, STRIDE);
+    // slot s holds frequency bitrev(s): weight both ends of the swap, conjugate, and leave frequency f in slot f
+    for (int e = tid; e < C * R; e += kThreads) {
+      const int c = e / R, s = e - c * R, f = sp_slot<R>(s);
+      if (f < s) continue;
+      float2* col = buf + c * STRIDE;
+      const float2 a = col[s], b = col[f];          // frequencies f and s
+      const int ka = sp_bin(v0 + c, f < R / 2 ? f : R - f), kb = sp_bin(v0 + c, s < R / 2 ? s : R - s);
+      const float wa = ka <= R / 2 ? wk[ka] : 0.f, wb = kb <= R / 2 ? wk[kb] : 0.f;
+      col[f] = float2{a.x * wa, -(a.y * wa)};
+      col[s] = float2{b.x * wb, -(b.y * wb)};
+    }
+    sp_fft<R>(buf, tw, C, STRIDE);
+    for (int e = tid; e < C * R; e += kThreads) {
+      const int u = e / C, c = e - u * C;
+      if (v0 + c >= NB) continue;
+      const float2 z = buf[c * STRIDE + sp_slot<R>(u)];
+      plane[(long long)u * NB + v0 + c] = float2{z.x, -z.y};
+    }
+  }
+}
+
+// dx[plane][2 r], dx[plane][2 r + 1] from rows 2 r, 2 r + 1 of the plane's half[row][v]; dx is contiguous
+template <int R>
+__global__ __launch_bounds__(kThreads) void spectrum_reg_rows_bwd_kernel(const float2* __restrict__ half, const float* __restrict__ tab,
+                                                                         float* __restrict__ dx, long long pairs) {
+  constexpr int B = kRowElems / R, NB = R / 2 + 1;
+  __shared__ float2 buf[kRowElems];
+  __shared__ float2 tw[R / 2];
+  __shared__ float win[R];
+  const int tid = threadIdx.x;
+  const long long p0 = (long long)blockIdx.x * B;
+  for (int i = tid; i < R; i += kThreads) win[i] = tab[i];
+  for (int i = tid; i < R / 2; i += kThreads) tw[i] = float2{tab[R + 2 * i], tab[R + 2 * i + 1]};
+  __syncthreads();
+  // A0, A1: the spectra of two real rows, A[R - v] = conj A[v], imaginary parts of v = 0 and R/2 dropped.  conj(A0 + i A1) goes in:
+  // the forward transform of it is conj(R (a0 + i a1))
+  for (int e = tid; e < B * R; e += kThreads) {
+    const int b = e / R, v = e - b * R;
+    const long long p = p0 + b;
+    float2 z = float2{0.f, 0.f};
+    if (p < pairs) {
+      const int w = v <= R / 2 ? v : R - v;
+      const float2* src = half + (2 * p) * NB + w;
+      float2 a0 = src[0], a1 = src[NB];
+      if (w == 0 || w == R / 2) a0.y = a1.y = 0.f;
+      if (v > R / 2) { a0.y = -a0.y; a1.y = -a1.y; }
+      z = float2{a0.x - a1.y, -(a0.y + a1.x)};
+    }
+    buf[e] = z;
+  }
+  sp_fft<R>(buf, tw, B, R);
+  for (int e = tid; e < B * R; e += kThreads) {
+    const int b = e / R, j = e - b * R;
+    const long long p = p0 + b;
+    if (p >= pairs) continue;
+    const long long plane = p / (R / 2);
+    const int r = (int)(p - plane * (R / 2));
+    const float2 z = buf[b * R + sp_slot<R>(j)];
+    float* dst = dx + plane * (long long)(R * R) + (long long)(2 * r) * R + j;
+    dst[0] = ((2.f * z.x) * win[j]) * win[2 * r];
+    dst[R] = ((-2.f * z.y) * win[j]) * win[2 * r + 1];
+  }
+}
+
+template <int R>
+void sp_reg_launch(const float* x, long long image_stride, int count, const float* tab, float2* half, const double* coef,
+                   const float* grad_loss, float* dx, hipStream_t st) {
+  const long long pairs = 3LL * count * (R / 2);
+  constexpr int B = kRowElems / R;
+  const dim3 rows((unsigned)((pairs + B - 1) / B));
+  GL_LAUNCH((spectrum_rows_kernel<R>), rows, dim3(kThreads), 0, st, x, image_stride, tab, half, pairs);
+  GL_LAUNCH((spectrum_reg_cols_bwd_kernel<R>), dim3((unsigned)(count * sp_tiles(R))), dim3(kThreads), 0, st, half, tab, coef,
+            grad_loss);
+  GL_LAUNCH((spectrum_reg_rows_bwd_kernel<R>), rows, dim3(kThreads), 0, st, half, tab, dx, pairs);
+}
+
+bool sp_window_ok(int window) { return window == GANLAB_SPECTRUM_WINDOW_NONE || window == GANLAB_SPECTRUM_WINDOW_HANN; }
+
+}  // namespace
+
+extern "C" {
+
+size_t ganlab_spectrum_reg_scratch(int count, int R) {
+  if (count <= 0 || !sp_res_ok(R)) return 0;
+  return sp_tables_bytes(R) + (size_t)count * sp_half_bytes(R);
+}
+
+int ganlab_spectrum_reg_finish_f64(const void* workspace, size_t workspace_bytes, int N, int R, int window, int band,
+                                   const double* target, float* loss, double* coef, void* stream) {
+  if (!workspace || !target || !loss || !coef || N <= 0 || R <= 0 || !sp_window_ok(window) ||
+      (band != GANLAB_SPECTRUM_BAND_ALL && band != GANLAB_SPECTRUM_BAND_HF))
+    return GANLAB_EINVAL;
+  if (!sp_res_ok(R)) return GANLAB_EUNSUPPORTED;
+  if (workspace_bytes < ganlab_spectrum_workspace(N, R)) return GANLAB_EWORKSPACE;
+  const double W = window == GANLAB_SPECTRUM_WINDOW_HANN ? 9. / 64. : 1.;
+  GL_LAUNCH(spectrum_reg_finish_kernel, dim3(1), dim3(kThreads), 0, gl_stream(stream), reinterpret_cast<const double*>(workspace),
+            target, loss, coef, N, R, band == GANLAB_SPECTRUM_BAND_HF ? R / 4 + 1 : 1, 1. / (3. * (double)R * (double)R * W));
+  return GL_CHECK_LAUNCH();
+}
+
+int ganlab_spectrum_reg_target_f64(const void* workspace, size_t workspace_bytes, int N, int R, double decay, int first,
+                                   double* target, void* stream) {
+  if (!workspace || !target || N <= 0 || R <= 0 || !(decay >= 0. && decay < 1.)) return GANLAB_EINVAL;
+  if (!sp_res_ok(R)) return GANLAB_EUNSUPPORTED;
+  if (workspace_bytes < ganlab_spectrum_workspace(N, R)) return GANLAB_EWORKSPACE;
+  GL_LAUNCH(spectrum_reg_target_kernel, dim3(1), dim3(kThreads), 0, gl_stream(stream), reinterpret_cast<const double*>(workspace),
+            target, N, R, decay, first ? 1 : 0);
+  return GL_CHECK_LAUNCH();
+}
+
+int ganlab_spectrum_reg_backward_f32(const float* x, long long image_stride, int count, int R, int window, const double* coef,
+                                     const float* grad_loss, float* dx, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!x || !coef || !grad_loss || !dx || !scratch || count <= 0 || R <= 0 || !sp_window_ok(window)) return GANLAB_EINVAL;
+  if (!sp_res_ok(R)) return GANLAB_EUNSUPPORTED;
+  if (image_stride < 3LL * R * R) return GANLAB_EINVAL;
+  if (scratch_bytes < ganlab_spectrum_reg_scratch(count, R)) return GANLAB_EWORKSPACE;
+  if (3LL * count * (R / 2) > 0x7fffffffLL) return GANLAB_EUNSUPPORTED;
+  hipStream_t st = gl_stream(stream);
+  float* tab = reinterpret_cast<float*>(scratch);
+  float2* half = reinterpret_cast<float2*>(reinterpret_cast<char*>(scratch) + sp_tables_bytes(R));
+  GL_LAUNCH(spectrum_tables_kernel, dim3((R + kThreads - 1) / kThreads), dim3(kThreads), 0, st, tab, R,
+            window == GANLAB_SPECTRUM_WINDOW_HANN ? 1 : 0);
+  switch (R) {
+    case 16: sp_reg_launch<16>(x, image_stride, count, tab, half, coef, grad_loss, dx, st); break;
+    case 32: sp_reg_launch<32>(x, image_stride, count, tab, half, coef, grad_loss, dx, st); break;
+    case 64: sp_reg_launch<64>(x, image_stride, count, tab, half, coef, grad_loss, dx, st); break;
+    case 128: sp_reg_launch<128>(x, image_stride, count, tab, half, coef, grad_loss, dx, st); break;
+    case 256: sp_reg_launch<256>(x, image_stride, count, tab, half, coef, grad_loss, dx, st); break;
+    case 512: sp_reg_launch<512>(x, image_stride, count, tab, half, coef, grad_loss, dx, st); break;
+    default: sp_reg_launch<1024>(x, image_stride, count, tab, half, coef, grad_loss, dx, st); break;
+  }
   return GL_CHECK_LAUNCH();
 }
 

@@ -243,7 +243,8 @@ class GraphedStep(_StepGraphs):
         super().__init__(learner, warmup)
 
     def eligible(self):
-        return super().eligible() and not self.L.gen_model.fade_in_phase
+        # (the power-spectrum regulariser's kernels are not captured: with config.spectrum_reg > 0 every iteration steps eagerly)
+        return super().eligible() and not self.L.gen_model.fade_in_phase and getattr(self.L, 'spectrum_reg', None) is None
 
     def _mix_kwargs(self):
         """The generator's own host draw of the mixing cut, made here so that it can select the graph."""

@@ -12,7 +12,7 @@ name, so ``ops.<name>`` is the one way in for callers:
   _ops/norm.py       BatchNorm (training), LayerNorm, their composed cross-checks
   _ops/loss.py       minibatch stddev, scalar reductions, BCE / hinge / channel-norm penalty
   _ops/attention.py  attention, 2x2 max pool, gated residual
-  _ops/metrics.py    SWD, PRDC, Frechet moments / KID, path length, MS-SSIM, radial spectrum
+  _ops/metrics.py    SWD, PRDC, Frechet moments / KID, path length, MS-SSIM, radial spectrum and its regulariser
   _ops/optim.py      spectral norm, orthogonal regularisation, Adam / RMSprop / SGD / optimistic Adam, EWMA
   _ops/augment.py    random draws, DiffAugment, ADA
   _ops/cond.py       labels, conditional BatchNorm
@@ -75,7 +75,9 @@ from ._ops.metrics import (  # noqa: F401
     _accumulator, moments_accum, kid_rowsums, PPL_MAX_DIM, PPL_MODES, PPL_SAMPLINGS, PPL_RECORD, check_ppl_epsilon, ppl_endpoints,
     row_sqdist, trimmed_mean, MSSSIM_LEVELS, _msssim_images, msssim_workspace, msssim_level, msssim_finish,
     SPECTRUM_MIN_RES, SPECTRUM_MAX_RES, SPECTRUM_WINDOWS, _spectrum_size, spectrum_scratch_bytes, _spectrum_alloc,
-    spectrum_workspace, spectrum_scratch, spectrum_feed, spectrum_finish)
+    spectrum_workspace, spectrum_scratch, spectrum_feed, spectrum_finish, SPECTRUM_BANDS, _spectrum_batch, _spectrum_chunk,
+    _spectrum_window, _spectrum_profiles, spectrum_profile_mean, spectrum_target_update, _SpectrumLossBwd, _SpectrumLoss,
+    spectrum_loss)
 from ._ops.optim import (  # noqa: F401
     SN_EPS, SnTable, sn_refresh, sn_backward, ortho_plan, OrthoTable, ortho_apply, lerp_rows, _adam_operands, adam_step,
     adam_step_dev, _optim_operands, rmsprop_step, rmsprop_step_dev, sgd_step, sgd_step_dev, oadam_step, oadam_step_dev,

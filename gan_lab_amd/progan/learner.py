@@ -242,6 +242,8 @@ class ProGANLearner(GANLearner):
         with torch.no_grad():                    # the generator is frozen in the D step (:752-753)
             xgenb = self._gen_forward(zb, **(gen_kwargs or {}))
         xb = self.fade_in_real(xb)
+        if self.spectrum_reg is not None:        # the target profile follows the reals as the critic sees them, un-augmented
+            self.spectrum_reg.observe(xb)
         gp = self.gradient_penalty
         xr = None
         aug, n = self.critic_aug, xgenb.shape[0]
@@ -305,9 +307,15 @@ class ProGANLearner(GANLearner):
         fake = self._gen_forward(zb, **(gen_kwargs or {}))   # needs G weights only -> overlaps the D all-reduce
         if d_update_pending:
             self._finish_d_update()
+        reg = None
+        if self.spectrum_reg is not None:        # on the un-augmented images; None below the transform's smallest size
+            reg = self.spectrum_reg.loss(fake)
+            self.last_losses['spectrum_reg'] = None if reg is None else reg.detach()     # unweighted; a device tensor
         if self.critic_aug is not None:
             fake = self._augment(fake, aug_params)
         loss = self.loss_func_gen(self.disc_model(fake))
+        if reg is not None:
+            loss = loss + self.spectrum_reg.weight * reg
         self.reducer.arm(self.arena_g)           # buckets go out while the backward is still producing the others
         with ops.direct_param_grads(ops.direct_grads_enabled()):
             loss.backward()
@@ -335,6 +343,8 @@ class ProGANLearner(GANLearner):
         self.batch_size = self.config.bs_dict[self.gen_model.curr_res]
         self._reset_opt_and_sched()
         self._set_loss()
+        if self.spectrum_reg is not None:        # the target profile has the old resolution's bins
+            self.spectrum_reg.reset()
         self.gen_model.alpha = 0
         if self.config.use_ewma_gen and COMPUTE_EWMA_VIA_HALFLIFE:
             self.beta = self.get_smoothing_ewma_beta(half_life=EWMA_SMOOTHING_HALFLIFE)
@@ -507,7 +517,8 @@ class ProGANLearner(GANLearner):
                 if self.log_every and (itr % self.log_every == 0 or itr == num_main_iters - 1):
                     self.last_losses = dict(itr=itr, loss_d=float(loss_d), loss_g=float(loss_g) if loss_g is not None
                                             else None, res=self.gen_model.curr_res, alpha=float(self.gen_model.alpha),
-                                            fade_in=bool(self.gen_model.fade_in_phase), batch=self.batch_size)
+                                            fade_in=bool(self.gen_model.fade_in_phase), batch=self.batch_size,
+                                            **{k: v for k, v in self.last_losses.items() if k == 'spectrum_reg'})
                     if parallel.rank() == 0:
                         print(('%9s' * 6) % (f'{self.curr_epoch_num}', f'{self.gen_model.curr_res}X'
                                              f'{self.gen_model.curr_res}',
@@ -787,20 +798,26 @@ class ProGANLearner(GANLearner):
             g_names, d_names = self._param_name_sets()
             if reference_format:
                 ck = ckpt.reference_checkpoint_dict(self, g_names, d_names, extra=dict(self._extra_checkpoint_fields(),
-                                                                                      **self._ada_checkpoint_fields()))
+                                                                                      **self._ada_checkpoint_fields(),
+                                                                                      **self._spectrum_reg_fields()))
                 ckpt.save_atomic(ck, save_path, foreign=True)
             else:
                 ckpt.save_atomic(self._plain_checkpoint_dict(), save_path)
         if sync:
             parallel.barrier()
 
+    def _spectrum_reg_fields(self):
+        """The regulariser's target profile, only while the option is on: files saved with it off are what they always were."""
+        return {} if self.spectrum_reg is None else self.spectrum_reg.state()
+
     def _plain_checkpoint_dict(self):
-        from .. import checkpoint as ckpt, optim
+        from .. import checkpoint as ckpt, optim, spectrum_reg
         cpu = lambda sd: {k: v.detach().cpu() for k, v in sd.items()}  # noqa: E731
         lagged = self.materialize_lagged_generator() if self.config.use_ewma_gen else None
         tcpu = lambda v: None if v is None else v.detach().cpu()  # noqa: E731
         ck = {
-            'config': ckpt.saved_config_fields({k: v for k, v in optim.saved_config_fields(vars(self.config), self._optimizer).items()
+            'config': ckpt.saved_config_fields({k: v for k, v in spectrum_reg.saved_config_fields(
+                                                optim.saved_config_fields(vars(self.config), self._optimizer)).items()
                                                 if not k.startswith('_') and
                                                 isinstance(v, (int, float, str, bool, dict, list, tuple, type(None)))}),
             'curr_res': self.gen_model.curr_res,
@@ -835,6 +852,7 @@ class ProGANLearner(GANLearner):
         }
         ck.update({k: (tcpu(v) if torch.is_tensor(v) else v) for k, v in self._extra_checkpoint_fields().items()})
         ck.update(self._ada_checkpoint_fields())
+        ck.update(self._spectrum_reg_fields())
         return ck
 
     def load_model(self, load_path, dev_of_saved_model='cpu'):
@@ -873,6 +891,8 @@ class ProGANLearner(GANLearner):
                         self.lagged_params[k].copy_(v.to(self.config.dev))
         self._restore_extra_fields(ck)
         self._restore_ada(ck)
+        if self.spectrum_reg is not None:
+            self.spectrum_reg.restore(ck)
         for attr in ('loss', 'gradient_penalty'):
             if ck.get(attr) is not None:
                 setattr(self, attr, ck[attr])

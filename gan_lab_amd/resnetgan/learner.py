@@ -138,6 +138,10 @@ class GANLearner(object):
         # in the package yet, so a valid fq_codes > 0 is refused and 0 builds nothing
         from .. import quantize
         quantize.require_layer(quantize.validate_config(config))
+        # the power-spectrum regulariser of the progressive generators (config.spectrum_reg*; spectrum_reg.py): None with the weight
+        # at 0 - nothing built, nothing launched; refused on a ResNet GAN config
+        from .. import spectrum_reg
+        self.spectrum_reg = spectrum_reg.from_config(config)
         self.ortho_g = self.ortho_d = None
         self._gradient_penalty = config.gradient_penalty
         self._optimizer = config.optimizer.casefold()

@@ -667,6 +667,26 @@ int ganlab_spectrum_feed_f32(const float* x, long long image_stride, int first, 
 int ganlab_spectrum_finish_f64(const void* workspace_a, const void* workspace_b, size_t workspace_bytes, int N, int R, double* out,
                                size_t out_bytes, void* stream);
 
+/* ---- the power-spectrum regulariser (Durall et al. 2020; csrc/spectrum.hip): with the set profile S of N images
+ * (their per-image profiles in a workspace filled by ganlab_spectrum_feed_f32), a target profile T (R/2 + 1 doubles) and the band
+ * B = 1 .. R/2 (ALL) or R/4+1 .. R/2 (HF),  L = mean_{k in B} (ln max(S[k], 1e-30) - ln max(T[k], 1e-30))^2. */
+#define GANLAB_SPECTRUM_BAND_ALL 0
+#define GANLAB_SPECTRUM_BAND_HF 1
+/* loss[0] = L as fp32; coef[k] = dL/dS[k] / (N members_k 3 R^2 W), R/2 + 1 doubles, 0 outside the band and where S[k] <= 1e-30:
+ * the weight of every |F_c[u,v]|^2 of bin k in L.  fp64, fixed order. */
+int ganlab_spectrum_reg_finish_f64(const void* workspace, size_t workspace_bytes, int N, int R, int window, int band,
+                                   const double* target, float* loss, double* coef, void* stream);
+/* target[k] = S[k] (first != 0), else decay target[k] + (1 - decay) S[k]; decay in [0, 1) */
+int ganlab_spectrum_reg_target_f64(const void* workspace, size_t workspace_bytes, int N, int R, double decay, int first,
+                                   double* target, void* stream);
+/* bytes of the scratch the backward of count images needs: the tables and the half spectra (0: refused) */
+size_t ganlab_spectrum_reg_scratch(int count, int R);
+/* dx (count contiguous (3, R, R) blocks) = grad_loss[0] dL/dx of the count images at x + j image_stride: the half spectrum is
+ * recomputed, weighted by coef[bin] and transformed back (dy_c = 2 R^2 Re IDFT2(G F_c), dx = dy w[i] w[j]).  grad_loss: one fp32
+ * value on the device.  The scratch may be reused by the next call on the same stream. */
+int ganlab_spectrum_reg_backward_f32(const float* x, long long image_stride, int count, int R, int window, const double* coef,
+                                     const float* grad_loss, float* dx, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- real-image input path -----------------------------------------------------------
  * uint8 NHWC dataset images -> 2^k box downsample -> fp32 NCHW ((v/255 - mean[c]) / std[c]); replaces the host
  * chain PIL Image.resize(BOX) -> ToTensor -> Normalize (data_config.py:307-341, progan/learner.py:1099-1112).
